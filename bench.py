@@ -11,11 +11,15 @@ RCCL once before the timed region.  Inputs are resident in HBM when the timed re
 The timed steps rotate over --batches (default 4) DISTINCT resident batches of --reads reads each (4 x 170 MB = 680 MB, more than
 the 256 MiB Infinity Cache), so no step finds its input cached from the step before: the bases really stream from HBM.
 
-One JSON line on rank 0 with the contract fields plus `roofline` (HBM bound; algorithmic bytes = 170 B per
-read: 150 B bases + 4 B offset + 16 B result) and, at N=1, `cpu_baseline` (the oracle = literal restatement
-of src/rkmh.cpp:845-898 with OpenMP, timed on this box's host cores on a bounded sample of the same reads,
-and used to check the GPU rows bit-for-bit), `host_path` (rk_classify_batch from pageable host memory: PCIe inclusive) and `e2e`
-(bin/rkmh stream on a generated FASTQ: parser + PCIe + kernel + TSV, wall clock of the whole process).  Neither is `value`.
+A plain run sets up, warms up, times --steps steps and prints one JSON line on rank 0: the contract fields plus `roofline` (HBM
+bound; algorithmic bytes = 170 B per read: 150 B bases + 4 B offset + 16 B result).  --dump-outputs DIR also writes the rows the
+last timed step computed (dump_outputs).
+
+--full adds everything else the benchmark measures or checks, after the timed steps.  At N=1: `cpu_baseline` (the oracle = literal
+restatement of src/rkmh.cpp:845-898 with OpenMP, timed on the host's cores on a bounded sample of the same reads, and used to check
+the GPU rows bit-for-bit), `host_path` (rk_classify_batch from pageable host memory: PCIe inclusive), `depth_filter` (-M), the legs
+of BASELINE configs 3, 4 and 5, and `e2e` (bin/rkmh stream on a generated FASTQ: parser + PCIe + kernel + TSV, wall clock of the
+whole process).  At N > 1: every rank's rows sampled against the oracle.  None of them is `value`.
 """
 import argparse
 import json
@@ -31,6 +35,7 @@ import torch  # noqa: E402
 
 B_READ = 170.0          # algorithmic bytes per 150 bp read (ASCII input): 150 + 4 + 16
 HBM_PEAK_GBS = 8000.0   # MI355X HBM3E peak (MI355X_MICROARCH.md)
+DUMP_BYTES = 64000000   # --dump-outputs: the files of all ranks together stay below this
 
 
 def usable_cpus():
@@ -57,6 +62,28 @@ def cpu_model():
     except OSError:
         pass
     return "unknown"
+
+
+def dump_outputs(dirname, d_outs, bounds, rank, world):
+    """--dump-outputs: the rows the last timed step computed, as a caller of rk_classify_batch_device receives them (int32 [n, 4]:
+    max_id, max_shared, diff, min_num), written as float64 (exact) to rows.npy, and the global number of the read behind each row
+    to read_index.npy (N > 1: rows_rank<r>.npy, read_index_rank<r>.npy).  d_outs[i] holds the rows of reads bounds[i].  A row
+    takes 40 bytes; more rows than this rank's share of DUMP_BYTES are cut to a fixed, seeded sample (in read order)."""
+    os.makedirs(dirname, exist_ok=True)
+    idx = np.concatenate([np.arange(lo_, hi_, dtype=np.int64) for lo_, hi_ in bounds])
+    cap = (DUMP_BYTES - 4096) // world // 40          # (4096: room for the .npy headers)
+    pick = np.sort(np.random.default_rng(0).choice(len(idx), size=cap, replace=False)) if len(idx) > cap else None
+    parts, at = [], 0
+    for d, (lo_, hi_) in zip(d_outs, bounds):
+        if pick is None:
+            parts.append(d.cpu().numpy())
+        else:
+            sel = pick[(pick >= at) & (pick < at + hi_ - lo_)] - at
+            parts.append(d[torch.from_numpy(sel).to(d.device)].cpu().numpy())
+        at += hi_ - lo_
+    sfx = "" if world == 1 else "_rank%d" % rank
+    np.save(os.path.join(dirname, "rows%s.npy" % sfx), np.concatenate(parts).astype(np.float64))
+    np.save(os.path.join(dirname, "read_index%s.npy" % sfx), (idx if pick is None else idx[pick]).astype(np.float64))
 
 
 def e2e_stream(n, L, rb, ro, synth):
@@ -665,14 +692,19 @@ def main():
                     help="untimed launches before the warm-up steps until the GPU clocks have ramped (a 1 ms kernel measured "
                          "during the first ~50 ms after idle runs 4-12 %% slower); 0 disables")
     ap.add_argument("--reads", type=int, default=1000000, help="reads per GPU per step")
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU-baseline time (0 disables)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the rows the last of them computed to DIR as .npy (float64; see dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every check and informational figure below (CPU baseline and oracle check, "
+                         "host path, -M, configs 3-5, end to end); without it a run measures the timed steps only")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="--full: target CPU-baseline time (0 disables it and the oracle checks)")
     ap.add_argument("--cpu-threads", type=int, default=0)
     ap.add_argument("--batches", type=int, default=4, help="distinct resident batches the timed steps rotate over (>= 4 x 170 MB defeats the 256 MiB Infinity Cache)")
-    ap.add_argument("--no-host-path", action="store_true", help="skip the PCIe-inclusive rk_classify_batch figure (N=1 only)")
-    ap.add_argument("--no-depth-filter", action="store_true", help="skip the -M figures (count pass + masked classify at 200 M slots; N=1 only)")
-    ap.add_argument("--e2e-reads", type=int, default=16000000, help="reads of the generated FASTQ for the bin/rkmh stream end-to-end figure (0 disables; N=1 only)")
-    ap.add_argument("--no-configs", action="store_true", help="skip the informational legs for BASELINE configs 3, 4 and 5 (N=1 only)")
-    ap.add_argument("--no-c4-full", action="store_true", help="skip config 4 at full size (3.1 Gb genome + 10 M reads generated in /tmp, ~40 s)")
+    ap.add_argument("--no-host-path", action="store_true", help="--full: skip the PCIe-inclusive rk_classify_batch figure (N=1 only)")
+    ap.add_argument("--no-depth-filter", action="store_true", help="--full: skip the -M figures (count pass + masked classify at 200 M slots; N=1 only)")
+    ap.add_argument("--e2e-reads", type=int, default=16000000, help="--full: reads of the generated FASTQ for the bin/rkmh stream end-to-end figure (0 disables; N=1 only)")
+    ap.add_argument("--no-configs", action="store_true", help="--full: skip the informational legs for BASELINE configs 3, 4 and 5 (N=1 only)")
+    ap.add_argument("--no-c4-full", action="store_true", help="--full: skip config 4 at full size (3.1 Gb genome + 10 M reads generated in /tmp, ~40 s)")
     ap.add_argument("--c4-genome-mb", type=int, default=3100, help="config 4 at full size: bases of the synthetic genome, in millions")
     ap.add_argument("--c4-reads", type=int, default=10000000, help="config 4 at full size: reads")
     ap.add_argument("--c3-total-reads", type=int, default=100000000,
@@ -745,7 +777,7 @@ def main():
     ns = [hi_ - lo_ for lo_, hi_ in bounds]
     d_bs, d_os, d_outs, qbs, qos = [], [], [], [], []
     for b, (lo_, hi_) in enumerate(bounds):
-        qb, qo = synth.generate_reads_fast(rb, ro, lo_, hi_, read_len=L, threads=min(32, os.cpu_count() or 1))
+        qb, qo = synth.generate_reads_fast(rb, ro, lo_, hi_, read_len=L, threads=min(32, usable_cpus()))
         if not c3_mode or b == 0:
             qbs.append(qb); qos.append(qo)                 # (config 3: only the first batch stays on the host, for the oracle samples)
         d_bs.append(torch.from_numpy(qb).to(dev))
@@ -778,6 +810,7 @@ def main():
             for _ in range(20):
                 step()
             torch.cuda.synchronize()
+        step_no[0] = 0                # the batch of every later step does not depend on how long the ramp took
     for _ in range(a.warmup):
         step()
     torch.cuda.synchronize()
@@ -801,10 +834,14 @@ def main():
 
     if any(bool((d[:, 0] < 0).any().item()) for d in d_outs):
         raise SystemExit("fused path flagged reads for rerouting: the benchmark batch must be fused-eligible")
-    outs = [d.cpu().numpy() for d in (d_outs[:1] if c3_mode else d_outs)]
-    out = outs[0]
+    if a.dump_outputs:
+        last = list(range(nb)) if c3_mode else [(step_no[0] - 1) % nb]     # the launches of the last timed step
+        dump_outputs(a.dump_outputs, [d_outs[b] for b in last], [bounds[b] for b in last], rank, world)
+    if a.full:
+        outs = [d.cpu().numpy() for d in (d_outs[:1] if c3_mode else d_outs)]
+        out = outs[0]
     c3_checked = 0
-    if c3_mode and a.cpu_seconds > 0:
+    if a.full and c3_mode and a.cpu_seconds > 0:
         # every rank samples rows of its first launch against the CPU oracle (sketches from the oracle too); the counts are summed
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import oracle  # checker only
@@ -871,7 +908,7 @@ def main():
             if c3_checked:
                 res["oracle_checked_reads"] = c3_checked
                 res["oracle_checked_ref_sketches"] = int(R)
-        if world == 1 and a.cpu_seconds > 0:
+        if a.full and world == 1 and a.cpu_seconds > 0:
             sys.path.insert(0, os.path.join(ROOT, "oracle"))
             import oracle  # CPU baseline + checker only
             thr = a.cpu_threads or min(oracle.max_threads(), usable_cpus())
@@ -914,7 +951,7 @@ def main():
                                                    "other %d timed batches (oracle-consistent; the mkmh policies are unpinned by any reference "
                                                    "artefact, DESIGN.md section 0)" % (m, checked_other, nb - 1),
                                    "oracle_checked_reads": m + checked_other}
-        if world == 1 and not a.no_host_path:
+        if a.full and world == 1 and not a.no_host_path:
             # PCIe-inclusive: the same batches from PAGEABLE host memory through rk_classify_batch (pinned staging, H2D, kernel,
             # D2H overlapped chunk by chunk).  Never the reported value.
             hb = np.concatenate([x[: n * L] for x in qbs] + [np.zeros(16, np.uint8)])
@@ -940,7 +977,7 @@ def main():
                                         "host buffers (rk_host_alloc), read by DMA in place; pageable_value = from ordinary memory, which the "
                                         "library page-locks for the call (hipHostRegister) or, failing that, copies through its staging buffers"}
             del pb, po
-        if world == 1 and not a.no_depth_filter:
+        if a.full and world == 1 and not a.no_depth_filter:
             # -M (rkmh.cpp:904-917) on the first batch, the reference's 200 M-slot table: pass 1 (count every window's hash) and the
             # masked classification that reads it back.  Informational: never the reported value.
             slots = 200000000
@@ -1004,11 +1041,11 @@ def main():
                                            "the compact depth map (only the slots of index keys), the mask per index key on the k-mer-space kernel; "
                                            "*_full_table / *_exact_min_num = the 200 M-slot table and the per-window slot lookup (what -N >= 0 with a "
                                            "large bound, or RKMH_EXACT_MIN_NUM=1, still runs)"}
-        if world == 1 and not a.no_configs:
+        if a.full and world == 1 and not a.no_configs:
             res.update(config_legs(rkmh_amd, api, synth, dev, n, L, a.cpu_seconds > 0))
             if not a.no_c4_full and "c4_filter" in res:
                 res["c4_filter"]["full_size"] = c4_full_size(api, synth, a.c4_genome_mb, a.c4_reads, check=a.cpu_seconds > 0)
-        if world == 1 and a.e2e_reads > 0:
+        if a.full and world == 1 and a.e2e_reads > 0:
             res["e2e"] = e2e_stream(a.e2e_reads, L, rb, ro, synth)
         print(json.dumps(res))
         sys.stdout.flush()

@@ -448,8 +448,8 @@ def test_error_paths_of_the_c_abi(orc, pave):
 
 
 def test_bench_json_contract(root):
-    """bench.py prints ONE JSON line with the driver's fields, the roofline object and (N=1) the CPU baseline."""
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--reads", "30000", "--steps", "3", "--warmup", "1",
+    """bench.py --full prints ONE JSON line with the driver's fields, the roofline object and (N=1) the CPU baseline."""
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--reads", "30000", "--steps", "3", "--warmup", "1",
                         "--cpu-seconds", "0.5", "--spinup-seconds", "0", "--c4-genome-mb", "120", "--c4-reads", "200000"], capture_output=True, cwd=root)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     lines = [l for l in r.stdout.decode().splitlines() if l.strip()]
@@ -487,29 +487,62 @@ def test_bench_json_contract(root):
     assert c5["k"] == 12 and c5["wall_s"] > 0 and c5["vcf_rows"] >= 5 and c5["reads"] > 50000
 
 
-def test_bench_spawns_its_own_ranks(root):
+def test_bench_plain_run_dumps_its_last_step(root, orc, tmp_path):
+    """A plain bench.py run (no --full) prints the contract fields and the roofline object and nothing it would need further runs
+    for; --dump-outputs DIR writes the rows of its last timed step: here warm-up 1 + 3 timed steps over 4 batches of 20000 reads
+    (and a clock ramp that must not shift them) end on batch 3, reads 60000..79999, bit-exact against the CPU oracle."""
+    from rkmh_amd import api, synth
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--reads", "20000", "--steps", "3", "--warmup", "1",
+                        "--spinup-seconds", "0.05", "--dump-outputs", str(tmp_path)], capture_output=True, cwd=root, timeout=600)
+    assert r.returncode == 0, r.stderr.decode()[-2000:]
+    lines = [l for l in r.stdout.decode().splitlines() if l.strip()]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    for k, t in (("metric", str), ("value", float), ("unit", str), ("n_gpus", int), ("steps", int), ("warmup", int),
+                 ("ms_per_step", float), ("higher_is_better", bool), ("dtype", str), ("config", dict), ("roofline", dict)):
+        assert isinstance(d[k], t), (k, d[k])
+    assert d["steps"] == 3 and d["warmup"] == 1 and abs(d["value"] - 20000 / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-6
+    for k in ("cpu_baseline", "host_path", "depth_filter", "c3_panel", "c4_filter", "c5_call", "e2e", "oracle_checked_ref_sketches"):
+        assert k not in d, k
+    assert sorted(os.listdir(tmp_path)) == ["read_index.npy", "rows.npy"]
+    rows, idx = np.load(tmp_path / "rows.npy"), np.load(tmp_path / "read_index.npy")
+    assert rows.dtype == np.float64 and idx.dtype == np.float64 and rows.shape == (20000, 4)
+    assert (idx == np.arange(60000, 80000)).all()
+    refs = api.parse_files([os.path.join(root, "tests", "golden", "data", "all_pave_ref.fa.gz")])
+    rb, ro = refs["bases"], refs["offsets"]
+    qb, qo = synth.generate_reads_fast(rb, ro, 60000, 80000)
+    sk, ln = orc.sketch_refs(rb, ro, [16], 1000, threads=8)
+    assert (rows == orc.classify_stream(qb, qo, [16], 1000, sk, ln, threads=8)).all()
+
+
+def test_bench_spawns_its_own_ranks(root, tmp_path):
     """`python bench.py --gpus 2` with no launcher around it (WORLD_SIZE unset): bench.py starts torch.distributed.run as a child
     process before it has touched the GPU, the two ranks run (here on GPU 0 over gloo), and the one JSON line comes through."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(RKMH_BENCH_ONE_DEVICE="1", RKMH_DIST_BACKEND="gloo")
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--c3-total-reads", "80000", "--steps", "4", "--warmup", "1",
-                        "--spinup-seconds", "0"], capture_output=True, cwd=root, env=env, timeout=600)
+                        "--spinup-seconds", "0", "--dump-outputs", str(tmp_path)], capture_output=True, cwd=root, env=env, timeout=600)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     lines = [l for l in r.stdout.decode().splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout.decode()[-2000:]
     d = json.loads(lines[0])
     assert d["n_gpus"] == 2 and d["steps"] == 4 and "cpu_baseline" not in d and "c3_panel" not in d
     assert d["scaling"] == "strong" and d["config"]["reads_per_gpu"] == 40000
+    # --dump-outputs: every rank writes the rows of its own shard
+    for rk in (0, 1):
+        rows, idx = np.load(tmp_path / ("rows_rank%d.npy" % rk)), np.load(tmp_path / ("read_index_rank%d.npy" % rk))
+        assert rows.shape == (40000, 4) and (idx == np.arange(40000 * rk, 40000 * (rk + 1))).all()
+        assert (rows[:, 0] >= 0).all() and (rows[:, 1] <= rows[:, 3]).all()
 
 
 def test_bench_two_ranks_launched_like_the_driver(root):
     """The driver's N>1 launch line (torch.distributed.run, one rank per GPU) with both ranks on GPU 0 and gloo instead of RCCL
     (a one-GPU box).  N > 1 measures BASELINE config 3: a FIXED total of reads against every bundled reference (266 sequences),
-    sharded over the ranks -- strong scaling; rank 0 prints ONE line, value = all reads over the slowest rank's time, every rank
-    sampled its rows against the oracle, no CPU baseline."""
+    sharded over the ranks -- strong scaling; rank 0 prints ONE line, value = all reads over the slowest rank's time; with --full
+    every rank sampled its rows against the oracle, no CPU baseline."""
     env = dict(os.environ, RKMH_BENCH_ONE_DEVICE="1", RKMH_DIST_BACKEND="gloo")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                        "--master-port", "29547", os.path.join(root, "bench.py"), "--gpus", "2", "--c3-total-reads", "100001", "--c3-launch-reads", "30000",
+                        "--master-port", "29547", os.path.join(root, "bench.py"), "--full", "--gpus", "2", "--c3-total-reads", "100001", "--c3-launch-reads", "30000",
                         "--steps", "4", "--warmup", "1", "--spinup-seconds", "0"], capture_output=True, cwd=root, env=env, timeout=600)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     lines = [l for l in r.stdout.decode().splitlines() if l.startswith("{")]
