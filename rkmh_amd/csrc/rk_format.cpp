@@ -1,7 +1,7 @@
 // rk_format.cpp -- the output of stream / classify / filter for one block of the device FASTQ front end (rk_fastq_slot_*), written
 // from the record names (sequences, quality strings) WHERE THEY LIE in the block's raw text: the host side of the per-read loop of
 // /root/reference/src/rkmh.cpp:845-898 shrinks to this.  Line format: rkmh.cpp:887-892; filter's records: rkmh.cpp:1292-1300 with
-// the decision of classify_and_count_diff_filter (/root/reference/src/equiv.hpp:324-353).  Used by bin/rkmh (rkmh_main.cpp) and,
+// the decision of classify_and_count_diff_filter (/root/reference/src/equiv.hpp:324-353).  Used by bin/rkmh (rkmh_frontends.cpp) and,
 // through ctypes, by the one-process-per-GPU front end (rkmh_amd/cli.py).
 #include "../../include/rkmh_amd.h"
 #include "rk_filter_rule.hpp"

@@ -1,0 +1,183 @@
+// rkmh_cli.hpp -- what the files of the `rkmh` command line share (the program on top of librkmh_amd.so, include/rkmh_amd.h).
+//   rkmh_main.cpp       main() and the dispatch to the sub-commands
+//   rkmh_exit.cpp       the fork for a fast exit, done_exit / fail_exit, stage timings, the CPUs this process may use, RKMH_* knobs
+//   rkmh_frontends.cpp  the device front ends (plain / BGZF / gzip FASTQ, packed reads, references), the host scanner pipeline,
+//                       the -M two-pass protocol and the registry of input files
+//   rkmh_classify.cpp   stream / classify and filter: one driver, two thin commands
+//   rkmh_commands.cpp   call, sketch (and the JSON sketches stream -R reads), hash, hpv16, pack; the hashing policy and help text
+#pragma once
+#include <getopt.h>
+
+#include <atomic>
+#include <condition_variable>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <deque>
+#include <functional>
+#include <map>
+#include <mutex>
+#include <string>
+#include <thread>
+#include <vector>
+
+#include "../../include/rkmh_amd.h"
+
+// ---- the process (rkmh_exit.cpp)
+double now_s();
+extern const bool g_timing; // RKMH_TIMING: stage timings on stderr
+void tick(const char* what, double& t0);
+[[noreturn]] void done_exit();
+[[noreturn]] void fail_exit();
+[[noreturn]] void die(const char* what);
+#define CK(call) do { if ((call) != RK_OK) die(#call); } while (0)
+void fork_for_fast_exit();
+int granted_cpus_main();
+// the RKMH_* knobs: env_flag -- unset: dflt, else atoi != 0; env_long -- unset or outside [lo, hi]: dflt
+bool env_flag(const char* name, bool dflt);
+long env_long(const char* name, long dflt, long lo, long hi);
+
+// ---- the hashing policy and the help text (rkmh_commands.cpp)
+extern rk_policy g_policy;
+void policy_apply(const char* spec, const char* from);
+std::string policy_text(const rk_policy& p);
+#define HASH_POLICY_OPTION {"hash-policy", required_argument, 0, 1004}
+#define HASH_POLICY_HELP \
+    "  --hash-policy <spec>    the mkmh choices the reference's tree does not fix, as presets (default, mash) and/or key=value:\n" \
+    "                          fold=swap32|h1|w2w1, windows=len-k|len-k+1, zero=count|skip, mask=lt|le, freqmax=incl|excl, seed=<n>;\n" \
+    "                          `mash` = fold=h1,windows=len-k+1 (the sketches Mash / sourmash compute).  RKMH_POLICY: the same, read first\n"
+void print_help();
+struct LoadedSketches { std::vector<std::string> names; std::vector<uint64_t> sk; std::vector<int32_t> lens; std::vector<int> ks; int S = 0; std::string policy; };
+bool load_sketch_json(const char* path, LoadedSketches& L);
+
+// ---- the sub-commands
+int main_stream(int argc, char** argv);
+int main_filter(int argc, char** argv);
+int main_call(int argc, char** argv);
+int main_sketch(int argc, char** argv);
+int main_hash(int argc, char** argv);
+int main_hpv16(int argc, char** argv);
+int main_pack(int argc, char** argv);
+
+// ---- stream / filter (rkmh_classify.cpp, rkmh_frontends.cpp)
+struct Opts {
+    std::vector<const char*> refs, reads;
+    std::vector<const char*> packed; // -F <file>: reads written by `rkmh pack`
+    std::vector<int> ks;
+    int sketch = 1000, threads = 1, min_occ = -1, min_matches = -1, min_diff = 0, max_samples = 100000;
+    const char* kmer_cache = getenv("RKMH_KMER_CACHE"); // --kmer-cache FILE: the k-mer enumeration of these references, kept between runs (rk_set_kmer_cache)
+    bool read_depth = false, ref_depth = false;
+    int device = 0;
+    std::vector<int> devices; // --devices a,b,...: reads are spread over these GPUs (one host thread + rk_ctx each); empty = --device
+};
+std::vector<int> parse_devices(const char* arg);
+extern bool g_no_kmer_cache;
+
+// bounded queue between pipeline stages (parser -> classify -> format/write)
+template <typename V> struct QueueT {
+    std::mutex m;
+    std::condition_variable cv;
+    std::deque<V> q;
+    bool done = false;
+    size_t cap = 2;
+    std::string err;
+    void push(V s) {
+        std::unique_lock<std::mutex> l(m);
+        cv.wait(l, [&] { return q.size() < cap; });
+        q.push_back(std::move(s));
+        cv.notify_all();
+    }
+    bool pop(V* s) {
+        std::unique_lock<std::mutex> l(m);
+        cv.wait(l, [&] { return !q.empty() || done; });
+        if (q.empty()) return false;
+        *s = std::move(q.front());
+        q.pop_front();
+        cv.notify_all();
+        return true;
+    }
+    void finish() { std::lock_guard<std::mutex> l(m); done = true; cv.notify_all(); }
+};
+struct Numbered { rk_seqset reads; int64_t seq = 0; };
+
+// The devices of one run (--devices): context 0 builds the reference sketches (rk_set_references on its GPU), the others import
+// them (rk_set_reference_sketches: a few MB through the host), all in parallel threads -- the in-process form of the one-rank-per-
+// GPU layout of rkmh_amd/cli.py, and the GPU analogue of the reference's -t OpenMP threads (rkmh.cpp:734, :813-898).
+struct DeviceGroup {
+    std::vector<rk_ctx*> ctx;
+    void create(const Opts& o);
+    void share_references(const Opts& o); // after the references were set on ctx[0]: the same sketches on every other context
+    void destroy() { for (rk_ctx* c : ctx) rk_ctx_destroy(c); ctx.clear(); }
+    size_t size() const { return ctx.size(); }
+};
+void group_run(DeviceGroup& g, const std::function<int(size_t)>& f);
+int min_num_bound_for(int compare_with);
+bool compact_maps_wanted(int bound, const char* read_map);
+bool reads_fit_sketch(const rk_seqset& reads, const Opts& o);
+void make_depth_maps(DeviceGroup& g, uint64_t slots, bool compact, std::vector<rk_counter*>& cnts);
+bool two_pass(DeviceGroup& g, std::vector<rk_counter*>& cnts, uint64_t slots, int min_occ, const std::function<bool()>& count,
+              const std::function<void()>& classify, double& t0, const char* tick_count = nullptr, const char* tick_classify = nullptr);
+void count_parsed(DeviceGroup& g, const rk_seqset& reads, std::vector<rk_counter*>& cnts);
+void classify_parsed(DeviceGroup& g, const rk_seqset& reads, int32_t* out4);
+
+// what a pass over the reads does with each block: stream's lines, filter's records, or pass 1 of -M (count, print nothing)
+enum RawKind { RAW_STREAM, RAW_FILTER, RAW_COUNT };
+void emit_lines(const rk_seqset& refs, const rk_seqset& reads, const int32_t* out4, const Opts& o, std::string& buf);
+void emit_passing(const rk_seqset& reads, const int32_t* rows, const Opts& o, std::string& buf);
+struct FilterDecision { int ref; int shared; bool diff_ok; };
+FilterDecision filter_decide(const int32_t* r, int min_diff);
+
+// The input files of a run, each looked at once (rkmh_frontends.cpp): what a path was found to be, and its open archive.  Read files
+// and references share the table; `reads` marks the compressed files raw_eligible took as read files (the device front end's jobs).
+enum InputKind { IN_PLAIN, IN_BGZF, IN_GZIP }; // IN_PLAIN: not opened as an archive (uncompressed text, or anything else)
+struct Input { InputKind kind = IN_PLAIN; rk_bgzf* bz = nullptr; rk_gzip* gz = nullptr; bool reads = false; };
+bool bgzf_on_device();
+bool raw_eligible(const char* path, int64_t* size, char first = '@');
+bool any_read_archive();
+void register_bgzf_mappings();
+
+// Work handed to a few helper threads: the lines of a device-inflated BGZF job (hundreds of megabytes of text, millions of records)
+// are formatted piece by piece by all of them while its worker waits, each piece parked under its own block number
+struct FormatPool {
+    std::mutex m;
+    std::condition_variable cv;
+    std::deque<std::function<void()>> q;
+    std::vector<std::thread> th;
+    bool closing = false;
+    void start(int n);
+    void run(std::function<void()> f) { { std::lock_guard<std::mutex> l(m); q.push_back(std::move(f)); } cv.notify_one(); }
+    void stop();
+};
+extern const std::vector<const char*>* g_read_paths; // the -f files of this run (RawEngine::create: are they all BGZF?)
+struct RawEngine {
+    // one slot per worker: one block on the device at a time.  (Two slots per worker -- the next block read while the previous one is on
+    // the device -- were measured no faster on 64 M reads and 0.2 s slower on 16 M, profiles/r04_e2e_ab.txt, and are gone.)
+    struct Worker { rk_fastq_slot* slot = nullptr; size_t dev = 0; bool device_text = false; uint64_t bytes = 0; std::vector<uint8_t> host_text; };
+    std::vector<Worker> w;
+    uint64_t block = 0;  // text per job: plain files, and BGZF files inflated on the host
+    uint64_t mega = 0;   // text per job of BGZF files inflated on the device (0: no such file in this run)
+    int pieces = 1;      // block numbers (= output pieces, formatted in parallel) per device-inflated job
+    uint64_t gz_stretch = 0; // ordinary gzip files in this run: the most compressed bytes one call takes (0: none)
+    bool need_plain_workers = false; // the references go through the workers' page-locked text buffers (refs_through_device)
+    FormatPool pool;
+    double t_read = 0, t_dev = 0, t_fmt = 0;
+    int64_t blocks = 0, records = 0;
+    bool create(DeviceGroup& g);
+    // A worker makes its slot when it starts, ONE worker at a time: allocations of several threads queue up inside the runtime anyway,
+    // and they slow every other call down while they do (measured: a device-text slot of 841 MB takes 24 ms on its own -- 23 of
+    // them page-locking its host arrays --, 60 to 230 ms when three are made at once beside the reference stage, which then takes
+    // 0.45 s instead of 0.15).  The first worker's slot exists already (create); the others follow 24 ms apart.
+    std::mutex slot_mu;
+    void destroy() { pool.stop(); for (auto& x : w) if (x.slot) rk_fastq_slot_destroy(x.slot); w.clear(); }
+};
+int64_t stream_files_raw(RawEngine& eng, DeviceGroup& g, const rk_seqset& refs, const Opts& o, const std::vector<const char*>& paths,
+                         const std::vector<int64_t>& fsizes, RawKind kind, std::vector<rk_counter*>* cnts, size_t* fail_file);
+bool two_pass_raw(RawEngine& eng, DeviceGroup& g, const rk_seqset& refs, const Opts& o, const std::vector<int64_t>& sizes,
+                  std::vector<rk_counter*>& cnts, RawKind kind, double& t0, uint64_t slots);
+void run_packed(DeviceGroup& g, const rk_seqset& refs, const Opts& o, const std::vector<const char*>& paths, RawKind kind, uint64_t slots, int bound, double& t0);
+struct DeviceRefs { std::vector<char> names; std::vector<uint64_t> name_offsets; };
+bool refs_for_device(const Opts& o, std::vector<int64_t>* sizes = nullptr, uint64_t* total_out = nullptr);
+bool refs_through_device(RawEngine& eng, DeviceGroup& g, const Opts& o, int max_samples, uint64_t counter_slots, rk_seqset& refs, DeviceRefs& keep);
+std::thread start_scanner(QueueT<Numbered>& q, std::vector<std::pair<const char*, uint64_t>> files, RawKind kind);
+void run_scanner_pipeline(DeviceGroup& group, const rk_seqset& refs, const Opts& o, RawKind kind, QueueT<Numbered>& q, std::thread& producer);
