@@ -66,11 +66,11 @@ struct KmLds {
     static constexpr int MQ = Q + KM_QCAP;                    // [KM_MQ][2] deferred hits with a posting list: read | rank << 8, list offset
     static constexpr int RI = MQ + 2 * KM_MQ;                 // [9] uint4 {start position, windows, first group, -} of read t
     static constexpr int NZ = RI + 4 * (KM_MAX_T + 1);        // [8] zero hashes of read t
-    static constexpr int BEST = NZ + KM_MAX_T;                // [8] max over increments of (count << 16 | 0xFFFF - ref)
+    static constexpr int BEST = NZ + KM_MAX_T;                // [8] sparse counters: max over increments of (count << 16 | 0xFFFF - ref)
     static constexpr int FLAGS = BEST + KM_MAX_T;             // [8] read must take the general path
     static constexpr int NWT = FLAGS + KM_MAX_T;              // [8] windows of read t, all k-mer sizes together
     static constexpr int FAM = NWT + KM_MAX_T;                // [8][4] hits of read t on lists stored as (base, exceptions): eight 16-bit counters, one per base
-    static constexpr int FAMF = FAM + 4 * KM_MAX_T;           // [8] read t has such hits: its arg-max comes from a scan of the counters, not from the running best
+    static constexpr int FAMF = FAM + 4 * KM_MAX_T;           // [8] read t has such hits: phase 2 expands its bases into the counters
     static constexpr int CNT = FAMF + KM_MAX_T;               // [T][cwords] per-reference counters, then [T][dset] hit multisets
     static_assert(RI % 4 == 0, "rinfo is read with 16-byte LDS loads");
     static_assert(CNT % 4 == 0, "the multisets are cleared with 16-byte LDS stores");
@@ -122,6 +122,15 @@ __device__ __forceinline__ uint32_t km_pack16(const u32x4& v, uint32_t& mism) {
 __device__ __forceinline__ uint32_t km_nonzero4(uint32_t m) {
     const uint32_t y = (m | ((m & 0x7f7f7f7fu) + 0x7f7f7f7fu)) & 0x80808080u;
     return ((y >> 7) * 0x01020408u) >> 24;
+}
+
+// largest counter field of a counter word (8-bit or 16-bit fields): byte / half-word selects of v_max_u32 (SDWA) and v_max3
+template <int CMODE>
+__device__ __forceinline__ uint32_t km_field_max(uint32_t x) {
+    if constexpr (CMODE == CM_DENSE8) {
+        const uint32_t m01 = max(x & 0xFFu, (x >> 8) & 0xFFu), m23 = max((x >> 16) & 0xFFu, x >> 24);
+        return max(m01, m23);
+    } else return max(x & 0xFFFFu, x >> 16);
 }
 
 // FAM: the index holds posting lists stored as (base, exceptions) (genome families, build_kpost).  A panel without them -- BASELINE
@@ -314,41 +323,39 @@ __global__ __launch_bounds__(KW, BIG ? 2 : KM_WAVES) void k_classify_kmer(const 
         uint32_t magic_v = magic, dlen_v = ulen - 4u * gpr_u;
         asm volatile("" : "+v"(magic_v), "+v"(dlen_v));
 
-        // +1 for reference `ref` of read t, whose counter row starts crow_b bytes into cnt; the monotone counters make
-        // (max_shared, first max_id) a running atomicMax
-        // count_posting: +1 for reference `ref` of read t; returns the candidate for the read's running maximum, count << 16 | ~ref
-        // (0: the read left for the general path).  add_posting = count + atomicMax.
+        // sparse counters: +1 for reference `ref` of read t, whose counter map starts crow_b bytes into cnt; returns the candidate for
+        // the read's running maximum, count << 16 | ~ref (0: the read left for the general path) -- the monotone counters make
+        // (max_shared, first max_id) a running atomicMax.  add_posting = count + atomicMax.
         auto count_posting = [&](uint32_t t, uint32_t crow_b, uint32_t ref) -> uint32_t {
-            uint32_t c;
-            if constexpr (CMODE == CM_SPARSE) { // large panels keep (ref, count) pairs of the references a read really hits
-                uint32_t* crow = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(cnt) + crow_b);
-                const uint32_t M1 = CW - 1u, key = ref + 1u;
-                uint32_t idx = ((ref * 0x9E3779B1u) >> 16) & M1, probe = 0;
-                c = 0;
-                for (; probe <= M1; ++probe) {
-                    const uint32_t old = atomicCAS(&crow[idx], 0u, (key << 11) | 1u);
-                    if (old == 0u) { c = 1u; break; }
-                    if ((old >> 11) == key) { c = (atomicAdd(&crow[idx], 1u) & 0x7FFu) + 1u; break; }
-                    idx = (idx + 1u) & M1;
-                }
-                if (probe > M1) { flags[t] = 1; return 0u; } // the read hits more references than the map holds: general path
+            uint32_t* crow = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(cnt) + crow_b);
+            const uint32_t M1 = CW - 1u, key = ref + 1u;
+            uint32_t idx = ((ref * 0x9E3779B1u) >> 16) & M1, probe = 0, c = 0;
+            for (; probe <= M1; ++probe) {
+                const uint32_t old = atomicCAS(&crow[idx], 0u, (key << 11) | 1u);
+                if (old == 0u) { c = 1u; break; }
+                if ((old >> 11) == key) { c = (atomicAdd(&crow[idx], 1u) & 0x7FFu) + 1u; break; }
+                idx = (idx + 1u) & M1;
+            }
+            if (probe > M1) { flags[t] = 1; return 0u; } // the read hits more references than the map holds: general path
+            return (c << 16) + (0xFFFFu - ref);
+        };
+        // +1 for reference `ref` of read t.  Dense counters: ONE non-returning LDS add and nothing else -- phase 2 derives the
+        // maximum, its first reference and the best earlier score from the finished row.
+        auto add_posting = [&](uint32_t t, uint32_t crow_b, uint32_t ref) {
+            if constexpr (CMODE == CM_SPARSE) {
+                const uint32_t v = count_posting(t, crow_b, ref);
+                if (v) atomicMax(&best[t], v);
             } else {
                 const uint32_t sh = (ref << (5 - clg)) & (32u - cbits);           // bit position of the counter inside its word
                 const uint32_t woff = (ref >> clg) << 2;                          // byte offset of the word inside the row
-                const uint32_t old = atomicAdd(reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(cnt) + crow_b + woff), 1u << sh);
-                c = __builtin_amdgcn_ubfe(old, sh, cbits) + 1u;
+                atomicAdd(reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(cnt) + crow_b + woff), 1u << sh);
             }
-            return (c << 16) + (0xFFFFu - ref);
-        };
-        auto add_posting = [&](uint32_t t, uint32_t crow_b, uint32_t ref) {
-            const uint32_t v = count_posting(t, crow_b, ref);
-            if (v) atomicMax(&best[t], v);
         };
         uint32_t mqn = 0; // deferred list hits (wave-uniform)
         auto process_mq = [&]() { // 16 lanes walk one hit's posting list, 4 hits at a time
             wave_sync();
             const uint32_t g = (uint32_t)lane >> 4, sl = (uint32_t)lane & 15u;
-            // The 16 lanes of a hit all feed the SAME running maximum best[t]: left to themselves they issue 16 atomicMax on one LDS
+            // (Sparse counters:) the 16 lanes of a hit all feed the SAME running maximum best[t]: left to themselves they issue 16 atomicMax on one LDS
             // address per step (and the four hits of a step are often four hits of one read: 64 on one address, served one after the
             // other).  Their candidates are reduced over the 16-lane row first (DPP) and one lane issues the atomic -- this and working a
             // full list of deferred hits off at once took reads of a 60-member family of near-identical references (every hit: 60
@@ -383,10 +390,15 @@ __global__ __launch_bounds__(KW, BIG ? 2 : KM_WAVES) void k_classify_kmer(const 
                     if (c < n) {
                         km_pair4 pm = pm0; // (reference, multiplicity)
                         if (c0) pm = *reinterpret_cast<const km_pair4*>(lp + 1 + 2 * c);
-                        if ((tr >> 8) < pm.y) v = count_posting(t, __umul24(t, CW * 4u), pm.x);
+                        if ((tr >> 8) < pm.y) {
+                            if constexpr (CMODE == CM_SPARSE) v = count_posting(t, __umul24(t, CW * 4u), pm.x);
+                            else add_posting(t, __umul24(t, CW * 4u), pm.x);
+                        }
                     }
-                    v = (uint32_t)row_max_i32((int)v); // (candidates are < 2^31: counts below 2^15)
-                    if (sl == 0 && v) atomicMax(&best[t], v);
+                    if constexpr (CMODE == CM_SPARSE) {
+                        v = (uint32_t)row_max_i32((int)v); // (candidates are < 2^31: counts below 2^15)
+                        if (sl == 0 && v) atomicMax(&best[t], v);
+                    }
                 }
             };
             // A list's header and its first sixteen postings are requested TOGETHER (the posting array ends in 256 bytes of padding,
@@ -465,9 +477,17 @@ __global__ __launch_bounds__(KW, BIG ? 2 : KM_WAVES) void k_classify_kmer(const 
             cell = match_cell(c.c, (c.y & km_rmask) << km_vb1);
             again = (cell & km_vmask) == km_vmask && ((c.c.w >> (km_vb1 - 1u)) & 1u) != 0u && c.t != 0xFFFFFFFFu;
         };
-        auto next_match = [&](const Cand& c, uint32_t hop, uint32_t& cell, bool& again) {
+        // a later bucket of a search that goes on (again): hop_load issues its ONE 16-byte load, next_match tests it.  The drain
+        // issues both rounds' loads before it pins them in registers (left to itself the compiler splits a bucket load and issues
+        // the parts lazily, behind the short-circuit of match_cell: three loads per hop)
+        auto hop_load = [&](const Cand& c, uint32_t hop, bool again) -> u32x4 {
+            u32x4 v = {0u, 0u, 0u, 0u};
+            if (again) v = *reinterpret_cast<const u32x4*>(km1p + (((c.y >> km_r) + hop) & ((1u << km1_b) - 1u)));
+            return v;
+        };
+        auto next_match = [&](const Cand& c, uint32_t hop, const u32x4& nv, uint32_t& cell, bool& again) {
             if (again) {
-                const uint4 nb = km1p[((c.y >> km_r) + hop) & ((1u << km1_b) - 1u)];
+                const uint4 nb = make_uint4(nv.x, nv.y, nv.z, nv.w);
                 cell = match_cell(nb, ((c.y & km_rmask) << km_vb1) | (hop << (32u - KM1_HB)));
                 again = (cell & km_vmask) == km_vmask && ((nb.w >> (km_vb1 - 1u)) & 1u) != 0u;
             }
@@ -531,23 +551,20 @@ __global__ __launch_bounds__(KW, BIG ? 2 : KM_WAVES) void k_classify_kmer(const 
                             if (nex > 7u) signed_add((valw >> 20) & 1023u);
                         }
                     }
-                    else if ((val >> 30) == 3u) { // three to six references that hold the hash once each, stored inline (build_index)
-                        if (rank == 0) {
-                            const uint32_t crow_b = __umul24(c.t, CW * 4u), n3 = (val >> 27) & 3u;
-                            add_posting(c.t, crow_b, val & 511u);
-                            add_posting(c.t, crow_b, (val >> 9) & 511u);
-                            add_posting(c.t, crow_b, (val >> 18) & 511u);
-                            if (n3 > 0u) add_posting(c.t, crow_b, valy & 511u);
-                            if (n3 > 1u) add_posting(c.t, crow_b, (valy >> 9) & 511u);
-                            if (n3 > 2u) add_posting(c.t, crow_b, (valy >> 18) & 511u);
-                        }
-                    } else if (!(val >> 31)) { // one posting (with multiplicity) or two single postings, stored inline
-                        const bool two = ((val >> 29) & 3u) != 0u;
-                        if (rank < (two ? 1u : ((val >> 20) & 0x1FFu))) {
-                            const uint32_t crow_b = __umul24(c.t, CW * 4u);
-                            add_posting(c.t, crow_b, val & (two ? 0x7FFu : 0xFFFFFu));
-                            if (two) add_posting(c.t, crow_b, (val >> 11) & 0x7FFu);
-                        }
+                    else if ((val >> 30) == 3u || !(val >> 31)) {
+                        // an inline value, decoded into one list of up to six references and worked off by ONE loop (the wave runs
+                        // the longest list any lane holds, not one body per form):
+                        //   three to six references that hold the hash once each (build_index): 9-bit fields, 3 in val, n3 in valy
+                        //   two single postings: 11-bit fields;  one posting: 20-bit reference, multiplicity in bits 20..28
+                        const bool three = (val >> 30) == 3u, two = !three && ((val >> 29) & 3u) != 0u;
+                        const uint32_t fw = three ? 9u : 11u; // width (and offset) of the second field
+                        const uint32_t lim = (three || two) ? 1u : ((val >> 20) & 0x1FFu);
+                        const uint32_t n = rank >= lim ? 0u : (three ? 3u + ((val >> 27) & 3u) : (two ? 2u : 1u));
+                        const uint32_t refs[6] = {__builtin_amdgcn_ubfe(val, 0u, three ? 9u : (two ? 11u : 20u)), __builtin_amdgcn_ubfe(val, fw, fw),
+                                                  (val >> 18) & 511u, valy & 511u, (valy >> 9) & 511u, (valy >> 18) & 511u};
+                        const uint32_t crow_b = __umul24(c.t, CW * 4u);
+#pragma unroll
+                        for (uint32_t j = 0; j < 6u; ++j) if (j < n) add_posting(c.t, crow_b, refs[j]);
                     } else multi = true;
                 }
             }
@@ -574,7 +591,8 @@ __global__ __launch_bounds__(KW, BIG ? 2 : KM_WAVES) void k_classify_kmer(const 
             for (uint32_t e0 = 0; e0 < qn; e0 += 2 * KW) { // two rounds of lookups in flight
                 const bool two = e0 + KW < qn;
                 const Cand a = lookup(e0 + (uint32_t)lane, qn);
-                Cand b = a;
+                // (not `b = a`: that copies registers whose load is still in flight, and the compiler waits for it before issuing b's)
+                Cand b{0u, 0xFFFFFFFFu, 0u, 0u, make_uint4(0u, 0u, 0u, 0u)};
                 if (two) b = lookup(e0 + KW + (uint32_t)lane, qn);
                 if constexpr (WIDE) {
                     uint3 ra, rb = make_uint3(KW_VID_NONE, 0u, 0u);
@@ -596,7 +614,12 @@ __global__ __launch_bounds__(KW, BIG ? 2 : KM_WAVES) void k_classify_kmer(const 
                 if (two) first_match(b, cb, gb);
                 // the searches that go on (about one lookup in ten, once) are continued for both rounds together: one more memory
                 // round trip per hop for the tile, not per round; the wave leaves when its last lane is done
-                for (uint32_t hop = 1; hop < (1u << KM1_HB) && __ballot(ga || gb); ++hop) { next_match(a, hop, ca, ga); next_match(b, hop, cb, gb); }
+                for (uint32_t hop = 1; hop < (1u << KM1_HB) && __ballot(ga || gb); ++hop) {
+                    u32x4 na = hop_load(a, hop, ga), nb = hop_load(b, hop, gb);
+                    asm volatile("" : "+v"(na), "+v"(nb));
+                    next_match(a, hop, na, ca, ga);
+                    next_match(b, hop, nb, cb, gb);
+                }
                 apply(a, ca);
                 if (two) apply(b, cb);
             }
@@ -737,14 +760,12 @@ __global__ __launch_bounds__(KW, BIG ? 2 : KM_WAVES) void k_classify_kmer(const 
                 const int nmins = (int)nwtot[t] - (int)nzero[t];
                 // bottom-S selection matters, or the hit multiset overflowed: exact answer comes from the general path
                 const bool reroute = nmins > S || flags[t] != 0;
-                uint32_t bk = best[t];
                 if (reroute) {
                     if (sl == 0) reinterpret_cast<int4*>(out4)[r0 + t] = make_int4(-2, 0, 0, 0);
                     continue;
                 }
                 if constexpr (FAM && CMODE != CM_SPARSE) {
-                    if (famf[t]) { // hits on (base, exceptions) lists: each touched base is expanded into the counters ONCE, then the
-                        // maximum and its first reference come from a scan of the row (the running best saw partial counts)
+                    if (famf[t]) { // hits on (base, exceptions) lists: each touched base is expanded into the counters ONCE
                         for (uint32_t b = 0; b < 8u; ++b) {
                             const uint32_t h = (fam[4u * (uint32_t)t + (b >> 1)] >> (16u * (b & 1u))) & 0xFFFFu;
                             if (h == 0u) continue;
@@ -759,50 +780,49 @@ __global__ __launch_bounds__(KW, BIG ? 2 : KM_WAVES) void k_classify_kmer(const 
                         }
                         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                        uint32_t km = 0;
-                        for (uint32_t w = (uint32_t)sl; w < CW; w += (uint32_t)LPR) {
-                            uint32_t x = ct[w];
-#pragma unroll
-                            for (uint32_t q = 0; q < (1u << clg); ++q) {
-                                const uint32_t cq = x & cmask, ref = (w << clg) + q;
-                                x >>= cbits;
-                                const uint32_t key = (cq << 16) + (0xFFFFu - ref);
-                                km = (cq != 0u && key > km) ? key : km;
-                            }
-                        }
-                        bk = (uint32_t)(LPR == 16 ? row_max_i32((int)km) : half_row_max_i32((int)km));
                     }
                 }
                 // first max wins (rkmh.cpp:878); diff = max - best EARLIER score (untouched refs score 0; none => -1)
-                const int max_id = bk ? (int)(0xFFFFu - (bk & 0xFFFFu)) : 0;
-                const int max_shared = (int)(bk >> 16);
-                int prev = max_id > 0 ? 0 : -1;
+                int max_id, max_shared, prev;
                 if constexpr (CMODE == CM_SPARSE) {
+                    const uint32_t bk = best[t];
+                    max_id = bk ? (int)(0xFFFFu - (bk & 0xFFFFu)) : 0;
+                    max_shared = (int)(bk >> 16);
+                    prev = max_id > 0 ? 0 : -1;
                     for (uint32_t w = sl; w < CW; w += LPR) {
                         const uint32_t x = ct[w];
                         const int r_ = (int)(x >> 11) - 1, cj = (int)(x & 0x7FFu);
                         if (x != 0u && r_ < max_id && cj > prev) prev = cj;
                     }
-                } else if (max_id > 0) {
-                    // counters of references below max_id: whole words up to the one that holds reference max_id - 1, of which only
-                    // the low fields count
-                    const int wb = (max_id - 1) >> clg;
-                    const uint32_t kb = (uint32_t)max_id - ((uint32_t)wb << clg);              // 1 .. counters per word
-                    const uint32_t mb = 0xFFFFFFFFu >> (32u - kb * cbits);
-                    uint32_t acc = 0;
-                    for (int w = sl; w <= wb; w += LPR) {
-                        const uint32_t x = ct[w] & (w == wb ? mb : 0xFFFFFFFFu);
-                        if constexpr (CMODE == CM_DENSE8) {
-                            const uint32_t m01 = (x & 0xFFu) > ((x >> 8) & 0xFFu) ? (x & 0xFFu) : ((x >> 8) & 0xFFu);
-                            const uint32_t m23 = ((x >> 16) & 0xFFu) > (x >> 24) ? ((x >> 16) & 0xFFu) : (x >> 24);
-                            const uint32_t m = m01 > m23 ? m01 : m23;
-                            acc = acc > m ? acc : m;
-                        } else {
-                            const uint32_t m = (x & 0xFFFFu) > (x >> 16) ? (x & 0xFFFFu) : (x >> 16);
-                            acc = acc > m ? acc : m;
-                        }
+                } else {
+                    // Dense counters: everything comes from the finished row.  Lane sl takes the nwl words from sl * nwl on (the
+                    // last lanes' past the row read its last word again: a repeat ties with, and so never displaces, the word itself).
+                    // Walking them in order it keeps its largest field maximum, the word that first holds it and the maximum of its
+                    // words before that one.  Then the largest (maximum << 8 | 255 - word) of the read's lanes names the maximum M
+                    // and the FIRST word wb that holds it, and the best earlier score is the maximum of the words before wb -- whole
+                    // lanes below wb's lane, the words of wb's lane before wb -- and of the fields of wb below its first M.
+                    const uint32_t nwl = (CW + (uint32_t)LPR - 1u) >> lsh, wbase = (uint32_t)sl * nwl; // words per lane (wave-uniform)
+                    uint32_t lmax = 0, lpre = 0, lfirst = wbase;
+                    for (uint32_t i = 0; i < nwl; ++i) {
+                        const uint32_t w = wbase + i;
+                        const uint32_t m = km_field_max<CMODE>(ct[w < CW ? w : CW - 1u]);
+                        if (m > lmax) { lpre = lmax; lmax = m; lfirst = w; }
                     }
-                    prev = (int)acc > prev ? (int)acc : prev;
+                    const uint32_t lkey = (lmax << 8) | (255u - lfirst);
+                    const uint32_t km = (uint32_t)(LPR == 16 ? row_max_i32((int)lkey) : half_row_max_i32((int)lkey));
+                    const uint32_t M = km >> 8, wb = 255u - (km & 255u);
+                    // first field of word wb equal to M: the lowest zero field of xb ^ (M in every field)
+                    const uint32_t xb = ct[wb];
+                    const uint32_t ones = CMODE == CM_DENSE8 ? 0x01010101u : 0x00010001u;
+                    const uint32_t y = xb ^ (M * ones);
+                    const uint32_t z = (y - ones) & ~y & (ones << (cbits - 1u));
+                    const uint32_t qf = (uint32_t)__builtin_ctz(z) >> (5 - clg); // (z != 0: word wb holds M)
+                    max_id = M ? (int)((wb << clg) + qf) : 0;
+                    max_shared = (int)M;
+                    uint32_t acc = km_field_max<CMODE>(__builtin_amdgcn_ubfe(xb, 0u, qf << (5 - clg))); // fields below it
+                    if (lkey == km) acc = max(acc, lpre);
+                    else if (wbase + nwl <= wb) acc = max(acc, lmax);
+                    prev = max_id > 0 ? (int)acc : -1;
                 }
                 prev = LPR == 16 ? row_max_i32(prev) : half_row_max_i32(prev);
                 if (sl == 0) reinterpret_cast<int4*>(out4)[r0 + t] = make_int4(max_id, max_shared, max_shared - prev, nmins < geo.nmin_cap ? nmins : geo.nmin_cap);
