@@ -315,17 +315,19 @@ CALL_HEADER = ("##fileformat=VCF4.2\n##source=rkmh\n##reference=%s\n"
 _SNP_ALTS = {ord("A"): b"CTG", ord("C"): b"TGA", ord("T"): b"CGA", ord("G"): b"ACT"}   # rkmh.cpp:1634-1637
 
 
-def call_rows(ref_names, ref_seqs, read_seqs, k, window_len=100, policy=None):
-    """ref_seqs / read_seqs: raw bytes (upper-cased here as rkmh.cpp:1609,1614 do). -> sorted list of VCF row strings."""
+def call_records(ref_names, ref_seqs, read_seqs, k, window_len=100, policy=None):
+    """ref_seqs / read_seqs: raw bytes (upper-cased here as rkmh.cpp:1609,1614 do).  -> list of
+    (ref_index, pos, orig, alt, kind, alt_depth, avg_d, depth), one per candidate k-mer that passes its depth test, in the
+    order the loop of rkmh.cpp:1772-1865 meets them.  orig / alt are one-character strings (alt '-' for a deletion, kind 1)."""
     from collections import Counter
     policy = policy or default_policy()
     depth_map = Counter()
     for r in read_seqs:                                            # rkmh.cpp:1613-1622
         for h in calc_hashes(to_upper(r), [k], policy):
             depth_map[int(h)] += 1
-    cc, cmax, cavg, corig = {}, {}, {}, {}
+    recs = []
     d_window = []                                                  # thread-private, NOT reset between refs (:1769)
-    for name, raw in zip(ref_names, ref_seqs):
+    for ri, raw in enumerate(ref_seqs):
         seq = to_upper(raw)
         hashes = calc_hashes(seq, [k], policy)
         for j in range(len(hashes)):
@@ -344,24 +346,86 @@ def call_rows(ref_names, ref_seqs, read_seqs, k, window_len=100, policy=None):
                         alt[alt_pos] = x
                         alt_depth = depth_map.get(calc_hash(bytes(alt), policy), 0)
                         if (alt_depth >= 0.1 * avg_d) & (alt_depth > depth):
-                            key = "%s\t%d\t.\t%s\t%s" % (name, j + alt_pos + 1, chr(orig), chr(x))
-                            cc[key] = cc.get(key, 0) + 1
-                            cavg[key] = max(avg_d, cavg.get(key, 0))
-                            corig[key] = max(corig.get(key, 0), depth)
-                            cmax[key] = max(cmax.get(key, 0), alt_depth)
+                            recs.append((ri, j + alt_pos + 1, chr(orig), chr(x), 0, alt_depth, avg_d, depth))
                 if j > 0:                                          # deletions, :1847-1865
                     for alt_pos in range(1, len(d_alt)):
                         orig = d_alt[alt_pos]
                         mod = d_alt[:alt_pos] + d_alt[alt_pos + 1:]
                         alt_depth = depth_map.get(calc_hash(mod, policy), 0)
                         if alt_depth > 0.9 * avg_d:
-                            key = "%s\t%d\t.\t%s\t-" % (name, j + alt_pos + 1, chr(orig))
-                            cc[key] = cc.get(key, 0) + 1
-                            cavg[key] = max(cavg.get(key, 0), avg_d)
-                            corig[key] = max(corig.get(key, 0), depth)
-                            cmax[key] = max(cmax.get(key, 0), alt_depth)
-    return ["%s\t99\tPASS\tKC=%d;MD=%d;RD=%d;OD=%d\n" % (key, cc[key], cmax[key], cavg[key], corig[key])
-            for key in sorted(cc, key=lambda s: s.encode())]     # std::map<string,...>: byte-wise order
+                            recs.append((ri, j + alt_pos + 1, chr(orig), "-", 1, alt_depth, avg_d, depth))
+    return recs
+
+
+def call_windows(ref_seqs, read_seqs, k, window_len=100, policy=None):
+    """The per-window quantities of rkmh.cpp:1785-1801 in numpy: (depth_map, upper-cased references, win_off[nref + 1], depth,
+    avg_d, selected) -- depth_map the exact hash -> count dictionary of the reads, the three arrays indexed by the global
+    window number (the references one after the other), selected = depth < 0.5 * avg_d."""
+    policy = policy or default_policy()
+    rh = [calc_hashes(to_upper(r), [k], policy) for r in read_seqs]
+    uniq, counts = np.unique(np.concatenate(rh) if rh else np.zeros(0, np.uint64), return_counts=True)
+    depth_map = dict(zip(uniq.tolist(), counts.tolist()))
+    seqs = [to_upper(raw) for raw in ref_seqs]
+    hashes = [calc_hashes(s, [k], policy) for s in seqs]
+    win_off = np.zeros(len(seqs) + 1, dtype=np.int64)
+    win_off[1:] = np.cumsum([len(h) for h in hashes])
+    allh = np.concatenate(hashes) if hashes else np.zeros(0, np.uint64)
+    depth = np.zeros(len(allh), dtype=np.int64)
+    if len(uniq) and len(allh):
+        at = np.minimum(np.searchsorted(uniq, allh), len(uniq) - 1)
+        depth = np.where(uniq[at] == allh, counts[at], 0).astype(np.int64)
+    csum = np.zeros(len(allh) + 1, dtype=np.int64)
+    np.cumsum(depth, out=csum[1:])
+    g = np.arange(len(allh), dtype=np.int64)
+    cnt = np.minimum(g + 1, int(window_len))                       # the window is never reset between references
+    avg = (csum[g + 1] - csum[g + 1 - cnt]) // cnt                 # non-negative integers: floor == the double -> int of :1791
+    return depth_map, seqs, win_off, depth, avg, depth.astype(np.float64) < 0.5 * avg.astype(np.float64)
+
+
+def call_records_fast(ref_names, ref_seqs, read_seqs, k, window_len=100, policy=None, with_candidate=False):
+    """The same records (as a multiset; here in window order too) by a second route that scales to millions of reference
+    windows: depths from numpy.unique, window means from an int64 cumulative sum, the windows below half their mean selected
+    in numpy; only those enumerate candidates.  Trusted because tests/test_call_cpu.py asserts it equal to call_records.
+    with_candidate: a ninth field, the candidate's number within its window -- 3 * alt_pos + (index of the alternative) for
+    an SNP, 3 k + alt_pos - 1 for a deletion -- for tests that must know which of the 4 k candidates made a record."""
+    tag = (lambda c: (c,)) if with_candidate else (lambda c: ())
+    policy = policy or default_policy()
+    depth_map, seqs, win_off, depth, avg, selected = call_windows(ref_seqs, read_seqs, k, window_len, policy)
+    recs = []
+    for gi in np.nonzero(selected)[0].tolist():
+        ri = int(np.searchsorted(win_off, gi, side="right")) - 1   # the last reference that starts at or before gi holds it
+        j = gi - int(win_off[ri])
+        seq, d, a = seqs[ri], int(depth[gi]), int(avg[gi])
+        for alt_pos in range(k):
+            orig = seq[j + alt_pos]
+            for xi, x in enumerate(_SNP_ALTS.get(orig, b"")):
+                ad = depth_map.get(calc_hash(seq[j:j + alt_pos] + bytes([x]) + seq[j + alt_pos + 1:j + k], policy), 0)
+                if ad >= 0.1 * a and ad > d:
+                    recs.append((ri, j + alt_pos + 1, chr(orig), chr(x), 0, ad, a, d) + tag(3 * alt_pos + xi))
+        if j > 0:
+            for alt_pos in range(1, k + 1):
+                ad = depth_map.get(calc_hash(seq[j - 1:j - 1 + alt_pos] + seq[j + alt_pos:j + k], policy), 0)
+                if ad > 0.9 * a:
+                    recs.append((ri, j + alt_pos + 1, chr(seq[j - 1 + alt_pos]), "-", 1, ad, a, d) + tag(3 * k + alt_pos - 1))
+    return recs
+
+
+def rows_from_records(ref_names, records):
+    """The VCF rows of rkmh.cpp:1821-1829 / :1856-1863 / :1885: records aggregated by (name, pos, orig, alt)."""
+    agg = {}
+    for ri, pos, orig, alt, kind, alt_depth, avg_d, depth in records:
+        a = agg.setdefault("%s\t%d\t.\t%s\t%s" % (ref_names[ri], pos, orig, alt), [0, 0, 0, 0])
+        a[0] += 1
+        a[1] = max(a[1], alt_depth)
+        a[2] = max(a[2], avg_d)
+        a[3] = max(a[3], depth)
+    return ["%s\t99\tPASS\tKC=%d;MD=%d;RD=%d;OD=%d\n" % (key, *agg[key])
+            for key in sorted(agg, key=lambda s: s.encode())]     # std::map<string,...>: byte-wise order
+
+
+def call_rows(ref_names, ref_seqs, read_seqs, k, window_len=100, policy=None):
+    """-> sorted list of the VCF row strings the reference prints with default flags."""
+    return rows_from_records(ref_names, call_records(ref_names, ref_seqs, read_seqs, k, window_len, policy))
 
 
 # ---- hpv16 (main_hpv16, /root/reference/src/rkmh.cpp:2366-2723) --------------------------------------------------------

@@ -97,3 +97,16 @@ def cli_golden(preset, fields):
 
 for preset, fields in PRESETS.items():
     cli_golden(preset, fields)
+
+
+# ---- call: the VCF rows of main_call's restatement (oracle.call_rows) for the planted HPV16 fixture of tests/helpers.py, at the
+# two settings tests/test_gpu_parity.py::test_call_matches_oracle runs.  First written before call_rows was split into
+# call_records + rows_from_records; tests/test_call_cpu.py holds the split to these rows.
+sys.path.insert(0, os.path.dirname(HERE))
+from helpers import _call_fixture  # noqa: E402
+
+rec, reads, _, _ = _call_fixture(oracle, DATA, None)
+doc = {"note": "oracle.call_rows on helpers._call_fixture(cov=40, seed=5), default policy", "ref_name": rec[0].decode(),
+       "cases": [{"k": k, "window_len": w, "rows": oracle.call_rows([rec[0].decode()], [rec[1]], reads, k, w)} for k, w in ((12, 100), (16, 30))]}
+json.dump(doc, open(os.path.join(HERE, "call_rows_hpv16.json"), "w"), indent=0)
+print("call_rows_hpv16", [len(c["rows"]) for c in doc["cases"]], "rows")

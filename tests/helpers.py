@@ -16,3 +16,33 @@ def golden(golden_dir, tag):
 
 def rand_dna(rng, n, alphabet=b"ACGT"):
     return bytes(rng.choice(np.frombuffer(alphabet, dtype=np.uint8), size=n).tolist())
+
+
+def _call_fixture(orc, data_dir, tmp_path, cov=40, seed=5, ref=None):
+    """C5-like input: reads drawn from HPV16 (or from `ref`, a (name, sequence) pair of at least 7.2 kb) carrying planted SNPs
+    and 1-bp deletions, 0.5 % substitution noise.  tmp_path None: nothing is written, the two paths come back as None."""
+    rec = ref if ref is not None else orc.kseq_parse_file(os.path.join(data_dir, "hpv_16.fa.gz"))[0]
+    ref = bytearray(orc.to_upper(rec[1]))
+    rng = np.random.default_rng(seed)
+    mut = bytearray(ref)
+    for pos, alt in ((500, b"A"), (1200, b"C"), (2503, b"G"), (4000, b"T"), (6100, b"A")):
+        mut[pos] = alt[0] if mut[pos] != alt[0] else b"ACGT"[(b"ACGT".index(alt) + 1) % 4]
+    for pos in (7000, 3100):
+        del mut[pos]
+    n = cov * len(ref) // 150
+    reads = []
+    for _ in range(n):
+        st = int(rng.integers(0, len(mut) - 150))
+        r = bytearray(mut[st:st + 150])
+        for j in np.nonzero(rng.random(150) < 0.005)[0]:
+            r[j] = b"ACGT"[int(rng.integers(0, 4))]
+        if rng.random() < 0.5:
+            r = bytearray(bytes(r).translate(bytes.maketrans(b"ACGT", b"TGCA"))[::-1])
+        reads.append(bytes(r))
+    if tmp_path is None:
+        return rec, reads, None, None
+    fa = tmp_path / "ref.fa"
+    fa.write_bytes(b">" + rec[0] + b"\n" + rec[1] + b"\n")
+    fq = tmp_path / "reads.fq"
+    fq.write_bytes(b"".join(b"@r%d\n%s\n+\n%s\n" % (i, r, b"I" * len(r)) for i, r in enumerate(reads)))
+    return rec, reads, fa, fq

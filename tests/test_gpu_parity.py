@@ -8,7 +8,7 @@ import sys
 import numpy as np
 import pytest
 
-from helpers import golden, rand_dna
+from helpers import _call_fixture, golden, rand_dna
 
 pytestmark = pytest.mark.gpu
 
@@ -1034,33 +1034,6 @@ def test_cli_filter_and_stream_at_scale(orc, root, data_dir, tmp_path):
         r = subprocess.run([exe, "stream", "-r", str(ref_fa), "-f", str(fq), "-k", "16", "-s", "1000", "-M", "2"], capture_output=True)
         assert r.returncode == 0, r.stderr
         assert r.stdout.decode() == want, (rep, len(r.stdout), len(want))
-
-
-def _call_fixture(orc, data_dir, tmp_path, cov=40, seed=5):
-    """C5-like input: reads drawn from HPV16 carrying planted SNPs and 1-bp deletions, 0.5 % substitution noise."""
-    rec = orc.kseq_parse_file(os.path.join(data_dir, "hpv_16.fa.gz"))[0]
-    ref = bytearray(orc.to_upper(rec[1]))
-    rng = np.random.default_rng(seed)
-    mut = bytearray(ref)
-    for pos, alt in ((500, b"A"), (1200, b"C"), (2503, b"G"), (4000, b"T"), (6100, b"A")):
-        mut[pos] = alt[0] if mut[pos] != alt[0] else b"ACGT"[(b"ACGT".index(alt) + 1) % 4]
-    for pos in (7000, 3100):
-        del mut[pos]
-    n = cov * len(ref) // 150
-    reads = []
-    for _ in range(n):
-        st = int(rng.integers(0, len(mut) - 150))
-        r = bytearray(mut[st:st + 150])
-        for j in np.nonzero(rng.random(150) < 0.005)[0]:
-            r[j] = b"ACGT"[int(rng.integers(0, 4))]
-        if rng.random() < 0.5:
-            r = bytearray(bytes(r).translate(bytes.maketrans(b"ACGT", b"TGCA"))[::-1])
-        reads.append(bytes(r))
-    fa = tmp_path / "ref.fa"
-    fa.write_bytes(b">" + rec[0] + b"\n" + rec[1] + b"\n")
-    fq = tmp_path / "reads.fq"
-    fq.write_bytes(b"".join(b"@r%d\n%s\n+\n%s\n" % (i, r, b"I" * len(r)) for i, r in enumerate(reads)))
-    return rec, reads, fa, fq
 
 
 def test_call_matches_oracle(ctx, orc, root, data_dir, tmp_path):
