@@ -457,6 +457,7 @@ void rk_bgzf_close(rk_bgzf* z);
 int64_t rk_bgzf_members(const rk_bgzf* z);
 uint64_t rk_bgzf_text_bytes(const rk_bgzf* z);
 uint64_t rk_bgzf_text_offset(const rk_bgzf* z, int64_t member);
+const char* rk_bgzf_inflater(void); /* "libdeflate" (where it can be loaded and RKMH_NO_LIBDEFLATE is unset) or "zlib": what rk_bgzf_fastq_records inflates with */
 int rk_bgzf_first_byte(const rk_bgzf* z);
 int64_t rk_bgzf_plan(const rk_bgzf* z, uint64_t target_bytes, int64_t* first, int64_t cap);
 int64_t rk_bgzf_plan_members(const rk_bgzf* z, uint64_t target_bytes, int64_t max_members, int64_t* first, int64_t cap);   /* ... and of at most max_members members each */

@@ -108,6 +108,7 @@ _SIGS = {
     "rk_bgzf_members": (C.c_int64, [C.c_void_p]),
     "rk_bgzf_text_bytes": (C.c_uint64, [C.c_void_p]),
     "rk_bgzf_text_offset": (C.c_uint64, [C.c_void_p, C.c_int64]),
+    "rk_bgzf_inflater": (C.c_char_p, []),
     "rk_bgzf_first_byte": (C.c_int, [C.c_void_p]),
     "rk_bgzf_image": (C.c_void_p, [C.c_void_p]),
     "rk_bgzf_lead_member": (C.c_int64, [C.c_void_p, C.c_int64]),

@@ -243,7 +243,11 @@ extern "C" int rk_fastq_slot_load_bgzf(rk_fastq_slot* s, const rk_bgzf* z, int64
     HIPCHK(hipEventSynchronize(s->ev));
     if (timing) fprintf(stderr, "[bgzf device] %u members, %.1f MB in, %.1f MB text: reserve %.1f ms, enqueue %.1f, wait %.1f\n", nm, cbytes / 1e6, ntext / 1e6,
                         t_reserve, t_enq - t_reserve, ms_since(t_0) - t_enq);
-    for (uint32_t i = 0; i < nm; ++i) if (h_status[i] != 0) return 1;
+    for (uint32_t i = 0; i < nm; ++i)
+        if (h_status[i] != 0) {
+            if (timing) fprintf(stderr, "[bgzf device] members %lld .. %lld: member %lld has status %u: the job is handed to the host\n", (long long)b0, (long long)b1, (long long)(lo + i), h_status[i]);
+            return 1;
+        }
     const uint8_t first_byte = reinterpret_cast<const uint8_t*>(h_info + 2)[0], last_byte = reinterpret_cast<const uint8_t*>(h_info + 2)[1];
     uint64_t head = cut_head ? h_info[0] : 0, tail = cut_tail ? h_info[1] : ntext;
     if (head == 0xFFFFFFFFull || tail == 0xFFFFFFFFull) return 1;

@@ -1107,6 +1107,10 @@ uint64_t rk_bgzf_text_offset(const rk_bgzf* z, int64_t member) {
     return z->uoff[(size_t)std::min<int64_t>(member, (int64_t)z->hlen.size())];
 }
 // the text's first byte (0: empty or corrupt): '@' = FASTQ
+// which inflater rk_bgzf_fastq_records runs in this process: "libdeflate" or "zlib".  libdeflate is the more lenient of the two: it
+// accepts a code-length repeat that runs past HLIT + HDIST and bits that match no code of an incomplete one-code tree, and then
+// delivers the text the member's CRC-32 and ISIZE vouch for, where zlib reports a corrupt member (tests/deflate_cases.py)
+const char* rk_bgzf_inflater(void) { return deflate_lib().run ? "libdeflate" : "zlib"; }
 int rk_bgzf_first_byte(const rk_bgzf* z) {
     if (!z) return 0;
     std::vector<unsigned char> t(65536);

@@ -1,3 +1,4 @@
+import ctypes as C
 import json
 import os
 
@@ -46,3 +47,48 @@ def _call_fixture(orc, data_dir, tmp_path, cov=40, seed=5, ref=None):
     fq = tmp_path / "reads.fq"
     fq.write_bytes(b"".join(b"@r%d\n%s\n+\n%s\n" % (i, r, b"I" * len(r)) for i, r in enumerate(reads)))
     return rec, reads, fa, fq
+
+
+def _through_device(gctx, path, text, slot_bytes, env):
+    """every stretch of the file through a device-text slot; the records filter prints for each must equal those of the same bytes
+    as plain text; returns the statuses"""
+    from rkmh_amd import api
+    old = {k: os.environ.get(k) for k in env}
+    os.environ.update(env)
+    gz = api.Gzip.open(str(path))
+    assert gz is not None and gz.first_byte() == ord("@")
+    dev = api.FastqSlot(gctx, max_bytes=slot_bytes, device_text=True)
+    plain = api.FastqSlot(gctx, max_bytes=slot_bytes)
+    dev.set_filter_output(-1, -100)      # every read passes: the whole text comes back, as filter prints it
+    statuses, at = [], 0
+    try:
+        ncalls = gz.plan(slot_bytes)
+        for call in range(ncalls):
+            st, n, off = dev.load_gzip(gz, call)
+            statuses.append(st)
+            if st != 0:
+                break
+            assert off == at, (call, off, at)
+            if n == 0:
+                continue
+            want_text = text[off:off + n] if off + n <= len(text) else text[off:] + b"\n"
+            assert len(want_text) == n
+            res = dev.classify_raw(n)
+            assert res.status == 0, (call, res.status)
+            got = dev.filter_records(res, -1, -100)
+            buf = plain.text_buffer()
+            C.memmove(buf, want_text, n)
+            res2 = plain.classify_raw(n)
+            assert res2.status == 0 and res2.nrec == res.nrec
+            assert got == plain.filter_records(res2, -1, -100), (call, off, n)
+            at = off + (n if off + n <= len(text) else n - 1)
+        if all(s == 0 for s in statuses):
+            assert at == len(text)
+    finally:
+        dev.destroy(); plain.destroy(); gz.close()
+        for k, v in old.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+    return statuses

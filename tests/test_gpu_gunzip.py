@@ -2,7 +2,8 @@
 chunk, the 32 KB in front of every chunk resolved in stream order.  What the slot receives, stretch after stretch, must be the
 file's text, record for record: compared through filter's output (names, bases and qualities of every record) with the same
 bytes given to an ordinary slot as plain text.  Stored, fixed-code and dynamic blocks, matches that reach (almost) 32 KB back
-across chunk edges, many stretches per file, damage, a second member behind the first, and the command line."""
+across chunk edges, many stretches per file, damage, a second member behind the first, and the command line.  The encoder of
+every stream here is zlib; the shapes other encoders write (and zlib never does) live in tests/test_gpu_deflate_cases.py."""
 import ctypes as C
 import gzip
 import os
@@ -11,6 +12,8 @@ import zlib
 
 import numpy as np
 import pytest
+
+from helpers import _through_device
 
 pytestmark = pytest.mark.gpu
 
@@ -57,51 +60,6 @@ def gctx(orc, data_dir):
     c.set_references(np.concatenate([rb, np.zeros(16, np.uint8)]), ro, [16], 1000)
     yield c
     c.close()
-
-
-def _through_device(gctx, path, text, slot_bytes, env):
-    """every stretch of the file through a device-text slot; the records filter prints for each must equal those of the same bytes
-    as plain text; returns the statuses"""
-    from rkmh_amd import api
-    old = {k: os.environ.get(k) for k in env}
-    os.environ.update(env)
-    gz = api.Gzip.open(str(path))
-    assert gz is not None and gz.first_byte() == ord("@")
-    dev = api.FastqSlot(gctx, max_bytes=slot_bytes, device_text=True)
-    plain = api.FastqSlot(gctx, max_bytes=slot_bytes)
-    dev.set_filter_output(-1, -100)      # every read passes: the whole text comes back, as filter prints it
-    statuses, at = [], 0
-    try:
-        ncalls = gz.plan(slot_bytes)
-        for call in range(ncalls):
-            st, n, off = dev.load_gzip(gz, call)
-            statuses.append(st)
-            if st != 0:
-                break
-            assert off == at, (call, off, at)
-            if n == 0:
-                continue
-            want_text = text[off:off + n] if off + n <= len(text) else text[off:] + b"\n"
-            assert len(want_text) == n
-            res = dev.classify_raw(n)
-            assert res.status == 0, (call, res.status)
-            got = dev.filter_records(res, -1, -100)
-            buf = plain.text_buffer()
-            C.memmove(buf, want_text, n)
-            res2 = plain.classify_raw(n)
-            assert res2.status == 0 and res2.nrec == res.nrec
-            assert got == plain.filter_records(res2, -1, -100), (call, off, n)
-            at = off + (n if off + n <= len(text) else n - 1)
-        if all(s == 0 for s in statuses):
-            assert at == len(text)
-    finally:
-        dev.destroy(); plain.destroy(); gz.close()
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-    return statuses
 
 
 @pytest.mark.parametrize("level,qual,nrec", [(1, "random", 30000), (6, "random", 30000), (9, "flat", 30000), (6, "wide", 12000), (1, "flat", 12000)])

@@ -1,7 +1,8 @@
 """DEFLATE on the device (rk_inflate.hip) for BGZF members: for every job of a file, the text the GPU route leaves in the slot
 (rk_fastq_slot_load_bgzf) must equal, byte for byte and offset for offset, what the host route inflates and cuts
 (rk_bgzf_fastq_records) -- for stored, fixed and dynamic blocks (levels 0, 1, 6, 9), members from 200 bytes to 64 KB, long
-self-overlapping matches, incompressible bytes, and jobs from one member to the whole file."""
+self-overlapping matches, incompressible bytes, and jobs from one member to the whole file.  The encoder of every member here is
+zlib; the shapes other encoders write (and zlib never does) live in tests/test_gpu_deflate_cases.py."""
 import ctypes as C
 import os
 import zlib
