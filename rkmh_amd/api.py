@@ -28,7 +28,8 @@ class NeedFullDepthMap(RkmhError):
 
 class Policy(C.Structure):
     _fields_ = [("fold", C.c_int32), ("drop_last_window", C.c_int32), ("counter_counts_zero", C.c_int32),
-                ("mask_strict_less", C.c_int32), ("freq_max_inclusive", C.c_int32), ("seed", C.c_uint32)]
+                ("mask_strict_less", C.c_int32), ("freq_max_inclusive", C.c_int32), ("seed", C.c_uint32),
+                ("canon", C.c_int32)]
 
 
 class CallRecord(C.Structure):
@@ -830,7 +831,7 @@ class Counter:
 
 
 def parse_policy(spec=None, base=None):
-    """rk_policy_parse: `spec` (presets default / mash, or fold= / windows= / zero= / mask= / freqmax= / seed=) applied onto `base`
+    """rk_policy_parse: `spec` (presets default / mash, or fold= / windows= / zero= / mask= / freqmax= / canon= / seed=) applied onto `base`
     (default: the build's defaults).  Raises RkmhError on text it does not know."""
     lib = load_library()
     p = Policy()

@@ -21,6 +21,7 @@ extern "C" const char* rk_version(void) { return "rkmh_amd 0.1 (gfx950)"; }
 extern "C" void rk_default_policy(rk_policy* p) {
     p->fold = RK_FOLD_SWAP32; p->drop_last_window = 1; p->counter_counts_zero = 1;
     p->mask_strict_less = 1; p->freq_max_inclusive = 1; p->seed = 42;
+    p->canon = RK_CANON_MINHASH;
 }
 extern "C" int rk_device_count(void) {
     int n = 0;
@@ -55,9 +56,10 @@ extern "C" int rk_ctx_create(int device, const rk_policy* policy, rk_ctx** out) 
     c->device = device;
     rk_policy p;
     if (policy) p = *policy; else rk_default_policy(&p);
+    if (p.canon != RK_CANON_MINHASH && p.canon != RK_CANON_LEXMIN) { delete c; return fail(RK_ERR_ARG, "hash policy: field 'canon' holds an unknown value"); }
     c->pol.fold = p.fold; c->pol.drop_last_window = p.drop_last_window;
     c->pol.counter_counts_zero = p.counter_counts_zero; c->pol.mask_strict_less = p.mask_strict_less;
-    c->pol.freq_max_inclusive = p.freq_max_inclusive; c->pol.seed = p.seed;
+    c->pol.freq_max_inclusive = p.freq_max_inclusive; c->pol.seed = p.seed; c->pol.canon = p.canon;
     HIPCHK(hipStreamCreateWithFlags(&c->st, hipStreamNonBlocking));
     for (auto& s : c->slot) {
         HIPCHK(hipStreamCreateWithFlags(&s.st, hipStreamNonBlocking));
@@ -70,6 +72,7 @@ extern "C" int rk_ctx_policy(const rk_ctx* c, rk_policy* out) {
     if (!c || !out) return fail(RK_ERR_ARG, "bad arguments");
     out->fold = c->pol.fold; out->drop_last_window = c->pol.drop_last_window; out->counter_counts_zero = c->pol.counter_counts_zero;
     out->mask_strict_less = c->pol.mask_strict_less; out->freq_max_inclusive = c->pol.freq_max_inclusive; out->seed = c->pol.seed;
+    out->canon = c->pol.canon;
     return RK_OK;
 }
 extern "C" void rk_ctx_destroy(rk_ctx* c) {

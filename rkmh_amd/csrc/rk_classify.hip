@@ -164,10 +164,13 @@ __device__ __forceinline__ void word_wait(uint32_t&) {}
 
 // MODE 0: classify; MODE 1: count pass of -M (rkmh.cpp:904-910); MODE 2: classify with the -M mask (rkmh.cpp:916)
 // MODE_ 3 / 4: MODE 0 / 2 with the first-level filter of large panels (RefIndex::pre) in front of the bucket table
-template <int KT, int MODE_, int FOLD, int PF>
+// CANON: the strand rule (policy U2) as a template parameter -- false (minhash) leaves every instantiation the code it was before
+// the key existed; true (lexmin) exists for the run-time-k form only (KT = 0, FOLD = -1), which the launcher picks under that policy
+template <int KT, int MODE_, int FOLD, int PF, bool CANON = false>
 __global__ __launch_bounds__(WAVE, RK_WAVES_PER_SIMD) void k_classify_tile(const uint8_t* __restrict__ bases, const uint32_t* __restrict__ offs,
                                                            uint32_t nreads, KsArr ks, int S, RefIndex ix, int32_t* counter,
                                                            uint64_t slots, int min_occ, int32_t* out4, DevPolicy pol, TileGeom geo) {
+    static_assert(!CANON || KT == 0, "canon=lexmin is served by the run-time-k form");
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
     constexpr bool PRE = MODE_ >= 3;
     constexpr int MODE = MODE_ == 3 ? 0 : (MODE_ == 4 ? 2 : MODE_);
@@ -283,7 +286,7 @@ __global__ __launch_bounds__(WAVE, RK_WAVES_PER_SIMD) void k_classify_tile(const
         {
             const int fwd_dw = (FWD_PAD + 3 + geo.cap_bytes + TAIL_PAD + 3) / 4;
             const int rc_dw = (geo.cap_bytes + TAIL_PAD + 3) / 4;
-            s.fwd = stage; s.rc = stage + fwd_dw; s.inv = s.rc + rc_dw;
+            s.fwd = stage; s.rc = stage + fwd_dw; s.inv = s.rc + rc_dw; // (rc above fwd in ONE array: lexmin_offset addresses both from fwd)
             s.fbase = FWD_PAD + (tstart & 3u); s.nbases = B;
         }
         const uint32_t o_next = (uint32_t)__shfl_down((int)cur_o, 1); // offset of read lane+1
@@ -571,7 +574,7 @@ __global__ __launch_bounds__(WAVE, RK_WAVES_PER_SIMD) void k_classify_tile(const
                                 if (hh == 0) atomicAdd(&nzero[tt], 1u);
                             }
                         };
-                        const bool split = compact && it + 1 == nIt && nW - it * WAVE <= 32u; // wave-uniform
+                        const bool split = compact && it + 1 == nIt && nW - it * WAVE <= 32u && !CANON; // wave-uniform (lexmin hashes one strand: nothing to share)
                         if (split) {
                             // The tile's last <= 32 windows: lanes l and l + 32 take window l together -- the low half hashes
                             // the forward strand, the high half the reverse complement, one exchange gives both the minimum.
@@ -604,7 +607,7 @@ __global__ __launch_bounds__(WAVE, RK_WAVES_PER_SIMD) void k_classify_tile(const
                             if (MODE == 1 && has_invalid && !window_valid<KT>(s, p, k)) h = 0;
                             else {
                                 if constexpr (KT == 0) { // run-time k: both strands through one block loop, uniform tail masks
-                                    h = canonical_rt(s.fwd, s.fbase + p, s.rc, B - (uint32_t)k - p, k, tmasks, pol.seed, pol.fold);
+                                    h = canonical_rt(s.fwd, s.fbase + p, s.rc, B - (uint32_t)k - p, k, tmasks, pol.seed, pol.fold, CANON ? 1 : 0);
                                 } else {
                                     if constexpr (FOLD == 0) { // the half swap of fold 0 happens inside the minimum
                                         const uint64_t f = murmur_window<KT, 3>(s.fwd, s.fbase + p, k, pol.seed, 0);
@@ -875,37 +878,38 @@ hipError_t launch_classify_tile(const uint8_t* bases, const uint32_t* offs, uint
     // rate of random accesses that miss the L2, about 5 * 10^10 per second here, not by latency or instructions.)
     bool pre_masked = ((size_t)ix.bmask + 1) * 16 > ((size_t)3 << 20);
     if (kn.pre_masked >= 0) pre_masked = kn.pre_masked != 0; // tests force either form
-#define RK_LAUNCH_P(KT, MODE, FOLD, PF)                                                                                    \
+#define RK_LAUNCH_P(KT, MODE, FOLD, PF, ...)                                                                         \
     do {                                                                                                             \
         if (lds > 64 * 1024) {                                                                                       \
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_classify_tile<KT, MODE, FOLD, PF>),       \
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_classify_tile<KT, MODE, FOLD, PF, ##__VA_ARGS__>), \
                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);               \
             if (e != hipSuccess) return e;                                                                           \
         }                                                                                                            \
         uint32_t grid = (ntiles + (uint32_t)tpb - 1) / (uint32_t)tpb;                                                \
         grid = (grid + 7u) & ~7u; /* whole rounds of the 8 XCDs: the virtual ids then cover [0, grid) exactly */      \
-        hipLaunchKernelGGL((k_classify_tile<KT, MODE, FOLD, PF>), dim3(grid), dim3(WAVE), lds, st, bases, offs, nreads,   \
+        hipLaunchKernelGGL((k_classify_tile<KT, MODE, FOLD, PF, ##__VA_ARGS__>), dim3(grid), dim3(WAVE), lds, st, bases, offs, nreads, \
                            ks, S, ix, counter, slots, min_occ, out4, pol, geo);                                      \
     } while (0)
-#define RK_LAUNCH(KT, MODE, FOLD)                                                                                    \
+#define RK_LAUNCH(KT, MODE, FOLD, ...)                                                                               \
     do {                                                                                                             \
-        if (geo.cap_bytes <= 2 * WAVE * 4 - 8) RK_LAUNCH_P(KT, MODE, FOLD, 2);                                       \
-        else if (geo.cap_bytes <= 3 * WAVE * 4 - 8) RK_LAUNCH_P(KT, MODE, FOLD, 3);                                  \
-        else RK_LAUNCH_P(KT, MODE, FOLD, 6);                                                                         \
+        if (geo.cap_bytes <= 2 * WAVE * 4 - 8) RK_LAUNCH_P(KT, MODE, FOLD, 2, ##__VA_ARGS__);                        \
+        else if (geo.cap_bytes <= 3 * WAVE * 4 - 8) RK_LAUNCH_P(KT, MODE, FOLD, 3, ##__VA_ARGS__);                   \
+        else RK_LAUNCH_P(KT, MODE, FOLD, 6, ##__VA_ARGS__);                                                          \
     } while (0)
-#define RK_LAUNCH_M(KT, FOLD)                                                                                        \
+#define RK_LAUNCH_M(KT, FOLD, ...)                                                                                   \
     do {                                                                                                             \
-        if (kmode == 1) RK_LAUNCH(KT, 1, FOLD);                                                                      \
-        else if (kmode == 0 && !ix.pre) RK_LAUNCH(KT, 0, FOLD);                                                      \
-        else if (kmode == 0) RK_LAUNCH(KT, 3, FOLD);                                                                 \
-        else if (!ix.pre || !pre_masked) RK_LAUNCH(KT, 2, FOLD);                                                     \
-        else RK_LAUNCH(KT, 4, FOLD);                                                                                 \
+        if (kmode == 1) RK_LAUNCH(KT, 1, FOLD, ##__VA_ARGS__);                                                       \
+        else if (kmode == 0 && !ix.pre) RK_LAUNCH(KT, 0, FOLD, ##__VA_ARGS__);                                       \
+        else if (kmode == 0) RK_LAUNCH(KT, 3, FOLD, ##__VA_ARGS__);                                                  \
+        else if (!ix.pre || !pre_masked) RK_LAUNCH(KT, 2, FOLD, ##__VA_ARGS__);                                      \
+        else RK_LAUNCH(KT, 4, FOLD, ##__VA_ARGS__);                                                                  \
     } while (0)
 #ifdef RK_TILE_ONLY_K // experiment builds : one compile-time k, seconds to compile
     if (ks.n != 1 || ks.k[0] != RK_TILE_ONLY_K) return hipErrorInvalidValue;
     RK_LAUNCH_M(RK_TILE_ONLY_K, -1);
     return hipGetLastError();
 #endif
+    if (pol.canon) { RK_LAUNCH_M(0, -1, true); return hipGetLastError(); } // canon=lexmin: the run-time-k form, any k
     // single k of 12, 20 (the reference's other documented settings), 21 or 31: window length known at compile time, runtime fold
     if (ks.n == 1 && ks.k[0] == 12) RK_LAUNCH_M(12, -1);
     else if (ks.n == 1 && ks.k[0] == 20) RK_LAUNCH_M(20, -1);

@@ -215,7 +215,7 @@ extern "C" int rk_counter_save_tagged(rk_counter* k, const char* path, const voi
 extern "C" int rk_counter_load_tagged(rk_counter* k, const char* path, const void* tag, uint32_t tag_len) {
     return counter_load_impl(k, path, tag, tag_len);
 }
-// Provenance of a read-depth map: everything that decides which slot a read's k-mers increment (k list, seed, fold, window and
+// Provenance of a read-depth map: everything that decides which slot a read's k-mers increment (k list, seed, fold, window, strand and
 // zero-counting policy) plus a fingerprint of the read set (count, total bases, FNV-1a over the read lengths and over up to
 // 2 x 1 MiB of bases from both ends of the batch).
 extern "C" int rk_depth_map_tag(const rk_ctx* c, const int* ks, int nks, const uint8_t* bases, const uint64_t* offsets,
@@ -226,11 +226,11 @@ extern "C" int rk_depth_map_tag(const rk_ctx* c, const int* ks, int nks, const u
         for (size_t i = 0; i < n; ++i) { h ^= b[i]; h *= 0x100000001b3ull; }
         return h;
     };
-    struct Tag { char magic[8]; int32_t fold, drop_last, counts_zero; uint32_t seed; int32_t nks; int32_t ks[RK_MAX_KS]; int64_t nseq; uint64_t total, hlen, hbases; } t;
+    struct Tag { char magic[8]; int32_t fold, drop_last, counts_zero; uint32_t seed; int32_t nks; int32_t ks[RK_MAX_KS]; int64_t nseq; uint64_t total, hlen, hbases; int32_t canon; } t; // (canon last: 0 = the bytes a tag had before the key existed)
     static_assert(sizeof(Tag) <= RK_DEPTH_TAG_BYTES, "tag layout");
     memset(&t, 0, sizeof t);
     memcpy(t.magic, "rkdepth2", 8); // 2: the fingerprint covers every base (1 sampled both ends)
-    t.fold = c->pol.fold; t.drop_last = c->pol.drop_last_window; t.counts_zero = c->pol.counter_counts_zero; t.seed = c->pol.seed;
+    t.fold = c->pol.fold; t.drop_last = c->pol.drop_last_window; t.counts_zero = c->pol.counter_counts_zero; t.seed = c->pol.seed; t.canon = c->pol.canon;
     t.nks = nks;
     for (int i = 0; i < nks; ++i) t.ks[i] = ks[i];
     t.nseq = nseq;

@@ -19,6 +19,7 @@ struct DevPolicy {
     int32_t mask_strict_less;
     int32_t freq_max_inclusive;
     uint32_t seed;
+    int32_t canon; // U2 (wave-uniform): 0 = the smaller of both strand hashes, 1 = the hash of the strand that is the smaller string
 };
 
 constexpr uint64_t MM_C1 = 0x87c37b91114253d5ULL;
@@ -213,10 +214,34 @@ __device__ __forceinline__ uint32_t packed_to_ascii4(uint32_t v, int d) {
     const uint32_t sel = (b & 3u) | ((b & 0xCu) << 6) | ((b & 0x30u) << 12) | ((b & 0xC0u) << 18);
     return __builtin_amdgcn_perm(0x47544341u, 0x47544341u, sel); // code 0..3 -> "ACTG"
 }
-// canonical hash (min over both strands of the folded value) of a packed k-mer, k <= 16
-__device__ __forceinline__ uint64_t canonical_packed(uint32_t v, int k, uint32_t seed, int fold) {
+// canon=lexmin in the packed domain.  Neither the 2-bit code (A0 C1 T2 G3: G and T swapped) nor the significance order (base 0 in
+// the LOWEST bits) is lexicographic: x ^ ((x >> 1) & 0x55..) turns the code into A0 C1 G2 T3, and the group reversal that
+// packed_revcomp performs puts base 0 on top -- two k-mers then compare as their upper-case strings do.
+__device__ __forceinline__ uint32_t packed_lexkey(uint32_t v, int k) {
+    uint32_t r = __builtin_bitreverse32(v ^ ((v >> 1) & 0x55555555u));
+    r = ((r >> 1) & 0x55555555u) | ((r & 0x55555555u) << 1);
+    return k < 16 ? r >> 2 * (16 - k) : r;
+}
+__device__ __forceinline__ uint64_t packed_lexkey64(uint64_t v, int k) {
+    uint64_t r = __builtin_bitreverse64(v ^ ((v >> 1) & 0x5555555555555555ull));
+    r = ((r >> 1) & 0x5555555555555555ull) | ((r & 0x5555555555555555ull) << 1);
+    return k < 32 ? r >> 2 * (32 - k) : r;
+}
+// canonical hash of a packed k-mer, k <= 16: the smaller of both strands' folded values, or (canon = 1, lexmin) the one hash of
+// the strand that is the smaller string
+__device__ __forceinline__ uint64_t canonical_packed(uint32_t v, int k, uint32_t seed, int fold, int canon) {
     const uint32_t rv = packed_revcomp(v, k);
     uint32_t f[4], r[4];
+    if (canon) {
+        const uint32_t x = packed_lexkey(v, k) <= packed_lexkey(rv, k) ? v : rv;
+#pragma unroll
+        for (int d = 0; d < 4; ++d) {
+            const int nv = k - 4 * d;
+            const uint32_t m = nv >= 4 ? 0xffffffffu : (nv <= 0 ? 0u : ((1u << (8 * nv)) - 1u));
+            f[d] = packed_to_ascii4(x, d) & m;
+        }
+        return murmur_regs16<-1>(f[0], f[1], f[2], f[3], k, seed, fold);
+    }
 #pragma unroll
     for (int d = 0; d < 4; ++d) {
         const int nv = k - 4 * d; // bytes of this dword that belong to the k-mer
@@ -242,9 +267,19 @@ __device__ __forceinline__ uint32_t packed_to_ascii4_64(uint64_t v, int d) {
     const uint32_t sel = (b & 3u) | ((b & 0xCu) << 6) | ((b & 0x30u) << 12) | ((b & 0xC0u) << 18);
     return __builtin_amdgcn_perm(0x47544341u, 0x47544341u, sel);
 }
-__device__ __forceinline__ uint64_t canonical_packed64(uint64_t v, int k, uint32_t seed, int fold) {
+__device__ __forceinline__ uint64_t canonical_packed64(uint64_t v, int k, uint32_t seed, int fold, int canon) {
     const uint64_t rv = packed_revcomp64(v, k);
     uint32_t f[5], r[5];
+    if (canon) {
+        const uint64_t x = packed_lexkey64(v, k) <= packed_lexkey64(rv, k) ? v : rv;
+#pragma unroll
+        for (int d = 0; d < 5; ++d) {
+            const int nv = k - 4 * d;
+            const uint32_t m = nv >= 4 ? 0xffffffffu : (nv <= 0 ? 0u : ((1u << (8 * nv)) - 1u));
+            f[d] = packed_to_ascii4_64(x, d) & m;
+        }
+        return murmur_regs20(f, k, seed, fold);
+    }
 #pragma unroll
     for (int d = 0; d < 5; ++d) {
         const int nv = k - 4 * d;
@@ -266,6 +301,11 @@ typedef uint32_t rk_u32x4 __attribute__((ext_vector_type(4)));
 struct __attribute__((packed)) rk_unaligned16 { rk_u32x4 v; };
 __device__ __forceinline__ rk_u32x4 lds_load16_unaligned(const uint32_t* w32, uint32_t byte_off) {
     return reinterpret_cast<const rk_unaligned16*>(reinterpret_cast<const uint8_t*>(w32) + byte_off)->v;
+}
+// one dword at any byte offset of an LDS dword array (unaligned DS access, as above)
+struct __attribute__((packed)) rk_unaligned4 { uint32_t v; };
+__device__ __forceinline__ uint32_t lds_load4_unaligned(const uint32_t* w32, uint32_t byte_off) {
+    return reinterpret_cast<const rk_unaligned4*>(reinterpret_cast<const uint8_t*>(w32) + byte_off)->v;
 }
 template <int KT, int FOLD = -1>
 __device__ __forceinline__ uint64_t murmur_window(const uint32_t* w32, uint32_t a, int k_rt, uint32_t seed, int fold) {
@@ -294,6 +334,24 @@ __device__ __forceinline__ uint64_t murmur_window(const uint32_t* w32, uint32_t 
         k1 *= MM_C1; k1 = rotl64(k1, 31); k1 *= MM_C2; h1 ^= k1;
     }
     return mm_finish<FOLD>(h1, h2, (uint32_t)k, fold);
+}
+
+// canon=lexmin for the LDS forms: the byte offset, relative to `fwd`, of the strand to hash -- the forward window at `af` or the
+// reverse-complement window at `ar` of `rc` (both images lie in one LDS array), whichever is the smaller byte string ('A' < 'C' <
+// 'G' < 'T' is the ASCII order; a palindrome is its own).  Dwords are compared from the last to the first, so the first one that
+// differs has the last word; a byte-swapped dword compares as its four characters do.
+template <int KT>
+__device__ __forceinline__ uint32_t lexmin_offset(const uint32_t* fwd, uint32_t af, const uint32_t* rc, uint32_t ar, int k_rt) {
+    const int k = KT ? KT : k_rt;
+    bool fwd_le = true;
+    for (int q = ((k + 3) >> 2) - 1; q >= 0; --q) {
+        uint32_t a = lds_load4_unaligned(fwd, af + 4u * (uint32_t)q), b = lds_load4_unaligned(rc, ar + 4u * (uint32_t)q);
+        const int nv = k - 4 * q; // bytes of this dword inside the window (only the last dword holds fewer than four)
+        if (nv < 4) { const uint32_t m = (1u << (8 * nv)) - 1u; a &= m; b &= m; }
+        if (a != b) fwd_le = __builtin_bswap32(a) < __builtin_bswap32(b);
+    }
+    const uint32_t rc_off = (uint32_t)(reinterpret_cast<const uint8_t*>(rc) - reinterpret_cast<const uint8_t*>(fwd));
+    return fwd_le ? af : rc_off + ar;
 }
 
 // Canonical hash of a window whose length is only known at run time: both strands advance through ONE loop over the
@@ -358,7 +416,8 @@ __device__ __forceinline__ uint64_t canonical_nb(const uint32_t* fwd, uint32_t a
     return f < r ? f : r;
 }
 __device__ __forceinline__ uint64_t canonical_rt(const uint32_t* fwd, uint32_t af, const uint32_t* rc, uint32_t ar, int k,
-                                                 const TailMasks& tm, uint32_t seed, int fold) {
+                                                 const TailMasks& tm, uint32_t seed, int fold, int canon) {
+    if (canon) return murmur_window<0>(fwd, lexmin_offset<0>(fwd, af, rc, ar, k), k, seed, fold); // lexmin: one chain
     // k is wave-uniform: one scalar branch picks the unrolled form of the common sizes (k = 16 .. 31: one block, 32 .. 47: two)
     const int nb = k >> 4;
     if (nb == 1) return canonical_nb<1>(fwd, af, rc, ar, k, tm, seed, fold);
@@ -385,11 +444,6 @@ __device__ __forceinline__ uint32_t revcomp4(uint32_t x) {
     const uint32_t sel = (x >> 1) & 0x03030303u;
     const uint32_t c = __builtin_amdgcn_perm(0x43414754u, 0x43414754u, sel); // "TGAC": A->T, C->G, T->A, G->C
     return __builtin_bswap32(c);
-}
-// one dword at any byte offset of an LDS dword array (unaligned DS access, see murmur_window below)
-struct __attribute__((packed)) rk_unaligned4 { uint32_t v; };
-__device__ __forceinline__ uint32_t lds_load4_unaligned(const uint32_t* w32, uint32_t byte_off) {
-    return reinterpret_cast<const rk_unaligned4*>(reinterpret_cast<const uint8_t*>(w32) + byte_off)->v;
 }
 // 4-bit mask: bit q set <=> byte q is NOT one of 'A','C','G','T'
 __device__ __forceinline__ uint32_t invalid4(uint32_t x) {
@@ -433,7 +487,7 @@ __device__ __forceinline__ Staged stage_piece(const uint8_t* __restrict__ bases,
     const int fwd_dw = (FWD_PAD + 3 + max_bases + TAIL_PAD + 3) / 4;
     const int rc_dw = (max_bases + TAIL_PAD + 3) / 4;
     s.fwd = lds;
-    s.rc = lds + fwd_dw;
+    s.rc = lds + fwd_dw; // (rc above fwd in ONE array: lexmin_offset addresses both from fwd)
     s.inv = s.rc + rc_dw;
     const uint32_t d = (uint32_t)(start & 3);
     s.fbase = FWD_PAD + d;
@@ -488,6 +542,7 @@ template <int KT>
 __device__ __forceinline__ uint64_t canonical_window(const Staged& s, uint32_t i, int k_rt, const DevPolicy& pol) {
     const int k = KT ? KT : k_rt;
     if (!window_valid<KT>(s, i, k)) return 0;
+    if (pol.canon) return murmur_window<KT>(s.fwd, lexmin_offset<KT>(s.fwd, s.fbase + i, s.rc, s.nbases - (uint32_t)k - i, k), k, pol.seed, pol.fold);
     uint64_t f = murmur_window<KT>(s.fwd, s.fbase + i, k, pol.seed, pol.fold);
     uint64_t r = murmur_window<KT>(s.rc, s.nbases - (uint32_t)k - i, k, pol.seed, pol.fold);
     return f < r ? f : r;
@@ -521,6 +576,14 @@ __device__ __forceinline__ uint8_t comp1(uint8_t c) { return c == 'A' ? 'T' : c 
 template <typename GetByte>
 __device__ __forceinline__ uint64_t canonical_bytes(GetByte gb, int k, const DevPolicy& pol) {
     for (int q = 0; q < k; ++q) if (!is_acgt(gb(q))) return 0;
+    if (pol.canon) { // lexmin: the first base that differs from its counterpart on the other strand decides
+        bool fwd_le = true;
+        for (int q = 0; q < k; ++q) {
+            const uint8_t a = gb(q), b = comp1(gb(k - 1 - q));
+            if (a != b) { fwd_le = a < b; break; }
+        }
+        return murmur_bytes([&](int q) -> uint8_t { return fwd_le ? gb(q) : comp1(gb(k - 1 - q)); }, k, pol.seed, pol.fold);
+    }
     const uint64_t f = murmur_bytes(gb, k, pol.seed, pol.fold);
     const uint64_t r = murmur_bytes([&](int q) -> uint8_t { return comp1(gb(k - 1 - q)); }, k, pol.seed, pol.fold);
     return f < r ? f : r;

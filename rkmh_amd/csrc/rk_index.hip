@@ -123,12 +123,13 @@ static void build_kpost(const std::vector<uint32_t>& post, int R, std::vector<ui
 
 // ---- the k-mer enumeration cache (rk_set_kmer_cache) ----
 // File: "RKKM1\n", u64 tag, u32 entries, then per entry {u32 k, u32 found, found x (u32 k-mer, u32 key id)}.  The tag is a hash of
-// everything the lists depend on: every index key in key-id order, the number of keys, fold and seed.  Any other file is ignored
+// everything the lists depend on: every index key in key-id order, the number of keys, fold, seed and the strand rule.  Any other file is ignored
 // (and overwritten after the enumeration has run): a cache never changes results, it only skips the work that would reproduce it.
 static uint64_t kmer_cache_tag(const rk_ctx* c, const std::vector<uint32_t>& dense, size_t nkeys) {
     uint64_t h = 0xcbf29ce484222325ull;
     auto mix = [&](uint64_t v) { h ^= v; h *= 0x100000001b3ull; h ^= h >> 29; };
     mix(0x726b6b6d31ull); mix((uint64_t)nkeys); mix((uint64_t)(uint32_t)c->pol.fold); mix((uint64_t)c->pol.seed);
+    if (c->pol.canon) mix(0x63616e6f6e00ull | (uint64_t)(uint32_t)c->pol.canon); // (canon=minhash: the tag files on disk already carry)
     for (size_t q = 0; q < nkeys; ++q) mix(((uint64_t)dense[q * 4 + 1] << 32) | dense[q * 4]);
     return h;
 }

@@ -527,7 +527,7 @@ __global__ __launch_bounds__(256) void k_enum_kmers(RefIndex ix, DevPolicy pol, 
     const int lane = threadIdx.x & 63;
     EnumQueue<uint32_t> Q{qmem[threadIdx.x >> 6], 0u};
     auto hash_one = [&](uint32_t v) {
-        const uint64_t h = canonical_packed(v, k, pol.seed, pol.fold);
+        const uint64_t h = canonical_packed(v, k, pol.seed, pol.fold, pol.canon);
         uint32_t slot = IDX_NOT_FOUND;
         if (h != 0) {
             if (ix.pre) { // hash-space filter first: one word instead of a bucket for the 99.99 % that are not keys
@@ -555,7 +555,7 @@ __global__ __launch_bounds__(256) void k_enum_kmers64(RefIndex ix, DevPolicy pol
     const int lane = threadIdx.x & 63;
     EnumQueue<uint64_t> Q{qmem[threadIdx.x >> 6], 0u};
     auto hash_one = [&](uint64_t v) {
-        const uint64_t h = canonical_packed64(v, k, pol.seed, pol.fold);
+        const uint64_t h = canonical_packed64(v, k, pol.seed, pol.fold, pol.canon);
         uint32_t slot = IDX_NOT_FOUND;
         if (h != 0) {
             if (ix.pre) {

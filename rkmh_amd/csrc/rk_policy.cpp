@@ -3,7 +3,9 @@
 // src/rkmh.cpp:17), so every choice the reference's tree does not fix (SURVEY.md section 8c, U1 ... U12) is a run-time switch: a user
 // holding the real rkmh can match it without rebuilding, and `mash` selects the variant the reference's README claims compatibility
 // with (README.md:12; hash type and seed of the schema, src/rkmh.cpp:493-497): the first 64 bits of MurmurHash3_x64_128, seed 42,
-// every one of the len - k + 1 windows.  Host code only.
+// every one of the len - k + 1 windows.  `mash` leaves the strand rule where it was (U2: both strands are hashed, the smaller HASH is
+// kept); canon=lexmin switches it to the rule Mash and sourmash publish (only the strand that is the smaller STRING is hashed).
+// Host code only.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -22,7 +24,8 @@ const Choice CHOICES[] = {
     {"windows", "len-k", 1}, {"windows", "len-k+1", 0},
     {"zero", "count", 1}, {"zero", "skip", 0},     // U12: does the 6-argument calc_hashes count the 0 sentinel
     {"mask", "lt", 1}, {"mask", "le", 0},          // U9: mask_by_frequency zeroes count < min (lt) or count <= min (le)
-    {"freqmax", "incl", 1}, {"freqmax", "excl", 0} // U10: minhashes_frequency_filter keeps count <= max (incl) or count < max
+    {"freqmax", "incl", 1}, {"freqmax", "excl", 0}, // U10: minhashes_frequency_filter keeps count <= max (incl) or count < max
+    {"canon", "minhash", RK_CANON_MINHASH}, {"canon", "lexmin", RK_CANON_LEXMIN} // U2: min of both strand hashes, or the hash of the smaller strand
 };
 int32_t* field(rk_policy* p, const char* key) {
     if (!strcmp(key, "fold")) return &p->fold;
@@ -30,6 +33,7 @@ int32_t* field(rk_policy* p, const char* key) {
     if (!strcmp(key, "zero")) return &p->counter_counts_zero;
     if (!strcmp(key, "mask")) return &p->mask_strict_less;
     if (!strcmp(key, "freqmax")) return &p->freq_max_inclusive;
+    if (!strcmp(key, "canon")) return &p->canon;
     return nullptr;
 }
 int bad(const std::string& msg) { rk__set_error(msg.c_str()); return RK_ERR_ARG; }
@@ -64,7 +68,7 @@ extern "C" int rk_policy_parse(const char* spec, rk_policy* p) {
             continue;
         }
         int32_t* f = field(p, key.c_str());
-        if (!f) return bad("hash policy: unknown key '" + key + "' (fold, windows, zero, mask, freqmax, seed)");
+        if (!f) return bad("hash policy: unknown key '" + key + "' (fold, windows, zero, mask, freqmax, canon, seed)");
         bool found = false;
         std::string names;
         for (const Choice& c : CHOICES) {
@@ -79,13 +83,16 @@ extern "C" int rk_policy_parse(const char* spec, rk_policy* p) {
 }
 
 // the canonical text of a policy, every key spelled out: "fold=swap32,windows=len-k,zero=count,mask=lt,freqmax=incl,seed=42".
+// canon= appears (between freqmax= and seed=) only when it is not minhash, so a policy without them reads as
+// it always did: the text is what sketch files record and what depth-map and k-mer caches are compared by.
 // Returns the length written (excluding the NUL) or RK_ERR_ARG (a value outside the known ones, or cap too small).
 extern "C" int rk_policy_describe(const rk_policy* p, char* dst, size_t cap) {
     if (!p || !dst) return bad("bad arguments");
     rk_policy q = *p;
     std::string out;
-    for (const char* key : {"fold", "windows", "zero", "mask", "freqmax"}) {
+    for (const char* key : {"fold", "windows", "zero", "mask", "freqmax", "canon"}) {
         const int32_t v = *field(&q, key);
+        if (v == RK_CANON_MINHASH && !strcmp(key, "canon")) continue;
         const char* name = nullptr;
         for (const Choice& c : CHOICES)
             if (!strcmp(c.key, key) && c.value == v && !name) name = c.name;
@@ -98,7 +105,9 @@ extern "C" int rk_policy_describe(const rk_policy* p, char* dst, size_t cap) {
     return (int)out.size();
 }
 
-// Do two policies give the same hash values and sketches (fold, window rule, seed)?  The other fields only act on depth counters.
+// Do two policies give the same hash values and sketches (fold, window rule, strand rule, seed)?  The other fields only
+// act on depth counters.
 extern "C" int rk_policy_same_hashes(const rk_policy* a, const rk_policy* b) {
-    return a && b && a->fold == b->fold && (a->drop_last_window != 0) == (b->drop_last_window != 0) && a->seed == b->seed ? 1 : 0;
+    return a && b && a->fold == b->fold && (a->drop_last_window != 0) == (b->drop_last_window != 0) && a->canon == b->canon &&
+           a->seed == b->seed ? 1 : 0;
 }
