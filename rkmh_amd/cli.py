@@ -215,7 +215,7 @@ def _device_ingest(ctx, rank, local, world, reads, ref_names, sketch, min_occ, m
     """This rank's byte range of every read file through the device FASTQ front end (rk_fastq_slot_*): worker threads read raw blocks
     straight into page-locked buffers, the GPU splits / checks / packs / classifies them, the lines are written in C from the names
     where they lie (rk_fastq_stream_lines / rk_fastq_filter_records) -- the host never parses a read, exactly as bin/rkmh does it
-    (rkmh_frontends.cpp, stream_files_raw).  -M: two such passes with the RCCL all-reduce of the table in between.  Returns this rank's
+    (rkmh_rawreads.cpp, stream_files_raw).  -M: two such passes with the RCCL all-reduce of the table in between.  Returns this rank's
     output is written to out_fd (see _RankOutput) and True returned -- or, when ANY rank met text that is not four lines per record,
     nothing is written and False returned (then every rank takes the parsing path)."""
     import threading

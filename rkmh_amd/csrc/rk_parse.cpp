@@ -987,7 +987,7 @@ void rk_seqset_free(rk_seqset* s) {
 // says how long the member is ('BC' extra field) -- so, unlike plain gzip (one deflate stream that only a sequential reader can
 // follow, src/rkmh.cpp:238-263 through gzFile), the members can be found without inflating anything and inflated by as many
 // threads as there are.  The device FASTQ front end's workers each inflate the members of their job straight in front of the
-// upload (rkmh_frontends.cpp, stream_files_raw); nothing in the process ever reads the file sequentially.
+// upload (rkmh_rawreads.cpp, stream_files_raw); nothing in the process ever reads the file sequentially.
 // Inflate = libdeflate when the system has it (dlopen: ~3 x zlib's rate per core), zlib otherwise; CRC-32 and ISIZE are checked.
 struct rk_bgzf {
     int fd = -1;

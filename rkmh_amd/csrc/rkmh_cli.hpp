@@ -1,12 +1,17 @@
 // rkmh_cli.hpp -- what the files of the `rkmh` command line share (the program on top of librkmh_amd.so, include/rkmh_amd.h).
 //   rkmh_main.cpp       main() and the dispatch to the sub-commands
 //   rkmh_exit.cpp       the fork for a fast exit, done_exit / fail_exit, stage timings, the CPUs this process may use, RKMH_* knobs
-//   rkmh_frontends.cpp  the device front ends (plain / BGZF / gzip FASTQ, packed reads, references), the host scanner pipeline,
-//                       the -M two-pass protocol and the registry of input files
+//   rkmh_frontends.cpp  what the front ends share: formatting and ordered output, the devices of a run, depth maps and the -M two-pass
+//                       protocol, the host scanner pipeline
+//   rkmh_rawreads.cpp   FASTQ read files through the device front end (plain / BGZF / gzip): the registry of input files, RawEngine,
+//                       stream_files_raw and two_pass_raw
+//   rkmh_packed.cpp     reads written by `rkmh pack` (-F)
+//   rkmh_refs.cpp       the -r files through the device
 //   rkmh_classify.cpp   stream / classify and filter: one driver, two thin commands
 //   rkmh_commands.cpp   call, sketch (and the JSON sketches stream -R reads), hash, hpv16, pack; the hashing policy and help text
 #pragma once
 #include <getopt.h>
+#include <sys/types.h>
 
 #include <atomic>
 #include <condition_variable>
@@ -30,8 +35,10 @@ extern const bool g_timing; // RKMH_TIMING: stage timings on stderr
 void tick(const char* what, double& t0);
 [[noreturn]] void done_exit();
 [[noreturn]] void fail_exit();
-[[noreturn]] void die(const char* what);
+[[noreturn]] void die(const char* what = nullptr); // "rkmh: [<what>: ]<rk_last_error()>" on stderr, then fail_exit
 #define CK(call) do { if ((call) != RK_OK) die(#call); } while (0)
+#define CKE(call, ...) do { if ((call) != RK_OK) die(__VA_ARGS__); } while (0) // the error alone, or behind a path: CKE(call, path)
+bool pread_full(int fd, void* dst, int64_t n, int64_t off); // all n bytes at off, or false
 void fork_for_fast_exit();
 int granted_cpus_main();
 // the RKMH_* knobs: env_flag -- unset: dflt, else atoi != 0; env_long -- unset or outside [lo, hi]: dflt
@@ -62,7 +69,7 @@ int main_hash(int argc, char** argv);
 int main_hpv16(int argc, char** argv);
 int main_pack(int argc, char** argv);
 
-// ---- stream / filter (rkmh_classify.cpp, rkmh_frontends.cpp)
+// ---- stream / filter (rkmh_classify.cpp, rkmh_frontends.cpp, rkmh_rawreads.cpp, rkmh_packed.cpp, rkmh_refs.cpp)
 struct Opts {
     std::vector<const char*> refs, reads;
     std::vector<const char*> packed; // -F <file>: reads written by `rkmh pack`
@@ -120,6 +127,7 @@ bool reads_fit_sketch(const rk_seqset& reads, const Opts& o);
 void make_depth_maps(DeviceGroup& g, uint64_t slots, bool compact, std::vector<rk_counter*>& cnts);
 bool two_pass(DeviceGroup& g, std::vector<rk_counter*>& cnts, uint64_t slots, int min_occ, const std::function<bool()>& count,
               const std::function<void()>& classify, double& t0, const char* tick_count = nullptr, const char* tick_classify = nullptr);
+extern std::atomic<bool> g_need_full; // a count pass met RK_ERR_NEED_FULL: two_pass repeats it with full tables
 void count_parsed(DeviceGroup& g, const rk_seqset& reads, std::vector<rk_counter*>& cnts);
 void classify_parsed(DeviceGroup& g, const rk_seqset& reads, int32_t* out4);
 
@@ -130,14 +138,57 @@ void emit_passing(const rk_seqset& reads, const int32_t* rows, const Opts& o, st
 struct FilterDecision { int ref; int shared; bool diff_ok; };
 FilterDecision filter_decide(const int32_t* r, int min_diff);
 
-// The input files of a run, each looked at once (rkmh_frontends.cpp): what a path was found to be, and its open archive.  Read files
+// The input files of a run, each looked at once (rkmh_rawreads.cpp): what a path was found to be, and its open archive.  Read files
 // and references share the table; `reads` marks the compressed files raw_eligible took as read files (the device front end's jobs).
 enum InputKind { IN_PLAIN, IN_BGZF, IN_GZIP }; // IN_PLAIN: not opened as an archive (uncompressed text, or anything else)
 struct Input { InputKind kind = IN_PLAIN; rk_bgzf* bz = nullptr; rk_gzip* gz = nullptr; bool reads = false; };
+Input& input_of(const char* path);             // opens the path as an archive when it is looked at for the first time
+const Input* known_input(const char* path);    // nullptr: not looked at yet
+inline int first_byte(const Input& in) { return in.kind == IN_BGZF ? rk_bgzf_first_byte(in.bz) : rk_gzip_first_byte(in.gz); }
+inline int64_t text_bytes(const Input& in) { return in.kind == IN_BGZF ? (int64_t)rk_bgzf_text_bytes(in.bz) : (int64_t)rk_gzip_text_bytes_hint(in.gz); }
 bool bgzf_on_device();
 bool raw_eligible(const char* path, int64_t* size, char first = '@');
 bool any_read_archive();
 void register_bgzf_mappings();
+
+// Formatted blocks leave in the order of their numbers.  A worker parks its finished block and goes straight on to its next one (it
+// only ever waits for memory: at most `window` blocks may be parked ahead of the one due); whoever parks the block that is DUE gives
+// the run of consecutive ready blocks their places in the output, in order, and hands them to the writer threads: several of them,
+// each with pwrite at the block's final offset, when standard output is a regular file (a file takes ~12 GB/s of buffered writes on the
+// test boxes, tools/ubench/file_write.cpp: the output is not what limits the pipeline), one with fwrite otherwise.
+struct OrderedOut {
+    struct Parked { std::vector<char> buf; size_t len = 0; off_t at = 0; bool keep = false; };
+    std::mutex m;
+    std::condition_variable cv, cv_task;
+    std::map<int64_t, Parked> parked;
+    std::deque<Parked> tasks;             // blocks with their place assigned, waiting for a writer
+    std::vector<std::vector<char>> spare; // buffers to format the next blocks into
+    std::vector<std::thread> writers;
+    int64_t next = 0;
+    size_t in_flight = 0;                 // tasks queued or being written
+    bool assigning = false, closing = false;
+    std::atomic<bool> failed{false};      // set by any writer thread
+    std::atomic<int64_t> limit{INT64_MAX}; // blocks from this number on are dropped, not written (another front end redoes them)
+    bool direct = false;                   // standard output is a regular file not opened for appending
+    off_t base = 0, total = 0;
+    void lower_limit(int64_t seq) { int64_t cur = limit.load(); while (seq < cur && !limit.compare_exchange_weak(cur, seq)) {} }
+    void start(size_t ndev = 1);
+    std::vector<char> take_buffer();
+    // buf[0 .. len) are the lines of block seq; the buffer becomes the sink's (a spare one comes back from take_buffer)
+    void put(int64_t seq, std::vector<char>&& buf, size_t len, int64_t window);
+    void finish();
+};
+struct Latch {
+    std::mutex m;
+    std::condition_variable cv;
+    int left = 0;
+    void done() { std::lock_guard<std::mutex> l(m); if (--left == 0) cv.notify_all(); }
+    void wait() { std::unique_lock<std::mutex> l(m); cv.wait(l, [&] { return left == 0; }); }
+};
+// one block's rows as lines / records (rk_format.cpp), and records [lo, hi) of a block as a result of their own
+rk_fastq_result sub_result(const rk_fastq_result& r, int64_t lo, int64_t hi);
+size_t format_raw(const rk_line_parts* lp, const rk_fastq_result& r, const uint8_t* text, std::vector<char>& buf);
+size_t format_filter_raw(const rk_fastq_result& r, const uint8_t* text, const Opts& o, std::vector<char>& buf);
 
 // Work handed to a few helper threads: the lines of a device-inflated BGZF job (hundreds of megabytes of text, millions of records)
 // are formatted piece by piece by all of them while its worker waits, each piece parked under its own block number

@@ -59,7 +59,8 @@ static void tell_parent(int status) {
     _exit(1);
 }
 [[noreturn]] void die(const char* what) {
-    fprintf(stderr, "rkmh: %s: %s\n", what, rk_last_error());
+    if (what) fprintf(stderr, "rkmh: %s: %s\n", what, rk_last_error());
+    else fprintf(stderr, "rkmh: %s\n", rk_last_error());
     fail_exit();
 }
 // A profiler's tool library has initialised the GPU runtime before main() (a forked child could not use it) and writes its tables

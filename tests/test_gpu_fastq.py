@@ -599,3 +599,70 @@ def test_cli_bgzf_payload_damage_is_refused_on_both_routes(root, data_dir, tmp_p
             assert r.returncode != 0, (level, env)
             assert b"corrupt BGZF member" in r.stderr, (level, env, r.stderr[-400:])
             assert r.stdout != want
+
+
+# ---- the stages of the read pipeline (rkmh_rawreads.cpp) that the larger command-line tests above do not reach: a few thousand reads each
+@pytest.fixture(scope="module")
+def few_reads(data_dir):
+    from rkmh_amd import api, synth
+    refs = api.parse_files([os.path.join(data_dir, "all_pave_ref.fa.gz")])
+    n = 4000
+    qb, qo = synth.generate_reads_fast(refs["bases"], refs["offsets"], 100000, 100000 + n, read_len=150, threads=4)
+    return [bytes(qb[int(qo[i]):int(qo[i + 1])]) for i in range(n)]
+
+
+def _stream_both_ways(root, data_dir, files, env, cmd="stream", flags=()):
+    """(stdout of the scanner, stdout and stderr of the device front end under env) of one command; both must end with status 0"""
+    args = [cmd, "-r", os.path.join(data_dir, "all_pave_ref.fa.gz"), "-k", "16", "-s", "1000"] + list(flags) + sum((["-f", str(f)] for f in files), [])
+    want = _cli(root, args, env={"RKMH_RAW": "0"})
+    r = subprocess.run([os.path.join(root, "bin", "rkmh")] + args, capture_output=True, env=dict(os.environ, RKMH_TIMING="1", **env), timeout=900)
+    assert r.returncode == 0, r.stderr.decode()[-1500:]
+    return want, r.stdout, r.stderr
+
+
+def test_cli_a_record_longer_than_the_block_is_handed_over(root, data_dir, tmp_path, few_reads):
+    """Four-line FASTQ whose middle holds one read of 70 000 bases, blocks of 40 KB: some range holds no record start at all, the
+    coordinator hands the file over from there and the scanner prints the rest -- same bytes as the scanner alone, status 0."""
+    n = len(few_reads)
+    long_read = bytes(np.random.default_rng(21).choice(np.frombuffer(b"ACGT", np.uint8), size=70000))
+    reads = few_reads[: n // 2] + [long_read] + few_reads[n // 2:]
+    fq = tmp_path / "long.fq"
+    fq.write_bytes(_fastq(reads, names=[b"lr%05d x" % i for i in range(len(reads))]))
+    for cmd in ("stream", "filter"):
+        want, got, err = _stream_both_ways(root, data_dir, [fq], {"RKMH_RAW_BLOCK_KB": "40"}, cmd=cmd)
+        assert got == want and len(want) > 1000, cmd
+        assert cmd != "stream" or want.count(b"\n") == n + 1
+        assert b"device front end: " in err and b"the scanner reads on from there" in err, err[-800:]
+
+
+def test_cli_three_files_the_second_turns_irregular(root, data_dir, tmp_path, few_reads):
+    """Three -f files, the second with its sequences on two lines from half way on: the first file comes from the device, the scanner
+    takes the rest of the second and all of the third, and the output is the scanner's for the three of them."""
+    import re
+    n = len(few_reads)
+    a, c = tmp_path / "a.fq", tmp_path / "c.fq"
+    a.write_bytes(_fastq(few_reads, names=[b"a%05d first file" % i for i in range(n)]))
+    c.write_bytes(_fastq(few_reads[:1500], names=[b"c%d" % i for i in range(1500)]))
+    odd = b"".join(b"@m%d\n" % i + r[:70] + b"\n" + r[70:] + b"\n+\n" + b"I" * len(r) + b"\n" for i, r in enumerate(few_reads[2000:2300]))
+    b = tmp_path / "b.fq"
+    b.write_bytes(_fastq(few_reads[:2000], names=[b"b%05d" % i for i in range(2000)]) + odd + _fastq(few_reads[2300:2800]))
+    want, got, err = _stream_both_ways(root, data_dir, [a, b, c], {"RKMH_RAW_BLOCK_KB": "64", "RKMH_RAW_WORKERS": "3"})
+    assert want.count(b"\n") == n + 2000 + 300 + 500 + 1500
+    assert got == want
+    assert str(b).encode() + b": not four lines per record" in err and b"the scanner reads on from there" in err, err[-800:]
+    assert int(re.search(rb"device front end: \d+ blocks, (\d+) records", err).group(1)) >= n     # all of the first file, at least
+
+
+def test_cli_mapped_file_whose_short_last_block_lacks_its_newline(root, data_dir, tmp_path, few_reads):
+    """RKMH_RAW_MMAP=1 on a file that ends without a newline, cut so that its last block is a short one: that block is copied and
+    completed, the output is that of the file with the newline."""
+    text = _fastq(few_reads, names=[b"mm%05d" % i for i in range(len(few_reads))])
+    assert len(text) % (96 << 10) not in (0, 1)
+    whole, nonl = tmp_path / "whole.fq", tmp_path / "nonl.fq"
+    whole.write_bytes(text)
+    nonl.write_bytes(text[:-1])
+    for cmd, flags in (("stream", ()), ("filter", ("-N", "3"))):
+        want, _, _ = _stream_both_ways(root, data_dir, [whole], {}, cmd=cmd, flags=flags)
+        _, got, err = _stream_both_ways(root, data_dir, [nonl], {"RKMH_RAW_MMAP": "1", "RKMH_RAW_BLOCK_KB": "96"}, cmd=cmd, flags=flags)
+        assert got == want and len(want) > 1000, cmd
+        assert b"device front end: " in err and b" %d records" % len(few_reads) in err, err[-600:]

@@ -283,3 +283,48 @@ def test_cli_gzip_references_through_the_device(tmp_path, data_dir):
     want2, _ = run([fa, panel_gz], {"RKMH_RAW_REFS": "0"})
     got2, err2 = run([fagz, panel_gz], {"RKMH_RAW_REFS": "1"})      # (the small panel is gzip as well; its lower-case text may send all of them to the host parser: same lines either way)
     assert got2 == want2
+
+
+def _few_reads_text(data_dir, n=4000):
+    from rkmh_amd import api, synth
+    refs = api.parse_files([os.path.join(data_dir, "all_pave_ref.fa.gz")])
+    qb, qo = synth.generate_reads_fast(refs["bases"], refs["offsets"], 200000, 200000 + n, read_len=150, threads=4)
+    rng = np.random.default_rng(17)
+    return b"".join(b"@gz%05d comment\n" % i + bytes(qb[int(qo[i]):int(qo[i + 1])]) + b"\n+\n" + bytes(rng.integers(33, 75, size=int(qo[i + 1] - qo[i]), dtype=np.uint8)) + b"\n"
+                    for i in range(n))
+
+
+def _scanner_and_device(data_dir, cmd, flags, files):
+    exe = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bin", "rkmh")
+    args = [exe, cmd, "-r", os.path.join(data_dir, "all_pave_ref.fa.gz"), "-k", "16", "-s", "1000"] + list(flags) + sum((["-f", str(f)] for f in files), [])
+    want = subprocess.run(args, capture_output=True, env=dict(os.environ, RKMH_RAW="0"))
+    got = subprocess.run(args, capture_output=True, env=dict(os.environ, RKMH_TIMING="1", RKMH_BGZF_TIMING="1"))
+    assert want.returncode == 0 and got.returncode == 0, (want.stderr[-600:], got.stderr[-600:])
+    return want.stdout, got.stdout, got.stderr
+
+
+def test_cli_the_same_gzip_file_twice(tmp_path, data_dir):
+    """-f r.fq.gz -f r.fq.gz: a gzip stream has a position, so the file is opened once more for its second turn -- the lines of the
+    file twice over, as the scanner prints them, for stream and filter"""
+    gz = tmp_path / "r.fq.gz"
+    gz.write_bytes(gzip.compress(_few_reads_text(data_dir), 6))
+    for cmd in ("stream", "filter"):
+        once, _, _ = _scanner_and_device(data_dir, cmd, (), [gz])
+        want, got, err = _scanner_and_device(data_dir, cmd, (), [gz, gz])
+        assert len(once) > 1000 and want == once + once
+        assert got == want, cmd
+        assert b"[gzip device]" in err and b"stops at byte" not in err and b" 8000 records" in err, err[-800:]
+
+
+def test_cli_minus_M_over_a_gzip_and_a_bgzf_file(tmp_path, data_dir):
+    """-M 2 over one ordinary gzip file and one BGZF file: pass 1 counts the gzip file stretch by stretch and the BGZF file job by job,
+    both passes run on the device front end, and the output is the parse-everything path's"""
+    from rkmh_amd import synth
+    text = _few_reads_text(data_dir)
+    gz, bg = tmp_path / "r.fq.gz", tmp_path / "r.bgzf.fq.gz"
+    gz.write_bytes(gzip.compress(text, 6))
+    bg.write_bytes(synth.bgzf_compress(text, level=1))
+    for cmd, flags in (("stream", ("-M", "2")), ("filter", ("-M", "2", "-N", "3"))):
+        want, got, err = _scanner_and_device(data_dir, cmd, flags, [gz, bg])
+        assert got == want and len(want) > 1000, cmd
+        assert b"device front end: " in err and b" 16000 records" in err and b"both passes" in err, err[-800:]
