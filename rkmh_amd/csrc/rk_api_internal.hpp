@@ -1,6 +1,8 @@
 // rk_api_internal.hpp -- what the translation units behind the C ABI (include/rkmh_amd.h) share: the context and counter objects, the
 // growable buffers, the error plumbing and the handful of internal entry points one part needs from another.
-//   rk_api.hip       contexts, errors, the general path (any length), the one-sequence mirrors of the mkmh calls, the classify routing
+//   rk_api.hip       contexts, errors, host memory (page-locked buffers, the staged upload), the mirrors that are one copy-launch-copy
+//   rk_general.hip   the general path (any length) as plan / upload and hash / count / sort / download, and the entry points that are one run of it
+//   rk_route.hip     the classify / count routing: fused kernels, re-routes through the general path, the double-buffered host pipeline
 //   rk_index.hip     reference sketches -> the resident index (buckets, postings, k-mer-space structures), depth filter masks
 //   rk_counters.hip  HASHTCounter (full and compact), its (de)serialisation
 //   rk_frontend.hip  FASTQ slots (text parsed on the device), BGZF jobs inflated on the device, reference FASTA through the device
@@ -17,6 +19,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -151,7 +154,7 @@ struct rk_ctx {
 
 inline int set_dev(rk_ctx* c) { HIPCHK(hipSetDevice(c->device)); return RK_OK; }
 
-// ---- the general path (rk_api.hip): hash tiles -> (optional) in-LDS sort / sketch / intersect, for sequences of any length
+// ---- the general path (rk_general.hip): hash tiles -> (optional) in-LDS sort / sketch / intersect, for sequences of any length
 struct GeneralOut {
     uint64_t* hashes = nullptr;      // host, [total hashes of the batch] (caller sized via hash_offsets)
     uint64_t* sketches = nullptr;    // host [n*S]
@@ -212,12 +215,28 @@ inline void par_memcpy(void* dst, const void* src, size_t n) {
 
 // ---- internal entry points shared between the parts (defined in the file named) ----
 int check_ks(const int* ks, int nks, KsArr* out);                                                           // rk_api.hip
-uint32_t next_pow2(uint32_t x);
-void apply_depth_cfg(const rk_ctx* c, GeneralCfg& cfg);
-int general_run(rk_ctx* c, const uint8_t* bases, const uint8_t* d_bases_in, const uint64_t* offsets, int64_t n, const GeneralCfg& cfg, const GeneralOut& out);
 bool is_pinned_host(const void* p, size_t bytes);
+// is_pinned_host for a caller's buffer: page-locked by the caller, not merely overlapping a temporary registration of ours
+bool caller_pinned_host(const void* p, size_t bytes);
+// page-locks a caller's pageable buffer of at least min_bytes for the duration of one call; `ok` says whether it did (rk_api.hip)
+struct ScopedHostRegister {
+    uintptr_t lo = 0, hi = 0;
+    bool ok = false;
+    ScopedHostRegister(const void* p, size_t bytes, size_t min_bytes);
+    ~ScopedHostRegister();
+    ScopedHostRegister(const ScopedHostRegister&) = delete;
+    ScopedHostRegister& operator=(const ScopedHostRegister&) = delete;
+};
 int upload_staged(rk_ctx* c, void* dst, const uint8_t* src, size_t bytes, hipStream_t st);
-int fused_device(rk_ctx* c, const void* d_bases, const void* d_offs, int64_t nreads, void* d_out4, uint32_t max_read_len, int mode, rk_counter* count_into,
+// hashes a sequence of `len` bases has: its windows at every k-mer size
+inline uint64_t hashes_of(const DevPolicy& pol, const KsArr& ks, uint64_t len) {
+    uint64_t nh = 0;
+    for (int j = 0; j < ks.n; ++j) nh += (uint64_t)num_windows((int)len, ks.k[j], pol.drop_last_window);
+    return nh;
+}
+GeneralCfg classify_cfg(const rk_ctx* c); // classification against the context's references, its depth filter applied   // rk_general.hip
+int general_run(rk_ctx* c, const uint8_t* bases, const uint8_t* d_bases_in, const uint64_t* offsets, int64_t n, const GeneralCfg& cfg, const GeneralOut& out);
+int fused_device(rk_ctx* c, const void* d_bases, const void* d_offs, int64_t nreads, void* d_out4, uint32_t max_read_len, int mode, rk_counter* count_into, // rk_route.hip
                  hipStream_t st, uint64_t total_bases = 0);
 // rows the fused kernel flagged (max_id == -2; `rows` = host copy of d_out4) answered by the general kernels on the resident bases and scattered back into d_out4 AND rows; synchronises st
 int reroute_flagged_device(rk_ctx* c, const void* d_bases, const void* d_offs, int64_t nreads, void* d_out4, int32_t* rows, hipStream_t st);

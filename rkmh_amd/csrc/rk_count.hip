@@ -10,7 +10,7 @@
 //   k_slot_scatter  per span: chunks of 16384 slots are counting-sorted by bin in LDS and appended to the bins in runs
 //   k_count_bins    per (bin, sub-range): the bin's slots are read (L2), those of the sub-range counted in 128 KB of LDS
 //                   counters, and the counters ADDED to the table with plain 16-byte read-modify-writes (a sub-range has one
-//                   owner per launch; launches into one table are chained by an event in rk_api.hip)
+//                   owner per launch; launches into one table are chained by an event in rk_route.hip)
 // All streaming: ~0.6 GB written + read per stage at C2 instead of 1.35e8 atomics.
 #include "rk_kernels.hpp"
 

@@ -647,7 +647,7 @@ struct RefIndex {
     const uint4* km1;      // single-probe exact map (see KM1_C above), 2^km1_b buckets
     uint32_t km1_b;
     const uint32_t* km1_vals;
-    // posting lists of the k-mer-space kernel (rk_api.hip, build_kpost): identical lists stored once, lists close to one of up to
+    // posting lists of the k-mer-space kernel (rk_index.hip, build_kpost): identical lists stored once, lists close to one of up to
     // eight BASE lists stored as (base, exceptions); kbase = [8 x (start, members)] then the members
     const uint32_t* kpost;
     const uint32_t* kbase;

@@ -1,7 +1,7 @@
 // rk_format.cpp -- the output of stream / classify / filter for one block of the device FASTQ front end (rk_fastq_slot_*), written
 // from the record names (sequences, quality strings) WHERE THEY LIE in the block's raw text: the host side of the per-read loop of
-// /root/reference/src/rkmh.cpp:845-898 shrinks to this.  Line format: rkmh.cpp:887-892; filter's records: rkmh.cpp:1292-1300 with
-// the decision of classify_and_count_diff_filter (/root/reference/src/equiv.hpp:324-353).  Used by bin/rkmh (rkmh_frontends.cpp) and,
+// src/rkmh.cpp:845-898 of the reference shrinks to this.  Line format: rkmh.cpp:887-892; filter's records: rkmh.cpp:1292-1300 with
+// the decision of classify_and_count_diff_filter (src/equiv.hpp:324-353).  Used by bin/rkmh (rkmh_frontends.cpp) and,
 // through ctypes, by the one-process-per-GPU front end (rkmh_amd/cli.py).
 #include "../../include/rkmh_amd.h"
 #include "rk_filter_rule.hpp"
@@ -73,6 +73,29 @@ extern "C" int rk_line_parts_create(const char* ref_names, const uint64_t* name_
     return RK_OK;
 }
 extern "C" void rk_line_parts_destroy(rk_line_parts* lp) { delete lp; }
+
+extern "C" int rk_format_stream_line(char* dst, size_t cap, const char* ref_name, const char* read_name,
+                                     int max_shared, int diff, int min_num, int sketch_size, int min_matches, int min_diff) {
+    // src/rkmh.cpp:887-892: ref \t read \t max_shared \t sketch_size<depth filter> \t <match filter> \t <diff filter> \n
+    const bool diff_filter = diff > min_diff;
+    const bool depth_filter = min_num <= min_matches;
+    const bool match_filter = max_shared < min_matches;
+    const size_t ln = strlen(ref_name), lq = strlen(read_name);
+    if (ln + lq + 64 >= cap) return bad("line buffer too small");
+    char* w = dst;
+    memcpy(w, ref_name, ln); w += ln; *w++ = '\t';
+    memcpy(w, read_name, lq); w += lq; *w++ = '\t';
+    w = put_int(w, max_shared); *w++ = '\t';
+    w = put_int(w, sketch_size);
+    if (depth_filter) { memcpy(w, "FAIL:DEPTH", 10); w += 10; }
+    *w++ = '\t';
+    if (match_filter) { memcpy(w, "FAIL:MATCHES", 12); w += 12; }
+    *w++ = '\t';
+    if (!diff_filter) { memcpy(w, "FAIL:DIFF", 9); w += 9; }
+    *w++ = '\n';
+    *w = '\0';
+    return (int)(w - dst);
+}
 
 extern "C" uint64_t rk_fastq_stream_lines_bound(const rk_line_parts* lp, const rk_fastq_result* r) {
     if (!lp || !r || r->status != 0) return 64;

@@ -402,7 +402,7 @@ __global__ __launch_bounds__(KW, BIG ? 2 : KM_WAVES) void k_classify_kmer(const 
                 }
             };
             // A list's header and its first sixteen postings are requested TOGETHER (the posting array ends in 256 bytes of padding,
-            // rk_api.hip), and the NEXT hit's while this one is counted: the posting lists live in global memory and a row used to pay
+            // rk_index.hip), and the NEXT hit's while this one is counted: the posting lists live in global memory and a row used to pay
             // two dependent round trips per hit, one hit after the other.
             uint32_t j = g;
             uint32_t tr = 0, n = 0;

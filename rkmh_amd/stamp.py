@@ -5,9 +5,9 @@ import os
 
 _ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 _CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
-# everything that shapes the profiled kernel's instruction counts and traffic: the kernels, the shared device code, the index /
-# filter / map sizing on the host side (rk_api.hip), and the build flags
-KERNEL_SOURCES = ("rk_kmer.hip", "rk_classify.hip", "rk_device.hpp", "rk_kernels.hip", "rk_kernels.hpp", "rk_api.hip")
+# everything that shapes the profiled kernel's instruction counts and traffic: the kernels, the shared device code, the sizing of
+# the kernel's per-read hit multiset on the host side (fused_device, rk_route.hip), and the build flags
+KERNEL_SOURCES = ("rk_kmer.hip", "rk_classify.hip", "rk_device.hpp", "rk_kernels.hip", "rk_kernels.hpp", "rk_route.hip")
 
 
 def kernel_source_stamp() -> str:
