@@ -46,6 +46,8 @@ extern "C" {
 /* Unpinned mkmh choices -- identical meaning to oracle/rk_oracle.h */
 enum { RK_FOLD_SWAP32 = 0, RK_FOLD_H1 = 1, RK_FOLD_W2W1 = 2 };
 enum { RK_CANON_MINHASH = 0, RK_CANON_LEXMIN = 1 };
+/* U6 rides in the `canon` word (its layout is fixed): the low byte is the strand rule, bit 8 the sketch rule */
+enum { RK_CANON_STRAND_MASK = 0xFF, RK_DEDUP_DISTINCT = 0x100 };
 typedef struct rk_policy {
     int32_t fold;                /* U1 */
     int32_t drop_last_window;    /* U3: 1 => len-k windows */
@@ -54,18 +56,25 @@ typedef struct rk_policy {
     int32_t freq_max_inclusive;  /* U10 */
     uint32_t seed;               /* 42, src/rkmh.cpp:497 */
     int32_t canon;               /* U2: RK_CANON_MINHASH = both strands are hashed, the smaller hash is kept; RK_CANON_LEXMIN = only the
-                                    strand that is the smaller upper-case string (A < C < G < T) is hashed; a palindrome is its own */
+                                    strand that is the smaller upper-case string (A < C < G < T) is hashed; a palindrome is its own.
+                                    U6, bit 8 (RK_DEDUP_DISTINCT): a sketch holds the S smallest DISTINCT non-zero hashes and
+                                    intersections are set intersections (Mash, sourmash); clear = mkmh's multiset.  Read the word
+                                    through rk_policy_strand / rk_policy_dedup. */
 } rk_policy;
+int rk_policy_strand(const rk_policy* p); /* the strand rule: RK_CANON_MINHASH / RK_CANON_LEXMIN */
+int rk_policy_dedup(const rk_policy* p);  /* the sketch rule: 0 = multiset, 1 = distinct */
 void rk_default_policy(rk_policy* p);
 /* The policy as text -- what `--hash-policy` / RKMH_POLICY of bin/rkmh and rkmh_amd.cli take and what a sketch file records
  * ("hashPolicy", next to the hashType / hashSeed keys of src/rkmh.cpp:493-497).  spec = comma-separated items applied left to
  * right onto *p (initialise it first, e.g. rk_default_policy): a preset -- `default`, or `mash`: the first 64 bits of
- * MurmurHash3_x64_128 over all len-k+1 windows, seed 42 (the strand rule stays: the smaller of the two strand hashes) -- or key=value:
+ * MurmurHash3_x64_128 over all len-k+1 windows, seed 42 (the strand rule stays: the smaller of the two strand hashes), or
+ * `sourmash` = mash,canon=lexmin,dedup=distinct -- or key=value:
  * fold=swap32|h1|w2w1 (U1), windows=len-k|len-k+1 (U3), zero=count|skip (U12), mask=lt|le (U9), freqmax=incl|excl (U10),
- * canon=minhash|lexmin (U2; lexmin = the strand rule of Mash and sourmash), seed=<n>.
- * rk_policy_describe writes the canonical text with every key spelled out, canon= only when it is not minhash (returns its length
- * or a negative error).
- * rk_policy_same_hashes: 1 when two policies give the same hash values and sketches (fold, window rule, canon, seed). */
+ * canon=minhash|lexmin (U2; lexmin = the strand rule of Mash and sourmash), dedup=multiset|distinct (U6; distinct = the sketch
+ * rule of Mash and sourmash; `default` and `mash` leave it alone), seed=<n>.
+ * rk_policy_describe writes the canonical text with every key spelled out, canon= only when it is not minhash and, behind it,
+ * dedup= only when it is distinct (returns its length or a negative error).
+ * rk_policy_same_hashes: 1 when two policies give the same hash values and sketches (fold, window rule, canon, dedup, seed). */
 int rk_policy_parse(const char* spec, rk_policy* p);
 int rk_policy_describe(const rk_policy* p, char* dst, size_t cap);
 int rk_policy_same_hashes(const rk_policy* a, const rk_policy* b);

@@ -30,6 +30,28 @@ class Policy(C.Structure):
     _fields_ = [("fold", C.c_int32), ("drop_last_window", C.c_int32), ("counter_counts_zero", C.c_int32),
                 ("mask_strict_less", C.c_int32), ("freq_max_inclusive", C.c_int32), ("seed", C.c_uint32),
                 ("canon", C.c_int32)]
+    # `canon` holds two rules (include/rkmh_amd.h): the strand rule in its low byte, the sketch rule (U6) in bit 8
+    STRAND_MASK, DEDUP_DISTINCT = 0xFF, 0x100
+
+    @property
+    def strand(self):
+        """The strand rule (rk_policy_strand): 0 = minhash, 1 = lexmin."""
+        return self.canon & self.STRAND_MASK
+
+    @strand.setter
+    def strand(self, v):
+        if not 0 <= int(v) <= self.STRAND_MASK:
+            raise ValueError("strand rule outside [0, 255]")
+        self.canon = (self.canon & ~self.STRAND_MASK) | int(v)
+
+    @property
+    def dedup(self):
+        """The sketch rule (rk_policy_dedup): 0 = multiset (every copy of a value is kept), 1 = distinct values."""
+        return 1 if self.canon & self.DEDUP_DISTINCT else 0
+
+    @dedup.setter
+    def dedup(self, v):
+        self.canon = (self.canon & ~self.DEDUP_DISTINCT) | (self.DEDUP_DISTINCT if v else 0)
 
 
 class CallRecord(C.Structure):
@@ -54,6 +76,8 @@ _SIGS = {
     "rk_policy_parse": (C.c_int, [C.c_char_p, C.POINTER(Policy)]),
     "rk_policy_describe": (C.c_int, [C.POINTER(Policy), C.c_char_p, C.c_size_t]),
     "rk_policy_same_hashes": (C.c_int, [C.POINTER(Policy), C.POINTER(Policy)]),
+    "rk_policy_strand": (C.c_int, [C.POINTER(Policy)]),
+    "rk_policy_dedup": (C.c_int, [C.POINTER(Policy)]),
     "rk_ctx_policy": (C.c_int, [C.c_void_p, C.POINTER(Policy)]),
     "rk_last_error": (C.c_char_p, []),
     "rk_version": (C.c_char_p, []),
@@ -831,7 +855,7 @@ class Counter:
 
 
 def parse_policy(spec=None, base=None):
-    """rk_policy_parse: `spec` (presets default / mash, or fold= / windows= / zero= / mask= / freqmax= / canon= / seed=) applied onto `base`
+    """rk_policy_parse: `spec` (presets default / mash / sourmash, or fold= / windows= / zero= / mask= / freqmax= / canon= / dedup= / seed=) applied onto `base`
     (default: the build's defaults).  Raises RkmhError on text it does not know."""
     lib = load_library()
     p = Policy()
@@ -857,7 +881,7 @@ class Context:
     """One GPU. Methods are named after the reference's functions they replace."""
 
     def __init__(self, device=0, policy_spec=None, **policy):
-        """policy_spec: the text form (`--hash-policy` of the command lines: presets default / mash, key=value; rk_policy_parse),
+        """policy_spec: the text form (`--hash-policy` of the command lines: presets default / mash / sourmash, key=value; rk_policy_parse),
         applied to the defaults first; keyword arguments then set single fields of the struct."""
         self._lib = load_library()
         p = parse_policy(policy_spec)

@@ -19,8 +19,8 @@ import numpy as np
 from . import api, dist as rdist
 
 HELP = """rkmh stream|classify -r <refs.fa> -f <reads.fq> [-k <k>]... [-s <sketch>] [-M n] [-I n] [-N n] [-D n] [--hash-policy <spec>]
-  --hash-policy <spec>   presets (default, mash) and/or fold=swap32|h1|w2w1, windows=len-k|len-k+1, zero=count|skip, mask=lt|le,
-                         freqmax=incl|excl, canon=minhash|lexmin, seed=<n> (rk_policy_parse); RKMH_POLICY: the same, read first
+  --hash-policy <spec>   presets (default, mash, sourmash) and/or fold=swap32|h1|w2w1, windows=len-k|len-k+1, zero=count|skip, mask=lt|le,
+                         freqmax=incl|excl, canon=minhash|lexmin, dedup=multiset|distinct, seed=<n> (rk_policy_parse); RKMH_POLICY: the same, read first
 """
 
 

@@ -55,10 +55,14 @@ extern "C" int rk_ctx_create(int device, const rk_policy* policy, rk_ctx** out) 
     c->device = device;
     rk_policy p;
     if (policy) p = *policy; else rk_default_policy(&p);
-    if (p.canon != RK_CANON_MINHASH && p.canon != RK_CANON_LEXMIN) { delete c; return fail(RK_ERR_ARG, "hash policy: field 'canon' holds an unknown value"); }
+    if ((rk_policy_strand(&p) != RK_CANON_MINHASH && rk_policy_strand(&p) != RK_CANON_LEXMIN) || (p.canon & ~(RK_CANON_STRAND_MASK | RK_DEDUP_DISTINCT)) != 0) {
+        delete c; return fail(RK_ERR_ARG, "hash policy: field 'canon' holds an unknown value");
+    }
     c->pol.fold = p.fold; c->pol.drop_last_window = p.drop_last_window;
     c->pol.counter_counts_zero = p.counter_counts_zero; c->pol.mask_strict_less = p.mask_strict_less;
-    c->pol.freq_max_inclusive = p.freq_max_inclusive; c->pol.seed = p.seed; c->pol.canon = p.canon;
+    c->pol.freq_max_inclusive = p.freq_max_inclusive; c->pol.seed = p.seed;
+    c->pol.canon = rk_policy_strand(&p); // the kernels' policy carries the strand rule alone; U6 acts through the launches (c->dedup)
+    c->dedup = rk_policy_dedup(&p) != 0;
     HIPCHK(hipStreamCreateWithFlags(&c->st, hipStreamNonBlocking));
     for (auto& s : c->slot) {
         HIPCHK(hipStreamCreateWithFlags(&s.st, hipStreamNonBlocking));
@@ -71,7 +75,7 @@ extern "C" int rk_ctx_policy(const rk_ctx* c, rk_policy* out) {
     if (!c || !out) return fail(RK_ERR_ARG, "bad arguments");
     out->fold = c->pol.fold; out->drop_last_window = c->pol.drop_last_window; out->counter_counts_zero = c->pol.counter_counts_zero;
     out->mask_strict_less = c->pol.mask_strict_less; out->freq_max_inclusive = c->pol.freq_max_inclusive; out->seed = c->pol.seed;
-    out->canon = c->pol.canon;
+    out->canon = c->pol.canon | (c->dedup ? RK_DEDUP_DISTINCT : 0);
     return RK_OK;
 }
 extern "C" void rk_ctx_destroy(rk_ctx* c) {
@@ -79,7 +83,7 @@ extern "C" void rk_ctx_destroy(rk_ctx* c) {
     hipError_t e = hipSetDevice(c->device); (void)e;
     e = hipDeviceSynchronize(); (void)e;
     for (DevBuf* b : {&c->d_fpb, &c->d_base, &c->d_kv, &c->d_post, &c->d_pre, &c->d_keepbits, &c->d_kpost, &c->d_kbase, &c->d_kkeys, &c->d_kslots, &c->w_bases, &c->w_tiles, &c->w_hashes, &c->w_segoff,
-                      &c->w_ids, &c->w_sk, &c->w_lens, &c->w_out, &c->w_misc, &c->w_sel, &c->w_selstate, &c->w_table, &c->w_gcount, &c->w_tail}) b->release();
+                      &c->w_ids, &c->w_sk, &c->w_lens, &c->w_out, &c->w_misc, &c->w_sel, &c->w_selstate, &c->w_table, &c->w_gcount, &c->w_tail, &c->w_dedup}) b->release();
     for (int j = 0; j < KM_MAX_KS; ++j) { c->d_kf4[j].release(); c->d_km1[j].release(); c->d_km1v[j].release(); c->d_km1m[j].release(); c->d_km1cells[j].release(); }
     c->d_keepkey.release(); c->d_kvm.release();
     for (auto& s : c->slot) {

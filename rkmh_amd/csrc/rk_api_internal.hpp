@@ -115,6 +115,7 @@ struct rk_ctx {
     int device = 0;
     hipStream_t st = nullptr;
     DevPolicy pol{};
+    bool dedup = false; // policy U6 (dedup=distinct): sketches hold distinct values, row field 3 counts distinct hashes
     // references
     int nref = 0, S = 0;
     KsArr ks{};
@@ -147,7 +148,7 @@ struct rk_ctx {
     uint32_t km1_ncells[KM_MAX_KS] = {0}, km1_vmask[KM_MAX_KS] = {0};
     KmerSets ksets_m{};                      // ksets with km1 = the masked copies (valid while a bounded depth filter is set)
     // workspaces for the general path
-    DevBuf w_bases, w_tiles, w_hashes, w_segoff, w_ids, w_sk, w_lens, w_out, w_misc, w_sel, w_selstate, w_table, w_gcount, w_tail;
+    DevBuf w_bases, w_tiles, w_hashes, w_segoff, w_ids, w_sk, w_lens, w_out, w_misc, w_sel, w_selstate, w_table, w_gcount, w_tail, w_dedup;
     int ref_count_mode = 0; // -I counter fill: 0 per k-mer occurrence (stream), 1 once per distinct hash per reference (filter)
     Slot slot[2];
 };

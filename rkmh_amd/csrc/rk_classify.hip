@@ -101,7 +101,10 @@ struct TileGeom {
     uint32_t magic;     // ... ceil(2^32 / magic_nw): the compact window -> read division of tiles made of such reads
     int32_t nmin_cap;   // row field 3 = min(non-zero hashes, nmin_cap) (-M with a bounded min_num: rk_set_min_num_bound; else INT_MAX)
     CompactSlots cs;    // count pass into a compact depth map (cs.tab != nullptr): `counter` then holds one entry per tracked slot
+    int32_t uset;       // DEDUP forms: 8-byte slots of the per-read set of distinct hashes (power of two, >= twice the windows of the longest
+                        // read, <= DEDUP_MAX_SLOTS); 0 otherwise.  (Last: the kernel arguments of the other forms stay where they were.)
 };
+constexpr int DEDUP_MAX_SLOTS = 4096; // a read of more than 2048 windows is handed back by the DEDUP forms
 
 __host__ __device__ inline int tile_map_words(int cap_bytes) { return cap_bytes / 32 + 2; }
 __host__ __device__ inline int tile_stage_dwords(const TileGeom& g) { return stage_lds_dwords(g.cap_bytes); }
@@ -109,7 +112,7 @@ __host__ __device__ inline size_t tile_lds_bytes(const TileGeom& g) {
     const size_t q_dw = 4 * (size_t)g.qcap; // queue region: 16-byte entries {hash, read}
     return ((size_t)((tile_stage_dwords(g) + 3) & ~3) + q_dw + 5 * (size_t)(g.T + 1) + 8 +
             2 * (size_t)tile_map_words(g.cap_bytes) +
-            (size_t)g.T * (size_t)(g.cwords + g.dset)) * 4;
+            (size_t)g.T * (size_t)(g.cwords + g.dset) + (g.uset ? 2 + 2 * (size_t)g.T * (size_t)g.uset : 0)) * 4;
 }
 
 // for every posting (ref, mult) of an index value
@@ -166,11 +169,17 @@ __device__ __forceinline__ void word_wait(uint32_t&) {}
 // MODE_ 3 / 4: MODE 0 / 2 with the first-level filter of large panels (RefIndex::pre) in front of the bucket table
 // CANON: the strand rule (policy U2) as a template parameter -- false (minhash) leaves every instantiation the code it was before
 // the key existed; true (lexmin) exists for the run-time-k form only (KT = 0, FOLD = -1), which the launcher picks under that policy
-template <int KT, int MODE_, int FOLD, int PF, bool CANON = false>
+// DEDUP: the sketch rule (policy U6, dedup=distinct), the same way: true counts a read's DISTINCT non-zero hashes for row field 3 and the
+// "more hashes than the sketch keeps" test -- every canonical hash that survives the mask goes into an exact per-read set in LDS
+// (open addressing, full 64-bit keys, CAS), and an occurrence that finds its value there is treated as a dropped window (counted
+// with the zeros, never looked up).  The index holds multiplicity 1 everywhere under that policy, so first occurrences alone give the
+// set intersection.  Classify modes of the run-time-k form only.
+template <int KT, int MODE_, int FOLD, int PF, bool CANON = false, bool DEDUP = false>
 __global__ __launch_bounds__(WAVE, RK_WAVES_PER_SIMD) void k_classify_tile(const uint8_t* __restrict__ bases, const uint32_t* __restrict__ offs,
                                                            uint32_t nreads, KsArr ks, int S, RefIndex ix, int32_t* counter,
                                                            uint64_t slots, int min_occ, int32_t* out4, DevPolicy pol, TileGeom geo) {
     static_assert(!CANON || KT == 0, "canon=lexmin is served by the run-time-k form");
+    static_assert(!DEDUP || (KT == 0 && MODE_ != 1), "dedup=distinct is served by the classify modes of the run-time-k form");
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
     constexpr bool PRE = MODE_ >= 3;
     constexpr int MODE = MODE_ == 3 ? 0 : (MODE_ == 4 ? 2 : MODE_);
@@ -193,6 +202,9 @@ __global__ __launch_bounds__(WAVE, RK_WAVES_PER_SIMD) void k_classify_tile(const
     // [64][2] hits with several postings (drain).  Aliases the first 32 queue entries: a drain step has its 64
     // entries in registers before it writes here, and entries left for later sit at index >= 64.
     uint32_t* mq = reinterpret_cast<uint32_t*>(qe);
+    // DEDUP: [T][US] distinct hashes of read t (0 = empty), on an 8-byte boundary behind dset
+    const uint32_t US = DEDUP ? (uint32_t)geo.uset : 0u;
+    unsigned long long* uset = reinterpret_cast<unsigned long long*>(smem + (((uint32_t)(dset + (uint32_t)T * DS - smem) + 1u) & ~1u));
     const int lane = threadIdx.x;
     const uint64_t lt_mask = (1ull << lane) - 1ull;
     const uint32_t clg = (uint32_t)geo.clg, cper_m1 = (1u << clg) - 1u, cbits = 32u >> clg, cmask = (1u << cbits) - 1u;
@@ -301,6 +313,7 @@ __global__ __launch_bounds__(WAVE, RK_WAVES_PER_SIMD) void k_classify_tile(const
                 // a read with more windows than a packed counter can count (only possible when the caller's length hint was
                 // too small for this read: 8-bit counters are chosen for hints of <= 255 windows) takes the general path
                 flags[lane] = nw > (geo.csparse ? 0x7FFu : cmask) ? 1u : 0u;
+                if (DEDUP && 2u * nw > US) flags[lane] = 1u; // more windows than the set is sized for (the caller's length hint was too small)
             }
         }
         const uint32_t ulen = (uint32_t)__builtin_amdgcn_readfirstlane((int)(o_next - cur_o)); // length of read 0
@@ -308,6 +321,8 @@ __global__ __launch_bounds__(WAVE, RK_WAVES_PER_SIMD) void k_classify_tile(const
         const uint32_t bad_words = (B + 31) / 32 + 1;
         if (MODE != 1)
             for (uint32_t i = lane; i < (uint32_t)Tn * DS; i += WAVE) dset[i] = 0;
+        if constexpr (DEDUP)
+            for (uint32_t i = lane; i < (uint32_t)Tn * US; i += WAVE) uset[i] = 0ull;
         const uint32_t ndw = ((tstart & 3u) + B + 3u) >> 2; // global dwords covering the tile
         // byte masks of the tile's first and last global dword (bytes of neighbouring tiles are not ours to judge)
         const uint32_t m_first = ~0u << (8u * (tstart & 3u));
@@ -572,6 +587,16 @@ __global__ __launch_bounds__(WAVE, RK_WAVES_PER_SIMD) void k_classify_tile(const
                                     if (!((wbits >> ((uint32_t)slot & 31u)) & 1u)) hh = 0;
                                 }
                                 if (hh == 0) atomicAdd(&nzero[tt], 1u);
+                                else if constexpr (DEDUP) { // a value the read already holds is no further sketch entry: dropped like a zero
+                                    unsigned long long* us = uset + tt * US;
+                                    uint32_t idx = (uint32_t)((hh * 0x9E3779B97F4A7C15ull) >> 40) & (US - 1u);
+                                    for (uint32_t probe = 0; probe < US; ++probe) { // (only a flagged read can fill its set)
+                                        const unsigned long long old = atomicCAS(&us[idx], 0ull, (unsigned long long)hh);
+                                        if (old == 0ull) break;
+                                        if (old == hh) { atomicAdd(&nzero[tt], 1u); hh = 0; break; }
+                                        idx = (idx + 1u) & (US - 1u);
+                                    }
+                                }
                             }
                         };
                         const bool split = compact && it + 1 == nIt && nW - it * WAVE <= 32u && !CANON; // wave-uniform (lexmin hashes one strand: nothing to share)
@@ -775,9 +800,10 @@ struct TileKnobs {
 };
 static const TileKnobs& knobs() { static const TileKnobs k; return k; }
 
-static TileGeom make_geom(int maxlen, int nref, int expect_hits, int win_per_read, int win_total) {
+static TileGeom make_geom(int maxlen, int nref, int expect_hits, int win_per_read, int win_total, int uset = 0) {
     const TileKnobs& kn = knobs();
     TileGeom g;
+    g.uset = uset;
     if (maxlen < 1) maxlen = 1;
     g.qcap = kn.qcap > 0 ? kn.qcap : 128;
     g.clg = win_total <= 255 ? 2 : 1;
@@ -804,7 +830,8 @@ static TileGeom make_geom(int maxlen, int nref, int expect_hits, int win_per_rea
     int tmax = 1;
     double best_fill = -1.0;
     for (int T = 1; T <= 16; ++T) {
-        if (T > 1 && (!fits(T, LDS_BUDGET_6_WAVES) || T * maxlen > 3 * WAVE * 4 - 8)) break;
+        // (DEDUP forms: four reads' sets on top of the budget -- one read per tile costs more than the occupancy does)
+        if (T > 1 && (!fits(T, LDS_BUDGET_6_WAVES + (size_t)uset * 8 * 4) || T * maxlen > 3 * WAVE * 4 - 8)) break;
         const int nw = T * win_per_read;
         fill[T] = (double)nw / (double)(((nw + WAVE - 1) / WAVE) * WAVE);
         if (fill[T] > best_fill) best_fill = fill[T];
@@ -844,13 +871,16 @@ bool classify_tile_supported(int nref, int maxlen) { return nref <= 16384 && max
 hipError_t launch_classify_tile(const uint8_t* bases, const uint32_t* offs, uint32_t nreads, const KsArr& ks, int S,
                                 const RefIndex& ix, int32_t* counter, uint64_t slots, int min_occ, int mode,
                                 int32_t* out4, const DevPolicy& pol, int maxlen, int expect_hits, hipStream_t st,
-                                uint32_t slot_stride, int nmin_cap, const CompactSlots* compact) {
+                                uint32_t slot_stride, int nmin_cap, const CompactSlots* compact, bool dedup) {
     if (nreads == 0) return hipSuccess;
+    if (dedup && mode == 1) return hipErrorInvalidValue; // the count passes count windows under either sketch rule
     const TileKnobs& kn = knobs();
     int win_total = 0; // most windows any read of the batch can have (all k): bounds every per-reference count
     for (int j = 0; j < ks.n; ++j) win_total += num_windows(maxlen, ks.k[j], pol.drop_last_window);
+    int uset = 0;
+    if (dedup) { uset = 64; while (uset < 2 * win_total && uset < DEDUP_MAX_SLOTS) uset <<= 1; }
     TileGeom geo = make_geom(maxlen, mode == 1 ? 0 : ix.nref, mode == 1 ? 0 : expect_hits,
-                             num_windows(maxlen, ks.k[0], pol.drop_last_window), win_total);
+                             num_windows(maxlen, ks.k[0], pol.drop_last_window), win_total, uset);
     if (mode == 1) { geo.qcap = compact ? 48 : 0; geo.dset = 0; } // (compact count: 3 * 64 queued slots of 4 bytes)
     while (tile_lds_bytes(geo) > 20 * 1024 && geo.T > 1) { geo.T -= 1; geo.cap_bytes = geo.T * maxlen; } // >= 8 waves per CU
     const size_t lds = tile_lds_bytes(geo);
@@ -909,6 +939,18 @@ hipError_t launch_classify_tile(const uint8_t* bases, const uint32_t* offs, uint
     RK_LAUNCH_M(RK_TILE_ONLY_K, -1);
     return hipGetLastError();
 #endif
+    if (dedup) { // dedup=distinct: the run-time-k form, any k, either strand rule (no count mode)
+#define RK_LAUNCH_D(CANON)                                                                                           \
+    do {                                                                                                             \
+        if (kmode == 0 && !ix.pre) RK_LAUNCH(0, 0, -1, CANON, true);                                                 \
+        else if (kmode == 0) RK_LAUNCH(0, 3, -1, CANON, true);                                                       \
+        else if (!ix.pre || !pre_masked) RK_LAUNCH(0, 2, -1, CANON, true);                                           \
+        else RK_LAUNCH(0, 4, -1, CANON, true);                                                                       \
+    } while (0)
+        if (pol.canon) RK_LAUNCH_D(true); else RK_LAUNCH_D(false);
+#undef RK_LAUNCH_D
+        return hipGetLastError();
+    }
     if (pol.canon) { RK_LAUNCH_M(0, -1, true); return hipGetLastError(); } // canon=lexmin: the run-time-k form, any k
     // single k of 12, 20 (the reference's other documented settings), 21 or 31: window length known at compile time, runtime fold
     if (ks.n == 1 && ks.k[0] == 12) RK_LAUNCH_M(12, -1);

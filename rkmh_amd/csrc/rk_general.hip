@@ -30,6 +30,8 @@ struct Chunk {
     std::vector<std::vector<uint32_t>> classes = std::vector<std::vector<uint32_t>>(32); // ids by next_pow2(hashes): class cls sorts 64 << cls values
     std::vector<uint32_t> long_seqs; // ids with more hashes than the in-LDS sorter holds
     std::vector<uint32_t> presel;    // ids whose block radix-selects the bottom S before it sorts (filled by the sort step)
+    std::vector<uint32_t> sel_ids;   // dedup=distinct: presel + long_seqs, the sequences a selection runs on, and ...
+    std::vector<DedupSeg> dsegs;     // ... the hash-set region of each of them (filled by the sort step)
     int64_t n() const { return i1 - i0; }
 };
 struct GTick { // RKMH_INDEX_TIMING (stderr: where a general-path batch spends its time)
@@ -161,7 +163,39 @@ static SortArgs sort_args(rk_ctx* c, const GeneralCfg& cfg, const GeneralOut& ou
     a.filter_mode = cfg.filter_mode; a.fmin = cfg.fmin; a.fmax = cfg.fmax;
     if (cfg.classify && out.out4) { a.gcount = gcount; a.gcount_rows = gcount_rows; }
     if (cfg.classify) { a.argmax_n = cfg.argmax_n; a.tail_counts = ntail ? c->w_tail.as<int32_t>() : nullptr; }
+    a.dedup = c->dedup ? 1 : 0;
     return a;
+}
+
+// dedup=distinct, the exact de-duplication pass in front of a selection: the sequences ids[] (u64 segment offsets at w_segoff, ids
+// already at d_ids) keep one copy of every value in w_hashes, the others become 0.  dsegs outlives the upload.  The hash sets live
+// in w_table, at most 2^25 slots (or one sequence's set) per launch.
+static uint64_t dedup_slots(uint64_t n_h) { uint64_t t = 1024; while (t < 2 * n_h) t <<= 1; return t; }
+static int dedup_sequences(rk_ctx* c, const std::vector<uint64_t>& seg, const std::vector<uint32_t>& ids, const uint32_t* d_ids, std::vector<DedupSeg>& dsegs) {
+    const uint64_t BATCH_SLOTS = 1ull << 25;
+    dsegs.resize(ids.size());
+    std::vector<size_t> cut(1, 0); // batches [cut[b], cut[b+1])
+    uint64_t used = 0, most = 0;
+    for (size_t j = 0; j < ids.size(); ++j) {
+        const uint64_t slots = dedup_slots(seg[ids[j] + 1] - seg[ids[j]]);
+        if (j > cut.back() && (used + slots > BATCH_SLOTS || j - cut.back() == 65535)) { cut.push_back(j); used = 0; }
+        dsegs[j] = DedupSeg{used, slots - 1};
+        used += slots;
+        most = std::max(most, used);
+    }
+    cut.push_back(ids.size());
+    RKCHK(c->w_table.reserve(most * 8));
+    RKCHK(c->w_dedup.reserve(ids.size() * sizeof(DedupSeg)));
+    HIPCHK(hipMemcpyAsync(c->w_dedup.p, dsegs.data(), ids.size() * sizeof(DedupSeg), hipMemcpyHostToDevice, c->st));
+    for (size_t b = 0; b + 1 < cut.size(); ++b) {
+        const size_t j0 = cut[b], j1 = cut[b + 1];
+        uint64_t max_n = 0;
+        for (size_t j = j0; j < j1; ++j) max_n = std::max(max_n, seg[ids[j] + 1] - seg[ids[j]]);
+        HIPCHK(hipMemsetAsync(c->w_table.p, 0, (dsegs[j1 - 1].tab_off + dsegs[j1 - 1].tmask + 1) * 8, c->st));
+        HIPCHK(launch_dedup_segments(c->w_hashes.as<uint64_t>(), c->w_segoff.as<uint64_t>(), d_ids + j0, c->w_dedup.as<DedupSeg>() + j0,
+                                     (uint32_t)(j1 - j0), max_n, c->w_table.as<uint64_t>(), c->st));
+    }
+    return RK_OK;
 }
 
 static int reserve_select(rk_ctx* c, int S) { // the scratch of select_then_sort
@@ -190,7 +224,7 @@ static int sort_chunk(rk_ctx* c, const GeneralCfg& cfg, const GeneralOut& out, C
     if (out.lens) RKCHK(c->w_lens.reserve(cn * 4));
     if (out.out4) RKCHK(c->w_out.reserve(cn * 16));
     if (ntail) RKCHK(c->w_tail.reserve(cn * ntail * 4));
-    RKCHK(c->w_ids.reserve(cn * 4));
+    RKCHK(c->w_ids.reserve(cn * 4 * (c->dedup ? 2 : 1)));
     // Sequences with far more hashes than the sketch keeps (long reads, genomes up to a few million k-mers) are not
     // sorted whole: their block radix-selects the bottom S first and sorts only those.
     const uint32_t Psel = next_pow2((uint32_t)S);
@@ -229,6 +263,14 @@ static int sort_chunk(rk_ctx* c, const GeneralCfg& cfg, const GeneralOut& out, C
             else ch.long_seqs[keep++] = li;
         }
         ch.long_seqs.resize(keep);
+    }
+    if (c->dedup && ch.presel.size() + ch.long_seqs.size() > 0) { // (both lists' ids go up once more, behind the launches' own)
+        std::vector<uint32_t>& sel_ids = ch.sel_ids;
+        sel_ids = ch.presel;
+        sel_ids.insert(sel_ids.end(), ch.long_seqs.begin(), ch.long_seqs.end());
+        uint32_t* d_sel = c->w_ids.as<uint32_t>() + cn;
+        HIPCHK(hipMemcpyAsync(d_sel, sel_ids.data(), sel_ids.size() * 4, hipMemcpyHostToDevice, c->st));
+        RKCHK(dedup_sequences(c, ch.seg, sel_ids, d_sel, ch.dsegs));
     }
     if (!ch.presel.empty()) RKCHK(launch(ch.presel, Psel, 1));
     // 3. multi-block select: sequences longer than the LDS sorter, exact bottom-S by radix select first
@@ -365,11 +407,22 @@ static int minhashes_impl(rk_ctx* c, uint64_t* h, int n, int S, uint64_t** mins,
     cfg.S = S; cfg.filt_counter = counter; cfg.filter_mode = filter_mode; cfg.fmin = fmin; cfg.fmax = fmax;
     GeneralOut out; out.sketches = r.get(); out.lens = &len; out.write_back_sorted = sort_input;
     const SortArgs a = sort_args(c, cfg, out, c->w_ids.as<uint32_t>(), 1, next_pow2((uint32_t)(long_input ? S : n)));
-    if (long_input) {
+    if (long_input && c->dedup) {
+        // dedup=distinct: the caller's array comes back sorted with every copy, as always -- so it is sorted and sent back first;
+        // then all but one copy of every value are zeroed and the selection runs on distinct values
+        if (sort_input) {
+            HIPCHK(launch_sort_u64(c->w_hashes.as<uint64_t>(), (uint64_t)n, c->w_misc.p, tmp_bytes, c->st));
+            HIPCHK(hipMemcpyAsync(h, c->w_hashes.p, (size_t)n * 8, hipMemcpyDeviceToHost, c->st));
+        }
+        std::vector<DedupSeg> dsegs;
+        RKCHK(dedup_sequences(c, {0, (uint64_t)n}, {0u}, c->w_ids.as<uint32_t>(), dsegs));
+        RKCHK(select_then_sort(c, cfg, a, c->w_hashes.as<uint64_t>(), (uint64_t)n));
+        HIPCHK(hipStreamSynchronize(c->st)); // dsegs
+    } else if (long_input) {
         RKCHK(select_then_sort(c, cfg, a, c->w_hashes.as<uint64_t>(), (uint64_t)n));
         if (sort_input) HIPCHK(launch_sort_u64(c->w_hashes.as<uint64_t>(), (uint64_t)n, c->w_misc.p, tmp_bytes, c->st));
     } else HIPCHK(launch_sort_intersect(a, nullptr, c->pol, c->st));
-    if (sort_input && n) HIPCHK(hipMemcpyAsync(h, c->w_hashes.p, (size_t)n * 8, hipMemcpyDeviceToHost, c->st));
+    if (sort_input && n && !(long_input && c->dedup)) HIPCHK(hipMemcpyAsync(h, c->w_hashes.p, (size_t)n * 8, hipMemcpyDeviceToHost, c->st));
     HIPCHK(hipMemcpyAsync(r.get(), c->w_sk.p, (size_t)S * 8, hipMemcpyDeviceToHost, c->st));
     HIPCHK(hipMemcpyAsync(&len, c->w_lens.p, 4, hipMemcpyDeviceToHost, c->st));
     HIPCHK(hipStreamSynchronize(c->st));

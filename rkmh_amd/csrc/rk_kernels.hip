@@ -109,7 +109,8 @@ __global__ void k_sort_intersect(SortArgs a, RefIndex ix, int has_ix, DevPolicy 
     int* sh = a.gcount ? a.gcount + (size_t)blockIdx.x * (size_t)ix.nref : lsh;
     int& s_nz = lsh[nl];
     // pre-selection scratch (only when a.preselect): histogram, threshold bucket, a few scalars
-    uint32_t* hist = reinterpret_cast<uint32_t*>(lsh + nl + 4);
+    uint32_t* wsum = reinterpret_cast<uint32_t*>(lsh + nl + 4); // [16] per-wave counts of the distinct compaction (a.dedup)
+    uint32_t* hist = wsum + 16;
     uint64_t* side = reinterpret_cast<uint64_t*>((reinterpret_cast<uintptr_t>(hist + (1 << PRESEL_BITS) + 8 + 1024 + 64) + 7) & ~(uintptr_t)7);
     uint32_t* ps = hist + (1 << PRESEL_BITS);            // [0] taken so far [1] side count [2] bin [3] below [4] bucket count
     uint32_t* csum = ps + 8;                             // [<= 1024] per-thread partial sums, then [64] per-lane sums
@@ -252,9 +253,35 @@ __global__ void k_sort_intersect(SortArgs a, RefIndex ix, int has_ix, DevPolicy 
             if (v[t] == 0 && (t + 1 == n_sort || v[t + 1] != 0)) s_nz = (int)(t + 1);
         __syncthreads();
         const uint32_t nz = (uint32_t)s_nz;
-        const uint32_t m = (n_sort - nz) < (uint32_t)a.S ? (n_sort - nz) : (uint32_t)a.S;
         if (a.write_back)
             for (uint32_t t = tid; t < n; t += T) a.hashes[seg + t] = v[t];
+        uint32_t nkept = n_sort - nz; // non-zero entries that may enter the sketch
+        if (a.dedup) {
+            // dedup=distinct: v[nz + j] = the j-th distinct value, by a prefix count over v[t] != v[t-1], T consecutive entries per
+            // round (ballot within a wave, per-wave counts in LDS).  In place: an entry moves to a position at or below its own, every
+            // entry of a round is read before the round writes, and position t - 1 of the round before can only have been
+            // overwritten by itself.
+            __syncthreads(); // (write_back has read v)
+            const uint32_t wv = (uint32_t)tid >> 6, nwv = ((uint32_t)T + 63u) >> 6;
+            const uint64_t below = (1ull << (tid & 63)) - 1ull;
+            uint32_t base = 0; // distinct values of the rounds before (block-uniform)
+            for (uint32_t r0 = nz; r0 < n_sort; r0 += (uint32_t)T) {
+                const uint32_t t = r0 + (uint32_t)tid;
+                uint64_t x = 0;
+                bool first = false;
+                if (t < n_sort) { x = v[t]; first = t == nz || v[t - 1] != x; }
+                const uint64_t bal = __ballot(first);
+                if ((tid & 63) == 0) wsum[wv] = (uint32_t)__popcll(bal);
+                __syncthreads();
+                uint32_t before = base, tot = 0;
+                for (uint32_t j = 0; j < nwv; ++j) { const uint32_t cw = wsum[j]; before += j < wv ? cw : 0u; tot += cw; }
+                if (first) v[nz + before + (uint32_t)__popcll(bal & below)] = x;
+                base += tot;
+                __syncthreads();
+            }
+            nkept = base;
+        }
+        const uint32_t m = nkept < (uint32_t)a.S ? nkept : (uint32_t)a.S;
         if (a.sketches) {
             uint64_t* sk = a.sketches + (uint64_t)id * (uint64_t)a.S;
             for (uint32_t t = tid; t < (uint32_t)a.S; t += T) sk[t] = t < m ? v[nz + t] : 0ull;
@@ -288,7 +315,7 @@ __global__ void k_sort_intersect(SortArgs a, RefIndex ix, int has_ix, DevPolicy 
     }
 }
 static size_t sort_intersect_lds(uint32_t P, size_t counters, bool preselect) {
-    size_t lds = (size_t)P * 8 + counters * 4 + 16; // sort buffer + counters + s_nz
+    size_t lds = (size_t)P * 8 + counters * 4 + 16 + 64; // sort buffer + counters + s_nz + the compaction's wave counts
     if (preselect) lds += ((size_t)(1 << PRESEL_BITS) + 8 + 1024 + 64) * 4 + (size_t)PRESEL_SIDE * 8 + 16;
     return lds;
 }
@@ -607,6 +634,37 @@ __device__ __forceinline__ void sel_digit(int d, int& shift, int& width) {
     width = d < 4 ? SEL_BITS : 64 - 4 * SEL_BITS;
     shift = d < 4 ? 64 - SEL_BITS * (d + 1) : 0;
 }
+// dedup=distinct in front of the selections: an exact hash set per sequence (open addressing, full 64-bit keys, at most half
+// full); the occurrence that finds its value already there is zeroed.  blockIdx.y = the sequence, blockIdx.x strides over it.
+__global__ __launch_bounds__(256) void k_dedup_segments(uint64_t* __restrict__ h, const uint64_t* __restrict__ seg_off, const uint32_t* __restrict__ ids,
+                                                        const DedupSeg* __restrict__ segs, unsigned long long* table) {
+    const uint32_t id = ids[blockIdx.y];
+    const uint64_t seg = seg_off[id], n = seg_off[id + 1] - seg;
+    const DedupSeg d = segs[blockIdx.y];
+    unsigned long long* tab = table + d.tab_off;
+    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256) {
+        const uint64_t v = h[seg + i];
+        if (v == 0) continue;
+        uint64_t s = ((v * 0x9E3779B97F4A7C15ull) >> 20) & d.tmask;
+        for (;;) { // ends: the table has more slots than the sequence has hashes
+            const unsigned long long old = atomicCAS(&tab[s], 0ull, (unsigned long long)v);
+            if (old == 0ull) break;
+            if (old == v) { h[seg + i] = 0; break; }
+            s = (s + 1) & d.tmask;
+        }
+    }
+}
+hipError_t launch_dedup_segments(uint64_t* hashes, const uint64_t* seg_off, const uint32_t* ids, const DedupSeg* segs, uint32_t nlist,
+                                 uint64_t max_n, uint64_t* table, hipStream_t st) {
+    if (nlist == 0 || max_n == 0) return hipSuccess;
+    if (nlist > 65535u) return hipErrorInvalidValue;
+    uint64_t gx = (max_n + 2047) / 2048; // eight hashes per thread
+    if (gx > 4096) gx = 4096;
+    hipLaunchKernelGGL(k_dedup_segments, dim3((uint32_t)gx, nlist), dim3(256), 0, st, hashes, seg_off, ids, segs,
+                       reinterpret_cast<unsigned long long*>(table));
+    return hipGetLastError();
+}
+
 __global__ __launch_bounds__(256) void k_sel_hist(const uint64_t* __restrict__ h, uint64_t n, const int32_t* counter, uint64_t slots,
                                                   int mode, int fmin, int fmax, DevPolicy pol, const uint32_t* state, uint32_t* hist,
                                                   int d) {

@@ -59,6 +59,9 @@ struct SortArgs {
     // the raw shared counts of the others are written to tail_counts[seq id][nref - argmax_n]
     int32_t argmax_n;
     int32_t* tail_counts;
+    // policy U6 (dedup=distinct): the sketch is the S smallest DISTINCT kept hashes -- the sorted values are compacted before the
+    // truncation to S.  Sequences that are selected from (preselect, sel_hashes) went through launch_dedup_segments first.
+    int32_t dedup;
 };
 // 0 when one block's per-reference counters fit the LDS beside its sort buffer, else the number of global counter rows
 // (= blocks) the caller must provide in SortArgs::gcount
@@ -95,6 +98,13 @@ hipError_t launch_sort_intersect(const SortArgs& a, const RefIndex* ix, const De
 hipError_t launch_select_bottom(const uint64_t* hashes, uint64_t n, int S, const int32_t* counter, uint64_t slots,
                                 int filter_mode, int fmin, int fmax, const DevPolicy& pol, uint32_t* sel_state,
                                 uint32_t* hist, uint64_t* sel_out, hipStream_t st);
+// dedup=distinct in front of a bottom-S SELECTION (block pre-select, multi-block select): every non-first occurrence of a value
+// within a sequence becomes 0, the dropped sentinel, so the selection's histograms count distinct values.  Exact: sequence
+// ids[j] is given tmask + 1 (a power of two >= twice its hashes) u64 slots of `table` from segs[j].tab_off on, which the caller
+// has zeroed; max_n = the longest of the nlist (<= 65535) sequences.  Which copy of a value stays is not defined.
+struct DedupSeg { uint64_t tab_off, tmask; };
+hipError_t launch_dedup_segments(uint64_t* hashes, const uint64_t* seg_off, const uint32_t* ids, const DedupSeg* segs, uint32_t nlist,
+                                 uint64_t max_n, uint64_t* table, hipStream_t st);
 // ---- FASTQ text indexed on the device (rk_fastq.hip) ----
 enum { FQ_BAD_CR = 1, FQ_BAD_LINES = 2, FQ_BAD_RECORD = 4, FQ_BAD_CHAR = 8, FQ_BAD_CAP = 16 }; // status bits: any of them = parse this block on the host
 struct FqDev {
@@ -210,7 +220,8 @@ constexpr int KPRE_MIN_K = 8; // the k-mer-space kernel (rk_kmer.hip) exists for
 hipError_t launch_classify_tile(const uint8_t* bases, const uint32_t* offs, uint32_t nreads, const KsArr& ks, int S,
                                 const RefIndex& ix, int32_t* counter, uint64_t slots, int min_occ, int mode,
                                 int32_t* out4, const DevPolicy& pol, int maxlen, int expect_hits, hipStream_t st,
-                                uint32_t slot_stride = 0, int nmin_cap = 0x7fffffff, const CompactSlots* compact = nullptr);
+                                uint32_t slot_stride = 0, int nmin_cap = 0x7fffffff, const CompactSlots* compact = nullptr,
+                                bool dedup = false); // dedup (policy U6, classify modes): row field 3 counts DISTINCT non-zero hashes
 // the k-mer-space kernel (rk_kmer.hip): plain classification with k-mer sizes from KPRE_MIN_K to 16 whose exact k-mer maps and group
 // filters were built (KmerSets: one per size; a single size runs the compile-time-k kernels, several the run-time-k one)
 bool classify_kmer_supported(int nref, int maxlen, int k);

@@ -40,7 +40,9 @@ int fused_device(rk_ctx* c, const void* d_bases, const void* d_offs, int64_t nre
     if (nreads > 0xfffffff0ll) return fail(RK_ERR_LIMIT, "more than 2^32-16 reads in one device batch");
     if (((uintptr_t)d_bases & 3) != 0) return fail(RK_ERR_ARG, "d_bases must be 4-byte aligned");
     int32_t* counter = nullptr; uint64_t slots = 1; int min_occ = 0;
-    const bool bounded = mode != 1 && c->depth && c->min_num_bound >= 0; // the mask acts per key: no slot bitmap in the kernels
+    // the mask acts per key: no slot bitmap in the kernels.  (dedup=distinct with a bound above 0 takes the exact per-window form: the
+    // probe that counts a read's first `bound` surviving windows would count repeated values)
+    const bool bounded = mode != 1 && c->depth && c->min_num_bound >= 0 && !(c->dedup && c->min_num_bound > 0);
     if (bounded && !c->ix.keepkey) return fail(RK_ERR_STATE, "depth filter: the per-key mask was not built");
     if (mode == 1) { counter = count_into->d; slots = count_into->slots; }
     else if (c->depth && !bounded) { counter = c->d_keepbits.as<int32_t>(); slots = c->depth->slots; min_occ = c->min_occ; } // the keep bitmap, see rk_set_depth_filter
@@ -91,7 +93,7 @@ int fused_device(rk_ctx* c, const void* d_bases, const void* d_offs, int64_t nre
         if (c->ksets_m.n >= 1) ix.km1 = c->ksets_m.km1[0]; // (the compile-time-k kernels read the first size's structures from ix)
         ix.kv = c->d_kvm.as<uint4>();                       // (hash-space kernels: the key array with the mask's verdict in it)
     }
-    const int nmin_cap = bounded ? c->min_num_bound : 0x7fffffff;
+    const int nmin_cap = (mode != 1 && c->depth && c->min_num_bound >= 0) ? c->min_num_bound : 0x7fffffff;
     // classification with k-mer sizes the exact k-mer maps were enumerated for: the k-mer-space kernel (rk_kmer.hip); under a
     // bounded depth filter it reads the masked copies of the maps (a dropped key is a zero-hash k-mer there)
     if (!counter && c->ksets.n == c->ks.n && c->ksets.n >= 1 && (!bounded || c->ksets_m.n == c->ksets.n) &&
@@ -100,7 +102,7 @@ int fused_device(rk_ctx* c, const void* d_bases, const void* d_offs, int64_t nre
                                     (int32_t*)d_out4, c->pol, (int)ml, expect, st, nmin_cap));
     else if (classify_tile_supported(c->ix.nref, (int)ml))
         HIPCHK(launch_classify_tile((const uint8_t*)d_bases, (const uint32_t*)d_offs, (uint32_t)nreads, c->ks, c->S, ix,
-                                    counter, slots, min_occ, 0, (int32_t*)d_out4, c->pol, (int)ml, expect, st, 0, nmin_cap));
+                                    counter, slots, min_occ, 0, (int32_t*)d_out4, c->pol, (int)ml, expect, st, 0, nmin_cap, nullptr, c->dedup));
     else
         HIPCHK(launch_fill_reroute((int32_t*)d_out4, (uint32_t)nreads, st)); // e.g. more than 16384 references: general path
     // bound > 0: the first `bound` surviving windows of every answered read are counted by hashing them (k_min_num_probe)

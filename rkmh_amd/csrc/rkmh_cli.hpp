@@ -51,11 +51,12 @@ void policy_apply(const char* spec, const char* from);
 std::string policy_text(const rk_policy& p);
 #define HASH_POLICY_OPTION {"hash-policy", required_argument, 0, 1004}
 #define HASH_POLICY_HELP \
-    "  --hash-policy <spec>    the mkmh choices the reference's tree does not fix, as presets (default, mash) and/or key=value:\n" \
+    "  --hash-policy <spec>    the mkmh choices the reference's tree does not fix, as presets (default, mash, sourmash) and/or key=value:\n" \
     "                          fold=swap32|h1|w2w1, windows=len-k|len-k+1, zero=count|skip, mask=lt|le, freqmax=incl|excl,\n" \
-    "                          canon=minhash|lexmin, seed=<n>;  `mash` = fold=h1,windows=len-k+1,seed=42 (the smaller of both strand\n" \
-    "                          hashes is kept);  canon=lexmin hashes only the strand that is the smaller string, the strand rule of\n" \
-    "                          Mash and sourmash (their sketches also drop repeated values: not done here).  RKMH_POLICY: the same, read first\n"
+    "                          canon=minhash|lexmin, dedup=multiset|distinct, seed=<n>;  `mash` = fold=h1,windows=len-k+1,seed=42 (the\n" \
+    "                          smaller of both strand hashes is kept, repeated values stay);  canon=lexmin hashes only the strand that\n" \
+    "                          is the smaller string, dedup=distinct sketches distinct values: the rules of Mash and sourmash;\n" \
+    "                          `sourmash` = mash,canon=lexmin,dedup=distinct.  RKMH_POLICY: the same, read first\n"
 void print_help();
 struct LoadedSketches { std::vector<std::string> names; std::vector<uint64_t> sk; std::vector<int32_t> lens; std::vector<int> ks; int S = 0; std::string policy; };
 bool load_sketch_json(const char* path, LoadedSketches& L);

@@ -8,7 +8,7 @@
 #include "rkmh_cli.hpp"
 
 // The hashing policy of this run: the build's defaults, then RKMH_POLICY, then --hash-policy (rk_policy_parse: presets `default`
-// and `mash`, or fold= / windows= / zero= / mask= / freqmax= / canon= / seed=).  The arithmetic behind these switches is mkmh's, which the
+// `mash` and `sourmash`, or fold= / windows= / zero= / mask= / freqmax= / canon= / dedup= / seed=).  The arithmetic behind these switches is mkmh's, which the
 // reference's tree does not hold (src/rkmh.cpp:17); every context of the process is created with g_policy.
 rk_policy g_policy;
 void policy_apply(const char* spec, const char* from) {

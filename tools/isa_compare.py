@@ -15,8 +15,8 @@ import os, re, sys
 
 
 def base_name(name):
-    """a kernel that gained a trailing, defaulted `bool = false` template parameter is still the kernel it was"""
-    return re.sub(r"Lb0E(?=EEv)", "", name)
+    """a kernel that gained trailing, defaulted `bool = false` template parameters is still the kernel it was"""
+    return re.sub(r"(?:Lb0E)+(?=EEv)", "", name)
 
 
 def kernels(path):
