@@ -581,6 +581,33 @@ int64_t rk_packed_filter_records(const rk_fastq_result* res, const rk_packed_blo
  * their first launch -- tens of milliseconds a caller can spend on a second thread while its references are sketched.  Optional. */
 int rk_warm_up(int device, int with_inflate);
 
+/* ------------------------------------------------------------------------------------------------
+ * SKETCH COMPARISON (`rkmh dist`; what `mash dist` and `sourmash compare` answer -- the reference compares sketches one pair at a
+ * time, src/rkmh.cpp:869).  A sketch is a row of rk_sketch_batch: sketch_size uint64, ascending, the first len of them non-zero,
+ * zeros behind.  Values may repeat (dedup=multiset) or not (dedup=distinct); D(x) = the distinct values of x[0, len).  Zeros are
+ * padding, never values.  Every pair (row i of a, row j of b) gives four int32 at out4[(i * nb + j) * 4]:
+ *   0 shared           sum over values of min(multiplicity in a, multiplicity in b) = rk_hash_intersection_size of the two rows
+ *   1 shared_distinct  |D(a) & D(b)|
+ *   2 common           |U & D(a) & D(b)|, U = the min(sketch_size, |D(a) | D(b)|) smallest values of D(a) | D(b): Mash's numerator
+ *   3 denom            |U|
+ * One launch of k_sketch_pairs (rk_pairs.hip): a tile of pairs per workgroup, a lane per pair walking a two-pointer merge.  Rows
+ * that are not ascending give meaningless counts and nothing worse.
+ * rk_compare_sketches: host arrays; RK_ERR_ARG for a sketch_size outside [1, RK_MAX_SKETCH], na or nb below 1, a length outside
+ * [0, sketch_size], NULL.  a and b (and their lengths) may be the same arrays: uploaded once.  The answer is computed in row blocks.
+ * rk_compare_sketches_device: device arrays the caller sized (d_out4: na * nb * 16 bytes), asynchronous on hip_stream (NULL = HIP's
+ * null stream; rk_ctx_stream() = the context's own, as for rk_classify_batch_device); lengths outside [0, sketch_size] are clamped
+ * on the device. */
+int rk_compare_sketches(rk_ctx* ctx, const uint64_t* a, const int32_t* alens, int na, const uint64_t* b, const int32_t* blens, int nb,
+                        int sketch_size, int32_t* out4);
+int rk_compare_sketches_device(rk_ctx* ctx, const void* d_a, const void* d_alens, int na, const void* d_b, const void* d_blens, int nb,
+                               int sketch_size, void* d_out4, void* hip_stream);
+/* Host code, usable without a GPU (rk_pairs_host.cpp).  rk_merge_sketches: the sketch_size smallest values of the union of n
+ * sketches -> out[sketch_size] (zero padded), *out_len; distinct = 0 keeps repeats, 1 keeps each value once.  Exact: the bottom of
+ * a union only ever needs the bottom of each part.  rk_mash_distance: j = common / denom (0 when denom = 0); the distance is 1 when
+ * common = 0, else -ln(2j / (1 + j)) / k clamped to [0, 1]; RK_ERR_ARG for negative counts, common > denom or k < 1. */
+int rk_merge_sketches(const uint64_t* sketches, const int32_t* lens, int n, int sketch_size, int distinct, uint64_t* out, int32_t* out_len);
+int rk_mash_distance(int common, int denom, int k, double* jaccard, double* distance);
+
 #ifdef __cplusplus
 }
 #endif

@@ -221,6 +221,10 @@ _SIGS = {
     "rk_fastq_slot_count": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     "rk_fastq_cut": (C.c_int64, [C.c_void_p, C.c_uint64]),
     "rk_synth_reads": (C.c_int, [_u8p, _u64p, C.c_int, C.c_uint64, C.c_uint64, C.c_int, C.c_uint64, _u8p, C.c_int]),
+    "rk_compare_sketches": (C.c_int, [C.c_void_p, _u64p, _i32p, C.c_int, _u64p, _i32p, C.c_int, C.c_int, _i32p]),
+    "rk_compare_sketches_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "rk_merge_sketches": (C.c_int, [_u64p, _i32p, C.c_int, C.c_int, C.c_int, _u64p, _i32p]),
+    "rk_mash_distance": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
 }
 
 
@@ -877,6 +881,30 @@ def describe_policy(p):
     return buf.value.decode()
 
 
+def merge_sketches(sketches, lens, sketch_size=None, distinct=False):
+    """rk_merge_sketches (host code, no GPU): the bottom sketch_size of the union of the rows of `sketches` (uint64 [n, sketch_size],
+    the first lens[i] of row i are its values) -> (uint64 [sketch_size] zero padded, length).  distinct: each value once."""
+    sketches = np.ascontiguousarray(sketches, dtype=np.uint64)
+    lens = np.ascontiguousarray(lens, dtype=np.int32)
+    if sketch_size is None:
+        sketch_size = sketches.shape[1]
+    n = len(lens)
+    if sketches.size != n * sketch_size:
+        raise ValueError("sketches must hold len(lens) rows of sketch_size values")
+    out = np.zeros(max(sketch_size, 1), dtype=np.uint64)
+    m = C.c_int32()
+    _chk(load_library().rk_merge_sketches(_p(sketches, C.c_uint64), _p(lens, C.c_int32), n, sketch_size, 1 if distinct else 0,
+                                          _p(out, C.c_uint64), C.byref(m)))
+    return out[:sketch_size], int(m.value)
+
+
+def mash_distance(common, denom, k):
+    """rk_mash_distance (host code, no GPU): (jaccard, distance) from fields 2 and 3 of a compare_sketches row."""
+    j, d = C.c_double(), C.c_double()
+    _chk(load_library().rk_mash_distance(int(common), int(denom), int(k), C.byref(j), C.byref(d)))
+    return j.value, d.value
+
+
 class Context:
     """One GPU. Methods are named after the reference's functions they replace."""
 
@@ -969,6 +997,35 @@ class Context:
         r = np.ctypeslib.as_array(out, shape=(max(n.value, 1),))[: n.value].copy()
         self._lib.rk_free(out)
         return r
+
+    # ---- sketch comparison ---------------------------------------------------------------------
+    def compare_sketches(self, a, alens, b=None, blens=None, sketch_size=None):
+        """rk_compare_sketches: every row of `a` (uint64 [na, sketch_size], lengths alens) against every row of `b` (None: of `a`
+        itself) -> int32 [na, nb, 4] = (shared, shared_distinct, common, denom) per pair."""
+        a = np.ascontiguousarray(a, dtype=np.uint64)
+        alens = np.ascontiguousarray(alens, dtype=np.int32)
+        if sketch_size is None:
+            sketch_size = a.shape[1]
+        if b is None:
+            b, blens = a, alens
+        else:
+            b = np.ascontiguousarray(b, dtype=np.uint64)
+            blens = np.ascontiguousarray(blens, dtype=np.int32)
+        na, nb = len(alens), len(blens)
+        if a.size != na * sketch_size or b.size != nb * sketch_size:
+            raise ValueError("sketch arrays must hold len(lens) rows of sketch_size values")
+        out = np.zeros((na, nb, 4), dtype=np.int32)
+        _chk(self._lib.rk_compare_sketches(self._h, _p(a, C.c_uint64), _p(alens, C.c_int32), na, _p(b, C.c_uint64), _p(blens, C.c_int32), nb,
+                                           sketch_size, _p(out, C.c_int32)))
+        return out
+
+    def compare_sketches_device(self, d_a_ptr, d_alens_ptr, na, d_b_ptr, d_blens_ptr, nb, sketch_size, d_out_ptr, stream=None):
+        """Resident arrays (raw device pointers; d_out: na * nb * 4 int32); asynchronous.  stream: a hipStream_t handle (e.g.
+        torch.cuda.current_stream().cuda_stream; 0 = null stream); None = the context's own stream, as for classify_device."""
+        if stream is None:
+            stream = self.stream
+        _chk(self._lib.rk_compare_sketches_device(self._h, C.c_void_p(d_a_ptr), C.c_void_p(d_alens_ptr), na, C.c_void_p(d_b_ptr),
+                                                  C.c_void_p(d_blens_ptr), nb, sketch_size, C.c_void_p(d_out_ptr), C.c_void_p(stream)))
 
     # ---- outer boundary (batches) ------------------------------------------------------------
     def hash_batch(self, bases, offsets, ks):

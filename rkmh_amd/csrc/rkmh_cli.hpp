@@ -8,7 +8,7 @@
 //   rkmh_packed.cpp     reads written by `rkmh pack` (-F)
 //   rkmh_refs.cpp       the -r files through the device
 //   rkmh_classify.cpp   stream / classify and filter: one driver, two thin commands
-//   rkmh_commands.cpp   call, sketch (and the JSON sketches stream -R reads), hash, hpv16, pack; the hashing policy and help text
+//   rkmh_commands.cpp   call, sketch (and the JSON sketches stream -R reads), dist, hash, hpv16, pack; the hashing policy and help text
 #pragma once
 #include <getopt.h>
 #include <sys/types.h>
@@ -59,13 +59,14 @@ std::string policy_text(const rk_policy& p);
     "                          `sourmash` = mash,canon=lexmin,dedup=distinct.  RKMH_POLICY: the same, read first\n"
 void print_help();
 struct LoadedSketches { std::vector<std::string> names; std::vector<uint64_t> sk; std::vector<int32_t> lens; std::vector<int> ks; int S = 0; std::string policy; };
-bool load_sketch_json(const char* path, LoadedSketches& L);
+bool load_sketch_json(const char* path, LoadedSketches& L, int max_S = 0); // max_S > 0: a larger "length" is refused before anything of that size is allocated
 
 // ---- the sub-commands
 int main_stream(int argc, char** argv);
 int main_filter(int argc, char** argv);
 int main_call(int argc, char** argv);
 int main_sketch(int argc, char** argv);
+int main_dist(int argc, char** argv);
 int main_hash(int argc, char** argv);
 int main_hpv16(int argc, char** argv);
 int main_pack(int argc, char** argv);

@@ -1,5 +1,5 @@
 // rkmh_commands.cpp -- the sub-commands of `rkmh` beside stream / filter: pack, call, sketch (and the JSON sketches stream -R reads),
-// hash and hpv16; the hashing policy of the run and the help text they share.
+// dist, hash and hpv16; the hashing policy of the run and the help text they share.
 #include <unistd.h>
 
 #include <algorithm>
@@ -30,6 +30,7 @@ void print_help() {
             "  hash                print the k-mer hashes of every sequence\n"
             "  hpv16               HPV type and HPV16 lineage / sublineage k-mer matches of every read\n"
             "  sketch              write MinHash sketches as JSON (load them with stream -R)\n"
+            "  dist                Mash distance between every query sketch and every reference sketch\n"
             "  pack                write reads as a packed file (2 bits per base + names): stream|filter -F <file> classifies it without parsing\n"
             "Run a command without options for its help text.\n");
 }
@@ -263,12 +264,49 @@ static void json_escape(std::string& out, const char* s) {
 }
 static void help_sketch() {
     fprintf(stderr,
-            "rkmh sketch -f <seqs.fa|fq> [-k <k>]... [-s <sketch>] [-o <out.json>] [--kmer-cache <file>]\n"
+            "rkmh sketch -f <seqs.fa|fq> [-k <k>]... [-s <sketch>] [-g] [-o <out.json>] [--kmer-cache <file>]\n"
             "  writes a JSON array with one MinHash sketch per sequence (schema of the reference's dump_hash_json);\n"
+            "  -g: one sketch per input FILE (named by its path; no k-mer spans two of its records), as Mash sketches an assembly;\n"
             "  `rkmh stream -R <out.json>` loads it instead of sketching references again;\n"
             "  --kmer-cache <file>: also enumerates the k-mers behind these sketches (k 8 .. 18) into <file>, which\n"
             "  `rkmh stream -R <out.json> --kmer-cache <file>` then loads instead of enumerating them at every start\n"
             "  the file records the hashing policy (\"hashPolicy\"); stream -R refuses sketches hashed under another one\n" HASH_POLICY_HELP);
+}
+// The sketches `sketch` writes and `dist` compares, one per sequence of the files -- or, whole_files (-g), one per FILE: the records
+// of a file are sketched one by one (no window spans two contigs) and reduced to the bottom S of their union under the policy's dedup
+// rule (rk_merge_sketches); such a sketch is named by the path as given and its seqLen is the sum of the record lengths.
+struct SketchSet { std::vector<std::string> names; std::vector<uint64_t> seq_len; std::vector<uint64_t> sk; std::vector<int32_t> lens; };
+static void sketch_files(rk_ctx* ctx, const std::vector<const char*>& files, const std::vector<int>& ks, int S, bool whole_files, SketchSet& out) {
+    auto sketch_records = [&](const rk_seqset& s, std::vector<uint64_t>& sk, std::vector<int32_t>& lens) {
+        sk.assign((size_t)s.nseq * (size_t)S, 0);
+        lens.assign((size_t)s.nseq, 0);
+        CK(rk_sketch_batch(ctx, s.bases, s.offsets, s.nseq, ks.data(), (int)ks.size(), S, sk.data(), lens.data()));
+    };
+    if (!whole_files) {
+        rk_seqset s;
+        CK(rk_parse_files(files.data(), (int)files.size(), &s));
+        sketch_records(s, out.sk, out.lens);
+        for (int64_t i = 0; i < s.nseq; ++i) {
+            out.names.push_back(s.names + s.name_offsets[i]);
+            out.seq_len.push_back(s.offsets[i + 1] - s.offsets[i]);
+        }
+        rk_seqset_free(&s);
+        return;
+    }
+    out.sk.assign(files.size() * (size_t)S, 0);
+    out.lens.assign(files.size(), 0);
+    std::vector<uint64_t> sk;
+    std::vector<int32_t> lens;
+    for (size_t f = 0; f < files.size(); ++f) {
+        rk_seqset s;
+        CK(rk_parse_files(&files[f], 1, &s));
+        if (s.nseq > 0x7fffffffll) { fprintf(stderr, "rkmh: %s holds more than 2^31-1 records\n", files[f]); exit(1); }
+        sketch_records(s, sk, lens);
+        CK(rk_merge_sketches(sk.data(), lens.data(), (int)s.nseq, S, rk_policy_dedup(&g_policy), &out.sk[f * (size_t)S], &out.lens[f]));
+        out.names.push_back(files[f]);
+        out.seq_len.push_back(s.nseq ? s.offsets[s.nseq] - s.offsets[0] : 0);
+        rk_seqset_free(&s);
+    }
 }
 int main_sketch(int argc, char** argv) {
     std::vector<const char*> files;
@@ -276,16 +314,19 @@ int main_sketch(int argc, char** argv) {
     int S = 1000, device = 0;
     const char* outp = nullptr;
     const char* kmer_cache = nullptr;
+    bool whole_files = false;
     if (argc <= 2) { help_sketch(); exit(1); }
     optind = 2;
     int c;
     static struct option long_options[] = {{"help", no_argument, 0, 'h'}, {"kmer", required_argument, 0, 'k'},
         {"fasta", required_argument, 0, 'f'}, {"reference", required_argument, 0, 'r'}, {"sketch-size", required_argument, 0, 's'},
-        {"output", required_argument, 0, 'o'}, {"device", required_argument, 0, 1000}, {"kmer-cache", required_argument, 0, 1003}, HASH_POLICY_OPTION, {0, 0, 0, 0}};
-    while ((c = getopt_long(argc, argv, "hk:f:r:s:o:t:", long_options, nullptr)) != -1) {
+        {"output", required_argument, 0, 'o'}, {"device", required_argument, 0, 1000}, {"kmer-cache", required_argument, 0, 1003},
+        {"whole-files", no_argument, 0, 'g'}, HASH_POLICY_OPTION, {0, 0, 0, 0}};
+    while ((c = getopt_long(argc, argv, "hgk:f:r:s:o:t:", long_options, nullptr)) != -1) {
         switch (c) {
             case 1004: policy_apply(optarg, "--hash-policy"); break;
             case 1003: kmer_cache = optarg; break;
+            case 'g': whole_files = true; break;
             case 'f': case 'r': files.push_back(optarg); break;
             case 'k': ks.push_back(atoi(optarg)); break;
             case 's': S = atoi(optarg); break;
@@ -297,18 +338,19 @@ int main_sketch(int argc, char** argv) {
     }
     if (ks.empty()) { fprintf(stderr, "No kmer size(s) provided. Will use a default kmer size of 16.\n"); ks.push_back(16); }
     if (files.empty()) { fprintf(stderr, "rkmh: -f <file> is required\n"); exit(1); }
+    if (whole_files && (S < 1 || S > RK_MAX_SKETCH)) { fprintf(stderr, "rkmh sketch: -g needs a sketch size of 1 .. %d\n", RK_MAX_SKETCH); exit(1); }
     rk_ctx* ctx = nullptr;
     CK(rk_ctx_create(device, &g_policy, &ctx));
-    rk_seqset s;
-    CK(rk_parse_files(files.data(), (int)files.size(), &s));
-    std::vector<uint64_t> sk((size_t)s.nseq * (size_t)S);
-    std::vector<int32_t> lens((size_t)s.nseq);
-    CK(rk_sketch_batch(ctx, s.bases, s.offsets, s.nseq, ks.data(), (int)ks.size(), S, sk.data(), lens.data()));
+    SketchSet set;
+    sketch_files(ctx, files, ks, S, whole_files, set);
+    const std::vector<uint64_t>& sk = set.sk;
+    const std::vector<int32_t>& lens = set.lens;
+    const int64_t nsk = (int64_t)set.names.size();
     if (kmer_cache && *kmer_cache) {
         // the index of these sketches is built once here, for its k-mer enumeration: the file's tag hashes the index keys, k and the
         // hashing policy, so a later `stream -R <these sketches> --kmer-cache <file>` finds it -- and anything else does not use it
         CK(rk_set_kmer_cache(ctx, kmer_cache));
-        CK(rk_set_reference_sketches(ctx, sk.data(), lens.data(), (int)s.nseq, ks.data(), (int)ks.size(), S));
+        CK(rk_set_reference_sketches(ctx, sk.data(), lens.data(), (int)nsk, ks.data(), (int)ks.size(), S));
         if (rk_kmer_cache_state(ctx) == 0) fprintf(stderr, "rkmh: no k-mer enumeration for these sketches (k-mer sizes outside 8 .. 18, or a hash with two k-mers): %s not written\n", kmer_cache);
     }
     FILE* fo = outp ? fopen(outp, "w") : stdout;
@@ -319,13 +361,13 @@ int main_sketch(int argc, char** argv) {
     char num[32];
     // "hashPolicy": this build's addition to dump_hash_json's keys (src/rkmh.cpp:489-525) -- what hashType / hashSeed leave open
     const std::string pol_text = policy_text(g_policy);
-    for (int64_t i = 0; i < s.nseq; ++i) {
+    for (int64_t i = 0; i < nsk; ++i) {
         std::string name;
-        json_escape(name, s.names + s.name_offsets[i]);
+        json_escape(name, set.names[(size_t)i].c_str());
         if (i) o += ',';
         o += "{\"alphabet\":\"ATGC\",\"canonical\":\"true\",\"hashBits\":64,\"hashPolicy\":\"" + pol_text + "\",\"hashSeed\":" + std::to_string(g_policy.seed) +
              ",\"hashType\":\"MurmurHash3_x64_128\",\"kmer\":\"" + kstr +
-             "\",\"name\":\"" + name + "\",\"preserveCase\":\"false\",\"seqLen\":" + std::to_string(s.offsets[i + 1] - s.offsets[i]) +
+             "\",\"name\":\"" + name + "\",\"preserveCase\":\"false\",\"seqLen\":" + std::to_string(set.seq_len[(size_t)i]) +
              ",\"sketches\":{\"comment\":\"\",\"hashes\":[";
         for (int j = 0; j < lens[(size_t)i]; ++j) {
             int n = snprintf(num, sizeof num, j ? ",%llu" : "%llu", (unsigned long long)sk[(size_t)i * S + j]);
@@ -337,7 +379,6 @@ int main_sketch(int argc, char** argv) {
     o += "]\n";
     fwrite(o.data(), 1, o.size(), fo);
     if (fo != stdout) fclose(fo);
-    rk_seqset_free(&s);
     rk_ctx_destroy(ctx);
     return 0;
 }
@@ -362,7 +403,7 @@ static std::string json_string_at(const std::string& t, size_t p) {
     }
     return r;
 }
-bool load_sketch_json(const char* path, LoadedSketches& L) {
+bool load_sketch_json(const char* path, LoadedSketches& L, int max_S) {
     FILE* f = fopen(path, "rb");
     if (!f) return false;
     std::string t;
@@ -410,6 +451,7 @@ bool load_sketch_json(const char* path, LoadedSketches& L) {
         pos = end;
     }
     if (all.empty() || L.S <= 0) return false;
+    if (max_S > 0 && L.S > max_S) return false; // (before the rows are allocated: L.S tells the caller why)
     L.sk.assign(all.size() * (size_t)L.S, 0);
     for (size_t i = 0; i < all.size(); ++i) {
         if ((int)all[i].size() > L.S) return false;
@@ -417,6 +459,118 @@ bool load_sketch_json(const char* path, LoadedSketches& L) {
         for (size_t j = 0; j < all[i].size(); ++j) L.sk[i * (size_t)L.S + j] = all[i][j];
     }
     return true;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------
+// dist: the Mash distance of every (query, reference) pair of sketches -- `mash dist`, which the reference has no command for.  The
+// four counts of a pair come from one launch over all pairs (rk_compare_sketches); the floating point is rk_mash_distance's.
+// Everything that can be refused is refused before a context exists: nothing is printed by a run that fails.
+static void help_dist() {
+    fprintf(stderr,
+            "rkmh dist (-r <refs.fa> ... | -R <refs.json>) [-f <queries.fa|fq> ... | -Q <queries.json>] [-k <k>] [-s <sketch>] [-g] [-d <maxdist>]\n"
+            "  prints one line per (query, reference) pair, query by query: reference, query, Mash distance, common/denom of the merged\n"
+            "  bottom-s sketch, shared hashes (the multiset intersection `stream` counts); without -f / -Q every reference is compared\n"
+            "  with every reference\n"
+            "  -R / -Q: sketches written by `rkmh sketch` (their k-mer size, sketch size and hashing policy must agree with each other and the run)\n"
+            "  -g: one sketch per input FILE, as Mash sketches an assembly;  -d <x>: only pairs at distance <= x;  --device <id>: GPU to use\n" HASH_POLICY_HELP);
+}
+int main_dist(int argc, char** argv) {
+    std::vector<const char*> ref_files, query_files, ref_json, query_json;
+    std::vector<int> ks;
+    int S = 0, device = 0;
+    bool whole_files = false;
+    double max_dist = 2.0;
+    if (argc <= 2) { help_dist(); exit(1); }
+    static struct option long_options[] = {{"help", no_argument, 0, 'h'}, {"kmer", required_argument, 0, 'k'}, {"fasta", required_argument, 0, 'f'},
+        {"reference", required_argument, 0, 'r'}, {"pre-references", required_argument, 0, 'R'}, {"pre-queries", required_argument, 0, 'Q'},
+        {"sketch-size", required_argument, 0, 's'}, {"whole-files", no_argument, 0, 'g'}, {"max-dist", required_argument, 0, 'd'},
+        {"threads", required_argument, 0, 't'}, {"device", required_argument, 0, 1000}, HASH_POLICY_OPTION, {0, 0, 0, 0}};
+    optind = 2;
+    int c;
+    while ((c = getopt_long(argc, argv, "hgk:f:r:R:Q:s:d:t:", long_options, nullptr)) != -1) {
+        switch (c) {
+            case 1004: policy_apply(optarg, "--hash-policy"); break;
+            case 'r': ref_files.push_back(optarg); break;
+            case 'f': query_files.push_back(optarg); break;
+            case 'R': ref_json.push_back(optarg); break;
+            case 'Q': query_json.push_back(optarg); break;
+            case 'k': ks.push_back(atoi(optarg)); break;
+            case 's': S = atoi(optarg); if (S < 1) S = -1; break;
+            case 'g': whole_files = true; break;
+            case 'd': max_dist = atof(optarg); break;
+            case 't': break;
+            case 1000: device = atoi(optarg); break;
+            default: help_dist(); exit(1);
+        }
+    }
+    auto refuse = [](const std::string& why) { fprintf(stderr, "rkmh dist: %s\n", why.c_str()); exit(1); };
+    if (ks.size() > 1) {
+        std::string given;
+        for (int k : ks) given += " " + std::to_string(k);
+        refuse("a distance needs one k-mer size; sizes provided:" + given);
+    }
+    if (S != 0 && (S < 1 || S > RK_MAX_SKETCH)) refuse("sketch size outside 1 .. " + std::to_string(RK_MAX_SKETCH));
+    if (ref_files.empty() == ref_json.empty()) refuse("references come from -r <fasta> ... or from -R <sketches.json> ..., one of the two");
+    if (!query_files.empty() && !query_json.empty()) refuse("queries come from -f <fasta|fastq> ... or from -Q <sketches.json> ..., not both");
+    if (whole_files && ref_files.empty() && query_files.empty()) refuse("-g says how -r / -f files are sketched; sketches loaded with -R / -Q are what they are");
+    const bool self = query_files.empty() && query_json.empty();
+    // sketch files: each agrees in itself (load_sketch_json), with the others, with -k / -s where given, and with the run's policy
+    int k = ks.empty() ? 0 : ks[0];
+    auto load = [&](const std::vector<const char*>& paths, SketchSet& into) {
+        for (const char* path : paths) {
+            LoadedSketches L;
+            if (!load_sketch_json(path, L, RK_MAX_SKETCH)) {
+                if (L.S > RK_MAX_SKETCH) refuse(std::string(path) + ": sketch size outside 1 .. " + std::to_string(RK_MAX_SKETCH));
+                refuse(std::string("cannot load sketches from ") + path + " (unreadable, or its sketches disagree in kmer, hashPolicy or length)");
+            }
+            rk_policy theirs;
+            rk_default_policy(&theirs);
+            if (rk_policy_parse(L.policy.c_str(), &theirs) != RK_OK) refuse(std::string(path) + ": " + rk_last_error());
+            if (!rk_policy_same_hashes(&theirs, &g_policy))
+                refuse(std::string(path) + " holds sketches hashed with " + policy_text(theirs) + ", this run hashes with " + policy_text(g_policy) + ": pass --hash-policy " + policy_text(theirs));
+            if (L.ks.size() != 1) refuse(std::string(path) + " holds sketches of " + std::to_string(L.ks.size()) + " k-mer sizes; a distance needs one");
+            if (k != 0 && L.ks[0] != k) refuse(std::string(path) + " holds sketches of k = " + std::to_string(L.ks[0]) + ", the others (or -k) say " + std::to_string(k));
+            if (S != 0 && L.S != S) refuse(std::string(path) + " holds sketches of size " + std::to_string(L.S) + ", the others (or -s) say " + std::to_string(S));
+            k = L.ks[0]; S = L.S;
+            into.names.insert(into.names.end(), L.names.begin(), L.names.end());
+            into.sk.insert(into.sk.end(), L.sk.begin(), L.sk.end());
+            into.lens.insert(into.lens.end(), L.lens.begin(), L.lens.end());
+        }
+    };
+    SketchSet refs, queries;
+    load(ref_json, refs);
+    load(query_json, queries);
+    if (k == 0) { fprintf(stderr, "No kmer size(s) provided. Will use a default kmer size of 16.\n"); k = 16; }
+    if (k < 1 || k > RK_MAX_K) refuse("k-mer size outside 1 .. " + std::to_string(RK_MAX_K));
+    if (S == 0) S = 1000;
+    rk_ctx* ctx = nullptr;
+    CK(rk_ctx_create(device, &g_policy, &ctx));
+    const std::vector<int> k1(1, k);
+    if (!ref_files.empty()) sketch_files(ctx, ref_files, k1, S, whole_files, refs);
+    if (!query_files.empty()) sketch_files(ctx, query_files, k1, S, whole_files, queries);
+    const SketchSet& q = self ? refs : queries;
+    const size_t nq = q.names.size(), nr = refs.names.size();
+    if (nr == 0 || nq == 0) { fprintf(stderr, "rkmh dist: no %s sketches\n", nr == 0 ? "reference" : "query"); exit(1); }
+    if (nq > 0x7fffffffull || nr > 0x7fffffffull) refuse("more than 2^31-1 sketches on one side");
+    std::vector<int32_t> out4(nq * nr * 4);
+    CK(rk_compare_sketches(ctx, q.sk.data(), q.lens.data(), (int)nq, refs.sk.data(), refs.lens.data(), (int)nr, S, out4.data()));
+    std::string o;
+    char num[96];
+    for (size_t i = 0; i < nq; ++i)
+        for (size_t j = 0; j < nr; ++j) {
+            const int32_t* r = &out4[(i * nr + j) * 4];
+            double jac = 0, d = 1;
+            CK(rk_mash_distance(r[2], r[3], k, &jac, &d));
+            if (d > max_dist) continue;
+            o += refs.names[j]; o += '\t'; o += q.names[i];
+            const int n = snprintf(num, sizeof num, "\t%.6g\t%d/%d\t%d\n", d, r[2], r[3], r[0]);
+            o.append(num, (size_t)n);
+            if (o.size() > (1u << 22)) { fwrite(o.data(), 1, o.size(), stdout); o.clear(); }
+        }
+    fwrite(o.data(), 1, o.size(), stdout);
+    fflush(stdout);
+    rk_ctx_destroy(ctx);
+    return 0;
 }
 
 int main_hash(int argc, char** argv) {
