@@ -171,3 +171,192 @@ def test_mode_cases(orc):
         masked = tc.want_rows(orc, refs, reads, [k], tc.DEFAULT, min_occ=2)
         plain = tc.want_rows(orc, refs, reads, [k], tc.DEFAULT)
         assert (masked[:, 3] < plain[:, 3]).sum() >= 10 and (masked[:, 1] > 0).sum() >= 10, k
+
+
+# ---- the catalogue of the DEDUP forms (dedup=distinct): tests/test_gpu_tile_dedup.py -------------------------------------------------
+import dedup_model as dm  # noqa: E402
+
+
+def test_pol_dedup_field():
+    """the new field is invisible where it is not set: every earlier policy text, and with it every earlier test id, stays as it was"""
+    assert tc.Pol(0, 1, 0, 42) == tc.Pol(0, 1, 0, 42, 0) == tc.DEFAULT and tc.DEFAULT.dedup == 0
+    assert str(tc.DEFAULT) == "fold=swap32,windows=len-k,canon=minhash,seed=42"
+    assert [str(p) for p in tc.DEDUP] == ["fold=swap32,windows=len-k,canon=minhash,seed=42,dedup=distinct",
+                                          "fold=swap32,windows=len-k,canon=lexmin,seed=42,dedup=distinct"]
+    assert all("dedup" not in str(p) for p in tc.CROSS) and len({str(p) for p in tc.CROSS}) == 24
+    assert all(p.dedup and p.seed == 42 for p in tc.DEDUP_CROSS) and len(set(tc.DEDUP_CROSS)) == 12
+    assert tc.DEDUP[1]._replace(dedup=0) == tc.Pol(0, 1, 1, 42)
+
+
+_DISTINCT_FACTS = {}
+
+
+def _distinct_facts(orc, k, pol, reads=None):
+    """(rows under the key, rows of the multiset rule on the same reads, reads that may be handed back) on ragged(k)"""
+    key = (k, pol, reads)
+    if key not in _DISTINCT_FACTS:
+        refs = tc.base_panel()
+        rd = tc.ragged(k).reads if reads is None else reads
+        sk = tc.want_sketches(orc, refs, [k], pol)
+        hs = tc.masked_hashes(orc, rd, [k], pol)
+        rows = tc.rows_distinct(sk, hs)
+        multi = tc.want_rows(orc, refs, rd, [k], pol._replace(dedup=0))
+        back = [i for i, r in enumerate(rd) if tc.may_hand_back_distinct(sk, hs[i], len(r), False)]
+        _DISTINCT_FACTS[key] = (rows, multi, back)
+    return _DISTINCT_FACTS[key]
+
+
+@pytest.mark.parametrize("k", tc.ALL_K)
+def test_dedup_ragged_every_k(orc, k):
+    """at every k the key changes at least four ragged rows (the tandem copies, and at small k nearly every read), and no read is
+    within the kernel's hand-back limits: under the key there is none on how often a value occurs, so k = 1 and 2 are the kernel's too"""
+    for pol in tc.DEDUP:
+        rows, multi, back = _distinct_facts(orc, k, pol)
+        assert rows.shape == multi.shape == (len(tc.ragged(k).reads), 4)
+        assert int((rows != multi).any(axis=1).sum()) >= 4, (k, str(pol))
+        assert (rows[:, 3] <= multi[:, 3]).all() and (rows[:, 1] <= multi[:, 1]).all()
+        assert back == [], (k, str(pol), back)
+        for i in tc.ragged(k).two_n:
+            assert rows[i, 3] == 1
+        every = 1 if k in tc.FULL_L_K else 8
+        if pol.canon and every == 1:
+            every = 8            # (the lexmin model is the slow one: the first and last length of each group of eight are enough here)
+        for L in (tc.uniform_lengths(k, every)[0], tc.uniform_lengths(k, every)[-1]):
+            _, _, uback = _distinct_facts(orc, k, pol, tc.uniform(k, L))
+            assert uback == [], (k, L)
+
+
+def test_dedup_every_field_differs(orc):
+    """over the catalogue the key changes each of the four row fields somewhere"""
+    seen = np.zeros(4, dtype=bool)
+    for k in (1, 2, 3, 7):
+        rows, multi, _ = _distinct_facts(orc, k, tc.DEDUP[0])
+        seen |= (rows != multi).any(axis=0)
+    assert seen.all(), seen
+
+
+@pytest.mark.parametrize("pol", tc.DEDUP_CROSS, ids=str)
+def test_dedup_policy_cross(orc, pol):
+    for k in tc.DEDUP_CROSS_K:
+        rows, multi, back = _distinct_facts(orc, k, pol)
+        assert int((rows != multi).any(axis=1).sum()) >= 4 and back == [], (k, str(pol))
+        assert 2 * int((rows[:, 1] > 0).sum()) >= len(rows), (k, str(pol))
+
+
+def test_distinct_rows_are_the_models(orc):
+    """want_rows / want_sketches under the key (hashes from the oracle or the lexmin model, the rule from dedup_model) against
+    dedup_model.classify / sketch_refs on the numpy model's hashes, plain and under -M 2 with every bound the device tests use"""
+    refs = tc.base_panel()
+    for pol in tc.DEDUP:
+        for k in (1, 24, 64):
+            reads = list(tc.ragged(k).reads)
+            sk = tc.want_sketches(orc, refs, [k], pol)
+            other = dm.sketch_refs(list(refs), [k], tc.S, pol.model())
+            assert all(a.tolist() == b.tolist() for a, b in zip(sk, other))
+            assert (tc.want_rows(orc, refs, reads, [k], pol, sketches=sk) == dm.classify(reads, other, [k], tc.S, pol.model())).all()
+            counter = sm.count_hashes(reads, [k], tc.COUNT_SLOTS, pol.model())
+            for bound in (None, 3, 0):
+                a = tc.want_rows(orc, refs, reads, [k], pol, sketches=sk, min_occ=2, bound=bound)
+                b = dm.classify(reads, other, [k], tc.S, pol.model(), counter=counter, min_occ=2, bound=bound)
+                assert (a == b).all(), (k, str(pol), bound)
+
+
+def _uset(windows):
+    u = 64
+    while u < 2 * windows and u < 2 * tc.DEDUP_MAX_WINDOWS:
+        u <<= 1
+    return u
+
+
+def test_set_ladder(orc):
+    refs, k = tc.base_panel(), tc.LADDER_K
+    assert [_uset(W) for W in tc.LADDER_W] == [64, 128, 128, 256, 256, 512, 512, 1024, 1024, 2048, 2048, 4096]
+    assert [2 * W == _uset(W) for W in tc.LADDER_W] == [True, False] * 6           # every other set is exactly half full
+    for pol in tc.DEDUP:
+        sk = tc.want_sketches(orc, refs, [k], pol)
+        for W in tc.LADDER_W:
+            lad = tc.set_ladder(W)
+            assert max(tc.nwin(len(r), k, pol) for r in lad.reads) == W
+            assert lad.random == (5, 6, 7) and len({lad.reads[i] for i in lad.random}) == 1
+            hs = tc.masked_hashes(orc, lad.reads, [k], pol)
+            rows = tc.rows_distinct(sk, hs)
+            assert [int(rows[i, 3]) for i in lad.random] == [W] * 3, (W, str(pol))      # every window its own value
+            assert rows[lad.periodic, 3] == 11 and len(hs[lad.periodic]) == W, (W, str(pol))
+            assert rows[lad.random[0], 1] >= (200 if W >= 512 else 1) and rows[lad.random[0], 0] == 10
+            assert not any(tc.may_hand_back_distinct(sk, hs[i], len(r), False) for i, r in enumerate(lad.reads)), (W, str(pol))
+        reads = tc.stale_set()
+        rows = tc.want_rows(orc, refs, reads, [k], pol, sketches=sk)
+        assert len(reads) == 37 and len(set(reads)) == 1 and len(reads[0]) == 150
+        assert (rows == rows[0]).all() and rows[0].tolist() == [3, 126, 126, 126]
+
+
+def test_several_k_in_one_set(orc):
+    refs = tc.base_panel()
+    for pol in tc.DEDUP:
+        for ks in tc.K_LISTS:
+            sk = tc.want_sketches(orc, refs, ks, pol)     # ([31, 33, 63]: the longest references are sketched to S of their 2573 hashes)
+            for k in ks:
+                for reads in (tc.ragged(k).reads, tc.uniform(k, k + 40)):
+                    hs = tc.masked_hashes(orc, reads, ks, pol)
+                    if reads is not tc.uniform(k, k + 40):   # a set sized from the first k alone would be too small for the longest ragged read
+                        assert _uset(max(len(h) for h in hs)) > _uset(max(tc.nwin(len(r), ks[0], pol) for r in reads)), (ks, k)
+                    assert not any(tc.may_hand_back_distinct(sk, h, len(r), False) for h, r in zip(hs, reads)), (ks, k, str(pol))
+        ks = tc.LIMIT_KS
+        tc.assert_wholly_sketched(refs, ks, pol)
+        sk = tc.want_sketches(orc, refs, ks, pol)
+        at_limit, beyond, at = tc.several_k_limit()
+        for batch, windows in ((at_limit, 2048), (beyond, 2050)):
+            hs = tc.masked_hashes(orc, batch, ks, pol)
+            assert len(batch[at]) == max(len(r) for r in batch) <= tc.FUSED_MAXLEN
+            assert len(hs[at]) == windows == sum(tc.nwin(len(batch[at]), k, pol) for k in ks)
+            distinct = len(np.unique(hs[at][hs[at] != 0]))
+            assert 1000 <= distinct <= tc.S and windows > tc.S, distinct                      # the kernel's to answer; the host entry routes by windows
+            back = [tc.may_hand_back_distinct(sk, h, len(r), False) for h, r in zip(hs, batch)]
+            assert back == [i == at and windows > tc.DEDUP_MAX_WINDOWS for i in range(len(batch))]
+            rows = tc.rows_distinct(sk, hs)
+            assert rows[at, 0] == 10 and rows[at, 1] >= 300 and rows[at, 3] == distinct
+
+
+@pytest.mark.parametrize("k", [64, 24])
+def test_prefetch_edges_dedup(orc, k):
+    refs = tc.base_panel()
+    for pol in tc.DEDUP:
+        sk = tc.want_sketches(orc, refs, [k], pol)
+        for L in tc.PREFETCH_L:
+            reads, at = tc.prefetch_edges(L, k)
+            hs = tc.masked_hashes(orc, reads, [k], pol)
+            rows = tc.rows_distinct(sk, hs)
+            assert rows[at, 1] >= 100 and rows[at, 0] == 10
+            back = [tc.may_hand_back_distinct(sk, h, len(r), False) for h, r in zip(hs, reads)]
+            assert back == [i == at and L > tc.FUSED_MAXLEN for i in range(len(reads))]
+
+
+def test_exactly_s(orc):
+    refs, S = tc.base_panel(), tc.EXACT_S
+    for pol in tc.DEDUP:
+        for k in tc.EXACT_K:
+            reads = tc.exactly_s(orc, k, pol)
+            sk = tc.want_sketches(orc, refs, [k], pol, sketch_size=S)
+            assert all(len(x) == S for x in sk)
+            hs = tc.masked_hashes(orc, reads, [k], pol)
+            rows = tc.rows_distinct(sk, hs, sketch_size=S)
+            for i, p in enumerate(tc.EXACT_P):
+                assert len(hs[i]) > S and len(np.unique(hs[i][hs[i] != 0])) == p and (hs[i] != 0).all()
+                assert rows[i, 3] == min(p, S)
+                assert tc.may_hand_back_distinct(sk, hs[i], len(reads[i]), False, sketch_size=S) == (p > S)
+            for i in range(len(tc.EXACT_P), len(reads)):
+                assert 0 < len(hs[i]) < S and not tc.may_hand_back_distinct(sk, hs[i], len(reads[i]), False, sketch_size=S)
+            assert (rows[len(tc.EXACT_P):, 1] > 0).sum() >= 3
+
+
+def test_dedup_mode_cases(orc):
+    """-M 2 under the key: the mask lowers field 3 on at least 30 rows and the best score on at least one"""
+    refs = tc.base_panel()
+    for pol in tc.DEDUP:
+        for k in tc.MODE_K + (24,):
+            reads = tc.ragged(k).reads
+            plain, _, _ = _distinct_facts(orc, k, pol)
+            masked = tc.want_rows(orc, refs, reads, [k], pol, min_occ=2)
+            assert (masked[:, 3] < plain[:, 3]).sum() >= 30 and (masked[:, 1] < plain[:, 1]).sum() >= 1, (k, str(pol))
+            capped = tc.want_rows(orc, refs, reads, [k], pol, min_occ=2, bound=3)
+            assert (capped[:, 3] == np.minimum(masked[:, 3], 3)).all() and (capped[:, :3] == masked[:, :3]).all()

@@ -12,14 +12,22 @@ comes back flagged fails the test.
   panel            base_panel(): 12 references of 400 .. 900 bases (a 2 % diverged pair, an exact duplicate, a tandem repeat of a
                    7-base unit, one with lower case / N / IUPAC letters)
   read sets        ragged(k), uniform(k, L), counter_width(), prefetch_edges(L, k), panel_edges(nref)
-  policies         Pol(fold, drop, canon, seed): the text for a Context, the oracle's struct, the model's dict
+  policies         Pol(fold, drop, canon, seed[, dedup]): the text for a Context, the oracle's struct, the model's dict
   expectations     want_rows / want_sketches: the oracle for canon=minhash, tests/sourmash_model.py for canon=lexmin
+
+The DEDUP forms of the kernel (dedup=distinct: k_classify_tile<0, MODE, -1, PF, CANON, true>) have a catalogue of their own on the same
+panel: Pol(..., dedup=1), the window hashes as above, the sketch rule from tests/dedup_model.py (want_rows / want_sketches dispatch on
+pol.dedup), the kernel's limits under the key in `may_hand_back_distinct`.
+
+  read sets        ragged(k), uniform(k, L), prefetch_edges(L, k) as above; set_ladder(W), stale_set(), several_k_limit(),
+                   exactly_s(k, pol): what only the per-read set of distinct hashes can get wrong
 """
 import collections
 import functools
 
 import numpy as np
 
+import dedup_model as dm
 import sourmash_model as sm
 
 S = 2000
@@ -42,10 +50,11 @@ PREFETCH_L = (504, 505, 760, 761, 1528, 1529)   # tile bytes <= 504 / 760 / 1528
 PANEL_NREF = (256, 257, 512, 513)               # dense | sparse rows: 512 | 513 with 8-bit fields, 256 | 257 with 16-bit
 
 
-class Pol(collections.namedtuple("Pol", "fold drop canon seed")):
+class Pol(collections.namedtuple("Pol", "fold drop canon seed dedup", defaults=(0,))):
     def spec(self):
-        return "fold=%s,windows=%s,canon=%s,seed=%d" % (("swap32", "h1", "w2w1")[self.fold], "len-k" if self.drop else "len-k+1",
+        text = "fold=%s,windows=%s,canon=%s,seed=%d" % (("swap32", "h1", "w2w1")[self.fold], "len-k" if self.drop else "len-k+1",
                                                         "lexmin" if self.canon else "minhash", self.seed)
+        return text + (",dedup=distinct" if self.dedup else "")
 
     def oracle(self, orc):
         assert not self.canon            # the oracle knows the minhash strand rule only
@@ -60,6 +69,16 @@ class Pol(collections.namedtuple("Pol", "fold drop canon seed")):
 
 DEFAULT = Pol(0, 1, 0, 42)
 CROSS = [Pol(f, d, c, s) for f in (0, 1, 2) for d in (1, 0) for c in (0, 1) for s in CROSS_SEEDS]
+DEDUP = (Pol(0, 1, 0, 42, dedup=1), Pol(0, 1, 1, 42, dedup=1))      # "both strand rules" of the DEDUP catalogue
+DEDUP_CROSS = [Pol(f, d, c, 42, dedup=1) for f in (0, 1, 2) for d in (1, 0) for c in (0, 1)]
+DEDUP_CROSS_K = (1, 8, 16, 17, 32, 33, 64)
+DEDUP_MAX_WINDOWS = 2048     # half of the largest per-read set (DEDUP_MAX_SLOTS, rk_classify.hip)
+LADDER_K = 24
+LADDER_W = (32, 33, 64, 65, 128, 129, 256, 257, 512, 513, 1024, 1025)   # windows of the longest read: uset = 64 | 128 | ... | 2048 | 4096
+LIMIT_KS = [16, 64]          # 2 L - 80 windows under windows=len-k: 2048 at L = 1064
+EXACT_S = 64                 # the sketch size of exactly_s()
+EXACT_K = (16, 24)
+EXACT_P = (63, 64, 65)
 
 
 def nwin(length, k, pol=DEFAULT):
@@ -224,6 +243,69 @@ def panel_edges(nref):
     return PanelEdges(refs, family, tuple(short), tuple(lng))
 
 
+# ---- read sets for the DEDUP forms: what only the per-read set of distinct hashes can get wrong --------------------------------------
+Ladder = collections.namedtuple("Ladder", "reads random periodic")
+
+
+@functools.lru_cache(maxsize=None)
+def set_ladder(W, k=LADDER_K):
+    """a batch whose longest read has W windows under windows=len-k (the host sizes the set from it: the power of two >= 2 W): a random
+    read of W windows around at most 250 panel bases (every hash distinct: at W = uset / 2 its set is exactly half full), three times in
+    a row (.random: for any T >= 2 reads per tile two neighbours share a tile -- (5, 6) unless T is 2, 3 or 6, (6, 7) unless T is 7 -- so
+    a set addressed by the wrong read of the tile shows as a read without distinct hashes), a read of W windows with period 11
+    (.periodic), ten short panel reads"""
+    rng = np.random.default_rng(90000 + W)
+    P = base_panel()
+    L = W + k
+    seg = P[10][300:300 + min(250, L // 2)]
+    cut = int(rng.integers(0, L - len(seg) + 1))
+    rnd = rand(rng, cut) + seg + rand(rng, L - cut - len(seg))
+    per = (rand(rng, 11) * (L // 11 + 1))[:L]
+    short = [_cut(rng, P, min(L, 30 + 8 * i)) for i in range(10)]
+    reads = short[:5] + [rnd, rnd, rnd, per] + short[5:]
+    assert max(len(r) for r in reads) == L == len(rnd) == len(per) and nwin(L, k) == W
+    return Ladder(tuple(reads), (5, 6, 7), 8)
+
+
+def stale_set():
+    """one 150-base panel read 37 times: whatever T is, some workgroup walks two tiles of it, and an entry left in a set by the first
+    makes every window of the second a duplicate"""
+    return (base_panel()[3][200:350],) * 37
+
+
+@functools.lru_cache(maxsize=None)
+def several_k_limit():
+    """(batch at the limit, batch beyond it, place of the long read) for ks = LIMIT_KS under windows=len-k: X + X with X of 532 bases
+    (250 of them from the panel) has 1048 + 1000 = 2048 windows -- only a list of k reaches that, a staged read has at most 1528 bases --
+    and 2 * 532 distinct hashes; one base more makes 2050 windows"""
+    rng = np.random.default_rng(2048)
+    P = base_panel()
+    X = rand(rng, 140) + P[10][300:550] + rand(rng, 142)
+    short = [_cut(rng, P, 70 + 7 * i) for i in range(10)]
+    return tuple(short[:5] + [X + X] + short[5:]), tuple(short[:5] + [X + X + b"A"] + short[5:]), 5
+
+
+_EXACTLY_S = {}
+
+
+def exactly_s(orc, k, pol):
+    """reads for a sketch of EXACT_S = 64: three copies of a random unit of p = 63, 64, 65 bases (more windows than S, exactly p distinct
+    hashes: the unit is redrawn until that holds), then ten panel reads of fewer windows than S"""
+    if (k, pol) not in _EXACTLY_S:
+        rng = np.random.default_rng(6400 + k)
+        reads = []
+        for p in EXACT_P:
+            while True:
+                r = rand(rng, p) * 3
+                h = window_hashes(orc, r, [k], pol)
+                if len(h) > EXACT_S and len(np.unique(h[h != 0])) == p:
+                    break
+            reads.append(r)
+        reads += [_cut(rng, base_panel(), k + 6 + 5 * i) for i in range(10)]
+        _EXACTLY_S[(k, pol)] = tuple(reads)
+    return _EXACTLY_S[(k, pol)]
+
+
 def sparse_rows(nref, max_windows):
     """the kernel's documented rule (make_geom): 8-bit count fields while no read of the batch has more than 255 windows, else 16-bit;
     a dense row of more than 128 words becomes a 128-entry map"""
@@ -260,8 +342,11 @@ def window_hashes(orc, seq, ks, pol):
     return orc.calc_hashes(orc.to_upper(seq), ks, pol.oracle(orc))
 
 
-def want_sketches(orc, refs, ks, pol):
+def want_sketches(orc, refs, ks, pol, sketch_size=S):
     """list of ascending arrays, one per reference"""
+    if pol.dedup:
+        return [dm.bottom_distinct(window_hashes(orc, r, ks, pol), sketch_size) for r in refs]
+    assert sketch_size == S
     if pol.canon:
         return sm.sketch_refs(list(refs), ks, S, pol.model())
     rb, ro = pack(list(refs))
@@ -269,9 +354,44 @@ def want_sketches(orc, refs, ks, pol):
     return [sk[j, : int(ln[j])] for j in range(len(refs))]
 
 
-def want_rows(orc, refs, reads, ks, pol, sketches=None, min_occ=None, slots=COUNT_SLOTS):
-    """int32 [n, 4] rows (max_id, max_shared, diff, min_num); min_occ: under the exact -M mask counted over these very reads"""
-    sketches = want_sketches(orc, refs, ks, pol) if sketches is None else sketches
+def masked_hashes(orc, reads, ks, pol, min_occ=None, slots=COUNT_SLOTS):
+    """every read's window hashes, all k pooled; min_occ: after mask_by_frequency against the counts of these very reads' windows
+    (every window counts, a zero hash in slot 0, a repeated value each time: the count pass is the same under either sketch rule)"""
+    hs = [window_hashes(orc, r, ks, pol) for r in reads]
+    if min_occ is None:
+        return hs
+    counter = np.zeros(slots, dtype=np.int64)
+    for h in hs:
+        np.add.at(counter, (h % np.uint64(slots)).astype(np.int64), 1)
+    return [sm.mask_by_frequency(h, counter, min_occ, pol.model()) for h in hs]
+
+
+def rows_distinct(sketches, hs, sketch_size=S, bound=None):
+    """the rule of tests/dedup_model.py on given hashes: sketch = bottom_distinct, shared = a set intersection, field 3 = len(sketch)
+    (capped by `bound`: rk_set_min_num_bound), first maximum wins"""
+    post = {}
+    for j, sk in enumerate(sketches):
+        for v in np.unique(sk).tolist():
+            post.setdefault(v, []).append(j)
+    rows = np.zeros((len(hs), 4), dtype=np.int32)
+    for i, h in enumerate(hs):
+        mins = dm.bottom_distinct(h, sketch_size)
+        shared = [0] * len(sketches)
+        for v in mins.tolist():
+            for j in post.get(v, ()):
+                shared[j] += 1
+        mi, ms, d = sm.argmax_diff(shared)
+        rows[i] = (mi, ms, d, len(mins) if bound is None or bound < 0 else min(len(mins), bound))
+    return rows
+
+
+def want_rows(orc, refs, reads, ks, pol, sketches=None, min_occ=None, slots=COUNT_SLOTS, bound=None, sketch_size=S):
+    """int32 [n, 4] rows (max_id, max_shared, diff, min_num); min_occ: under the exact -M mask counted over these very reads;
+    bound, sketch_size: for dedup=distinct policies only"""
+    sketches = want_sketches(orc, refs, ks, pol, sketch_size) if sketches is None else sketches
+    if pol.dedup:
+        return rows_distinct(sketches, masked_hashes(orc, reads, ks, pol, min_occ, slots), sketch_size, bound)
+    assert bound is None and sketch_size == S
     if pol.canon:
         counter = sm.count_hashes(list(reads), ks, slots, pol.model()) if min_occ is not None else None
         return sm.classify(list(reads), sketches, ks, S, pol.model(), counter=counter, min_occ=min_occ or 0)
@@ -319,6 +439,22 @@ def may_hand_back(sketches, h, length, sparse):
         multi, _ = shared_counts(sketches, h)
         return int((multi > 0).sum()) > 128
     return False
+
+
+def may_hand_back_distinct(sketches, h, length, sparse, sketch_size=S):
+    """The kernel's documented limits under dedup=distinct, on one read's (masked) window hashes of all k: it may come back flagged
+    when it is longer than the kernel stages, has more windows than half the largest per-read set, more distinct non-zero hashes than
+    the sketch keeps, hits more than 1024 distinct sketch hashes, or -- under a sparse row -- more than 128 references.  A duplicate
+    is dropped before the look-up, so the hit set only ever sees rank 0: no limit on how often a sketch hash occurs."""
+    if length > FUSED_MAXLEN or len(h) > DEDUP_MAX_WINDOWS:
+        return True
+    v = np.unique(h[h != 0])
+    if len(v) > sketch_size:
+        return True
+    hit = [np.isin(v, np.asarray(s, dtype=np.uint64)) for s in sketches]
+    if int(np.logical_or.reduce(hit).sum()) > 1024 if hit else False:
+        return True
+    return bool(sparse) and sum(1 for x in hit if x.any()) > 128
 
 
 def row_from_shared(multi, h):
