@@ -608,6 +608,42 @@ int rk_compare_sketches_device(rk_ctx* ctx, const void* d_a, const void* d_alens
 int rk_merge_sketches(const uint64_t* sketches, const int32_t* lens, int n, int sketch_size, int distinct, uint64_t* out, int32_t* out_len);
 int rk_mash_distance(int common, int denom, int k, double* jaccard, double* distance);
 
+/* ------------------------------------------------------------------------------------------------
+ * SCALED SKETCHES (`rkmh sketch --scaled`, `rkmh dist --scaled`; the FracMinHash sketches that sourmash makes by default).  These
+ * are this library's own definitions; no compatibility with any other tool's files is claimed.
+ *   max_hash(scaled) = floor((2^64 - 1) / scaled), scaled >= 1; scaled = 1 keeps everything.
+ *   The scaled sketch of a sequence: the ascending array of the DISTINCT window hashes h with 0 < h <= max_hash, under the
+ *   context's policy and the k-mer sizes given, pooled over the sizes as rk_sketch_batch pools them.  0 stays "no hash".  A scaled
+ *   sketch is a set under every policy (the dedup key governs bottom-S sketches only); fold, windows, canon and seed apply unchanged.
+ *   A batch of scaled sketches is CSR: sketch i is values[offsets[i], offsets[i + 1]), both arrays uint64, offsets[n + 1].
+ *   For a pair: shared = |A & B|, union = |A| + |B| - shared, Jaccard = shared / union, containment of A in B = shared / |A|.
+ *   A sketch made at scaled = n becomes one of scaled N >= n by cutting it at the first value above max_hash(N) (rk_merge_scaled).
+ * rk_scaled_max_hash: host only; RK_ERR_ARG for scaled = 0.
+ * rk_sketch_scaled_batch: input as for rk_hash_batch.  *values is malloc'd (rk_free), sk_offsets[nseq + 1] is the caller's.  It takes
+ * max_hash rather than scaled, so a threshold can sit exactly on a hash.  Any batch the general path takes: empty sequences,
+ * sequences shorter than k, up to 2^31 - 1 bases in one, any number of chunks.  Per chunk the window hashes are kept, compacted with
+ * wave ballots, sorted by sequence and freed of repeats on the device (rk_scaled.hip).
+ * rk_compare_scaled: host arrays; shared[i * nb + j] = |a_i & b_j|.  a and b may be the same arrays: uploaded once.  RK_ERR_ARG for
+ * NULL, na or nb below 1, offsets that decrease, a sketch of 2^31 values or more, lanes outside {0, 1, 8, 64}.  The answer is
+ * downloaded in row blocks.  lanes: how many lanes of k_scaled_pairs share one pair; 0 = chosen from the mean length of the shorter
+ * side; the answer never depends on it.
+ * rk_compare_scaled_device: resident arrays (x_nvalues = the number of uint64 behind d_x_values; d_shared: na * nb int32),
+ * asynchronous on hip_stream (NULL = HIP's null stream; rk_ctx_stream() = the context's own).  Every row is clamped on the device to
+ * lie inside [0, nvalues]; rows that are not ascending give meaningless counts and nothing worse.
+ * rk_merge_scaled: host only; the ascending distinct union of n sketches cut at max_hash -> *out (malloc'd, rk_free), *out_len.
+ * rk_scaled_distance: host only; rk_mash_distance's formula and clamps on j = shared / (la + lb - shared); j = 0 and distance 1 when
+ * the union is empty; RK_ERR_ARG for negative counts, shared > min(la, lb) or k < 1.  Either result pointer may be NULL. */
+int rk_scaled_max_hash(uint64_t scaled, uint64_t* max_hash);
+int rk_sketch_scaled_batch(rk_ctx* ctx, const uint8_t* bases, const uint64_t* offsets, int64_t nseq, const int* ks, int nks,
+                           uint64_t max_hash, uint64_t** values, uint64_t* sk_offsets);
+int rk_compare_scaled(rk_ctx* ctx, const uint64_t* a_values, const uint64_t* a_offsets, int na, const uint64_t* b_values,
+                      const uint64_t* b_offsets, int nb, int lanes, int32_t* shared);
+int rk_compare_scaled_device(rk_ctx* ctx, const void* d_a_values, const void* d_a_offsets, int na, uint64_t a_nvalues,
+                             const void* d_b_values, const void* d_b_offsets, int nb, uint64_t b_nvalues, int lanes,
+                             void* d_shared, void* hip_stream);
+int rk_merge_scaled(const uint64_t* values, const uint64_t* offsets, int n, uint64_t max_hash, uint64_t** out, uint64_t* out_len);
+int rk_scaled_distance(int64_t shared, int64_t la, int64_t lb, int k, double* jaccard, double* distance);
+
 #ifdef __cplusplus
 }
 #endif

@@ -225,6 +225,13 @@ _SIGS = {
     "rk_compare_sketches_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "rk_merge_sketches": (C.c_int, [_u64p, _i32p, C.c_int, C.c_int, C.c_int, _u64p, _i32p]),
     "rk_mash_distance": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "rk_scaled_max_hash": (C.c_int, [C.c_uint64, C.POINTER(C.c_uint64)]),
+    "rk_sketch_scaled_batch": (C.c_int, [C.c_void_p, _u8p, _u64p, C.c_int64, C.POINTER(C.c_int), C.c_int, C.c_uint64, C.POINTER(_u64p), _u64p]),
+    "rk_compare_scaled": (C.c_int, [C.c_void_p, _u64p, _u64p, C.c_int, _u64p, _u64p, C.c_int, C.c_int, _i32p]),
+    "rk_compare_scaled_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int, C.c_uint64,
+                                           C.c_int, C.c_void_p, C.c_void_p]),
+    "rk_merge_scaled": (C.c_int, [_u64p, _u64p, C.c_int, C.c_uint64, C.POINTER(_u64p), C.POINTER(C.c_uint64)]),
+    "rk_scaled_distance": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
 }
 
 
@@ -905,6 +912,40 @@ def mash_distance(common, denom, k):
     return j.value, d.value
 
 
+def scaled_max_hash(scaled):
+    """rk_scaled_max_hash (host code, no GPU): floor((2^64 - 1) / scaled); a scaled sketch keeps the hashes 0 < h <= max_hash."""
+    v = C.c_uint64()
+    _chk(load_library().rk_scaled_max_hash(C.c_uint64(int(scaled)), C.byref(v)))
+    return int(v.value)
+
+
+def _csr(values, offsets):
+    values = np.ascontiguousarray(values, dtype=np.uint64)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    if len(offsets) < 1 or int(offsets[-1]) > len(values) or int(offsets.max()) > len(values):
+        raise ValueError("offsets run past the %d values" % len(values))
+    return values, offsets
+
+
+def merge_scaled(values, offsets, max_hash=(1 << 64) - 1):
+    """rk_merge_scaled (host code, no GPU): the ascending distinct union of the CSR sketches (values, offsets[n + 1]) cut at
+    max_hash -> uint64 array.  One sketch and a smaller max_hash: that sketch at a larger `scaled`."""
+    values, offsets = _csr(values, offsets)
+    out, n = _u64p(), C.c_uint64()
+    lib = load_library()
+    _chk(lib.rk_merge_scaled(_p(values, C.c_uint64), _p(offsets, C.c_uint64), len(offsets) - 1, C.c_uint64(int(max_hash)), C.byref(out), C.byref(n)))
+    r = np.ctypeslib.as_array(out, shape=(max(int(n.value), 1),))[: int(n.value)].copy()
+    lib.rk_free(out)
+    return r
+
+
+def scaled_distance(shared, la, lb, k):
+    """rk_scaled_distance (host code, no GPU): (jaccard, distance) of two scaled sketches of la and lb values that share `shared`."""
+    j, d = C.c_double(), C.c_double()
+    _chk(load_library().rk_scaled_distance(int(shared), int(la), int(lb), int(k), C.byref(j), C.byref(d)))
+    return j.value, d.value
+
+
 class Context:
     """One GPU. Methods are named after the reference's functions they replace."""
 
@@ -1026,6 +1067,46 @@ class Context:
             stream = self.stream
         _chk(self._lib.rk_compare_sketches_device(self._h, C.c_void_p(d_a_ptr), C.c_void_p(d_alens_ptr), na, C.c_void_p(d_b_ptr),
                                                   C.c_void_p(d_blens_ptr), nb, sketch_size, C.c_void_p(d_out_ptr), C.c_void_p(stream)))
+
+    # ---- scaled sketches -----------------------------------------------------------------------
+    def sketch_scaled_batch(self, bases, offsets, ks, max_hash):
+        """rk_sketch_scaled_batch: the distinct window hashes 0 < h <= max_hash of every sequence, ascending -> (values uint64,
+        offsets uint64 [n + 1]): sketch i is values[offsets[i]:offsets[i + 1]]."""
+        ks = _ks(ks)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = len(offsets) - 1
+        so = np.zeros(n + 1, dtype=np.uint64)
+        out = _u64p()
+        _chk(self._lib.rk_sketch_scaled_batch(self._h, _p(bases, C.c_uint8), _p(offsets, C.c_uint64), n, _p(ks, C.c_int), len(ks),
+                                              C.c_uint64(int(max_hash)), C.byref(out), _p(so, C.c_uint64)))
+        tot = int(so[-1])
+        r = np.ctypeslib.as_array(out, shape=(max(tot, 1),))[:tot].copy()
+        self._lib.rk_free(out)
+        return r, so
+
+    def compare_scaled(self, a_values, a_offsets, b_values=None, b_offsets=None, lanes=0):
+        """rk_compare_scaled: every CSR sketch of `a` against every one of `b` (None: of `a` itself) -> int32 [na, nb], the number
+        of shared values.  lanes: 0 (chosen from the lengths), 1, 8 or 64 lanes of the kernel per pair; the answer is the same."""
+        a_values, a_offsets = _csr(a_values, a_offsets)
+        if b_values is None:
+            b_values, b_offsets = a_values, a_offsets
+        else:
+            b_values, b_offsets = _csr(b_values, b_offsets)
+        na, nb = len(a_offsets) - 1, len(b_offsets) - 1
+        out = np.zeros((max(na, 0), max(nb, 0)), dtype=np.int32)
+        _chk(self._lib.rk_compare_scaled(self._h, _p(a_values, C.c_uint64), _p(a_offsets, C.c_uint64), na, _p(b_values, C.c_uint64),
+                                         _p(b_offsets, C.c_uint64), nb, int(lanes), _p(out, C.c_int32)))
+        return out
+
+    def compare_scaled_device(self, d_a_values_ptr, d_a_offsets_ptr, na, a_nvalues, d_b_values_ptr, d_b_offsets_ptr, nb, b_nvalues,
+                              d_shared_ptr, lanes=0, stream=None):
+        """Resident CSR arrays (raw device pointers; d_shared: na * nb int32); asynchronous.  Rows are clamped to [0, nvalues] on the
+        device.  stream as for compare_sketches_device."""
+        if stream is None:
+            stream = self.stream
+        _chk(self._lib.rk_compare_scaled_device(self._h, C.c_void_p(d_a_values_ptr), C.c_void_p(d_a_offsets_ptr), na, C.c_uint64(int(a_nvalues)),
+                                                C.c_void_p(d_b_values_ptr), C.c_void_p(d_b_offsets_ptr), nb, C.c_uint64(int(b_nvalues)),
+                                                int(lanes), C.c_void_p(d_shared_ptr), C.c_void_p(stream)))
 
     # ---- outer boundary (batches) ------------------------------------------------------------
     def hash_batch(self, bases, offsets, ks):

@@ -7,6 +7,8 @@
 //   rk_counters.hip  HASHTCounter (full and compact), its (de)serialisation
 //   rk_frontend.hip  FASTQ slots (text parsed on the device), BGZF jobs inflated on the device, reference FASTA through the device
 //   rk_call.hip      `call`
+//   rk_pairs.hip     all-pairs comparison of bottom-S sketches
+//   rk_scaled.hip    scaled sketches: the keep step of the general path, all-pairs intersection of variable-length sets
 #pragma once
 #include "../../include/rkmh_amd.h"
 #include "rk_kernels.hpp"
@@ -149,6 +151,7 @@ struct rk_ctx {
     KmerSets ksets_m{};                      // ksets with km1 = the masked copies (valid while a bounded depth filter is set)
     // workspaces for the general path
     DevBuf w_bases, w_tiles, w_hashes, w_segoff, w_ids, w_sk, w_lens, w_out, w_misc, w_sel, w_selstate, w_table, w_gcount, w_tail, w_dedup;
+    DevBuf w_sc_cnt, w_sc_pre, w_sc_off, w_sc_a, w_sc_b; // scaled sketches (rk_scaled.hip): block counts, their scan, CSR offsets, kept / distinct values
     int ref_count_mode = 0; // -I counter fill: 0 per k-mer occurrence (stream), 1 once per distinct hash per reference (filter)
     Slot slot[2];
 };
@@ -156,6 +159,8 @@ struct rk_ctx {
 inline int set_dev(rk_ctx* c) { HIPCHK(hipSetDevice(c->device)); return RK_OK; }
 
 // ---- the general path (rk_general.hip): hash tiles -> (optional) in-LDS sort / sketch / intersect, for sequences of any length
+// scaled sketches of a batch, grown chunk by chunk (rk_scaled.hip): values is malloc'd, offsets[n + 1] the caller's
+struct ScaledSink { uint64_t max_hash = 0; uint64_t* values = nullptr; size_t len = 0, cap = 0; uint64_t* offsets = nullptr; };
 struct GeneralOut {
     uint64_t* hashes = nullptr;      // host, [total hashes of the batch] (caller sized via hash_offsets)
     uint64_t* sketches = nullptr;    // host [n*S]
@@ -163,6 +168,7 @@ struct GeneralOut {
     int32_t* out4 = nullptr;         // host [n*4]
     bool write_back_sorted = false;  // hashes out = sorted segments (minhashes in-place semantics)
     int32_t* tail_counts = nullptr;  // host [n * (nref - argmax_n)] (cfg.argmax_n > 0)
+    ScaledSink* scaled = nullptr;    // the distinct hashes 0 < h <= max_hash of every sequence, ascending, as CSR
 };
 struct GeneralCfg {
     KsArr ks;
@@ -237,6 +243,8 @@ inline uint64_t hashes_of(const DevPolicy& pol, const KsArr& ks, uint64_t len) {
 }
 GeneralCfg classify_cfg(const rk_ctx* c); // classification against the context's references, its depth filter applied   // rk_general.hip
 int general_run(rk_ctx* c, const uint8_t* bases, const uint8_t* d_bases_in, const uint64_t* offsets, int64_t n, const GeneralCfg& cfg, const GeneralOut& out);
+// the scaled step of one chunk (hashes in w_hashes, segment offsets seg[] also at w_segoff): appends to sink; synchronises c->st   // rk_scaled.hip
+int scaled_keep_chunk(rk_ctx* c, const std::vector<uint64_t>& seg, uint64_t nhashes, int64_t i0, ScaledSink& sink);
 int fused_device(rk_ctx* c, const void* d_bases, const void* d_offs, int64_t nreads, void* d_out4, uint32_t max_read_len, int mode, rk_counter* count_into, // rk_route.hip
                  hipStream_t st, uint64_t total_bases = 0);
 // rows the fused kernel flagged (max_id == -2; `rows` = host copy of d_out4) answered by the general kernels on the resident bases and scattered back into d_out4 AND rows; synchronises st

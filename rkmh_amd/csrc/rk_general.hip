@@ -324,6 +324,11 @@ int general_run(rk_ctx* c, const uint8_t* bases, const uint8_t* d_bases_in, cons
         RKCHK(upload_and_hash(c, bases, d_bases_in, cfg, out, ch, hash_cursor));
         tick("uploaded, hashing launched");
         RKCHK(count_hashes(c, cfg, ch, hash_cursor));
+        if (out.scaled) {
+            if (gtiming) { HIPCHK(hipStreamSynchronize(c->st)); tick("hashed"); }
+            RKCHK(scaled_keep_chunk(c, ch.seg, ch.nhashes, ch.i0, *out.scaled));
+            tick("scaled kept");
+        }
         if (needs_sort(out)) {
             RKCHK(sort_chunk(c, cfg, out, ch, ntail));
             tick("sorts launched");

@@ -1,0 +1,383 @@
+// rk_scaled.hip -- scaled (FracMinHash) sketches (include/rkmh_amd.h, "SCALED SKETCHES"): the step of the general path that turns a
+// chunk's window hashes into one variable-length set per sequence (keep / sort / drop repeats), and k_scaled_pairs, which intersects
+// every pair of such sets.  The host-only half (threshold, union, distance) is rk_scaled_host.cpp; semantics, routes, the lane rule
+// and measurements: DESIGN.md section 11.
+#include "rk_api_internal.hpp"
+
+namespace {
+
+// ---- keeping: an order-preserving compaction of a flat array, run twice per chunk -------------------------------------------
+//   KEEP_HASH      v = the chunk's window hashes:          element t stays when 0 < v[t] <= max_hash
+//   KEEP_FIRST     v = the kept values, sorted by segment: element t stays when it is the first of its value in its segment
+// Because the order is kept, a sequence's values stay together; where a sequence begins in the output is the number of elements kept
+// before its first one (k_keep_bounds).  Count first (k_keep_count), scan the block counts (k_scan_blocks), size the output, scatter
+// (k_keep_scatter): no atomics, positions come from wave ballots.
+enum { KEEP_HASH = 0, KEEP_FIRST = 1 };
+constexpr int KEEP_T = 256, KEEP_ROUNDS = 4, KEEP_BLK = KEEP_T * KEEP_ROUNDS; // elements of one workgroup: round r, thread t -> element r * 256 + t
+
+// does a segment begin at element t?  off[0 .. nseg] ascending (equal entries: empty segments); at most 33 halvings
+__device__ __forceinline__ bool segment_starts_at(const uint64_t* __restrict__ off, uint32_t nseg, uint64_t t) {
+    uint32_t lo = 0, hi = nseg + 1; // first entry >= t
+    while (lo < hi) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if (off[mid] < t) lo = mid + 1; else hi = mid;
+    }
+    return lo <= nseg && off[lo] == t;
+}
+template <int MODE>
+__device__ __forceinline__ bool keeps(const uint64_t* __restrict__ v, uint64_t t, uint64_t max_hash, const uint64_t* __restrict__ off, uint32_t nseg) {
+    const uint64_t x = v[t];
+    if (MODE == KEEP_HASH) return x != 0 && x <= max_hash;
+    if (t == 0 || v[t - 1] != x) return true;
+    return segment_starts_at(off, nseg, t); // equal to the element before it: stays only as the first of the next segment
+}
+__device__ __forceinline__ uint32_t lanes_below(uint64_t bal) { // set bits of bal below this lane
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
+}
+
+template <int MODE>
+__global__ __launch_bounds__(KEEP_T) void k_keep_count(const uint64_t* __restrict__ v, uint64_t n, uint64_t max_hash, const uint64_t* __restrict__ off,
+                                                       uint32_t nseg, uint32_t* __restrict__ block_count) {
+    __shared__ uint32_t wsum[KEEP_T / 64];
+    const uint64_t base = (uint64_t)blockIdx.x * KEEP_BLK;
+    uint32_t cnt = 0; // wave-uniform
+    for (int r = 0; r < KEEP_ROUNDS; ++r) {
+        const uint64_t t = base + (uint64_t)(r * KEEP_T) + threadIdx.x;
+        cnt += (uint32_t)__popcll(__ballot(t < n && keeps<MODE>(v, t, max_hash, off, nseg)));
+    }
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) block_count[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+}
+
+// pre[b] = block_count[0] + ... + block_count[b - 1] for b in [0, nblocks]; one workgroup of 1024, each thread a contiguous span
+__global__ __launch_bounds__(1024) void k_scan_blocks(const uint32_t* __restrict__ block_count, uint64_t nblocks, uint64_t* __restrict__ pre) {
+    __shared__ uint64_t part[1024];
+    const uint64_t per = (nblocks + 1023) / 1024;
+    const uint64_t b0 = min((uint64_t)threadIdx.x * per, nblocks), b1 = min(b0 + per, nblocks);
+    uint64_t sum = 0;
+    for (uint64_t b = b0; b < b1; ++b) sum += block_count[b];
+    part[threadIdx.x] = sum;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint64_t acc = 0;
+        for (int i = 0; i < 1024; ++i) { const uint64_t s = part[i]; part[i] = acc; acc += s; }
+        pre[nblocks] = acc;
+    }
+    __syncthreads();
+    uint64_t acc = part[threadIdx.x];
+    for (uint64_t b = b0; b < b1; ++b) { pre[b] = acc; acc += block_count[b]; }
+}
+
+// out_off[s] = elements kept before element off[s], for s in [0, nseg]: one wave per boundary counts the part of its block before it
+template <int MODE>
+__global__ __launch_bounds__(KEEP_T) void k_keep_bounds(const uint64_t* __restrict__ v, uint64_t n, uint64_t max_hash, const uint64_t* __restrict__ off,
+                                                        uint32_t nseg, const uint64_t* __restrict__ pre, uint64_t* __restrict__ out_off) {
+    const uint32_t s = blockIdx.x * (KEEP_T / 64) + (threadIdx.x >> 6);
+    if (s > nseg) return; // whole waves leave
+    const uint64_t p = min(off[s], n);
+    const uint64_t blk = p / KEEP_BLK; // <= number of blocks; pre has an entry for it
+    uint64_t cnt = 0;
+    for (uint64_t t0 = blk * KEEP_BLK; t0 < p; t0 += 64) { // at most 16 rounds
+        const uint64_t t = t0 + (threadIdx.x & 63);
+        cnt += (uint64_t)__popcll(__ballot(t < p && keeps<MODE>(v, t, max_hash, off, nseg)));
+    }
+    if ((threadIdx.x & 63) == 0) out_off[s] = pre[blk] + cnt;
+}
+
+template <int MODE>
+__global__ __launch_bounds__(KEEP_T) void k_keep_scatter(const uint64_t* __restrict__ v, uint64_t n, uint64_t max_hash, const uint64_t* __restrict__ off,
+                                                         uint32_t nseg, const uint64_t* __restrict__ pre, uint64_t* __restrict__ out, uint64_t out_cap) {
+    __shared__ uint32_t wcnt[KEEP_ROUNDS * (KEEP_T / 64)]; // kept by (round, wave), in element order
+    const uint64_t base = (uint64_t)blockIdx.x * KEEP_BLK;
+    const uint32_t wave = threadIdx.x >> 6;
+    uint64_t x[KEEP_ROUNDS];
+    uint32_t rank[KEEP_ROUNDS];
+    bool keep[KEEP_ROUNDS];
+    for (int r = 0; r < KEEP_ROUNDS; ++r) {
+        const uint64_t t = base + (uint64_t)(r * KEEP_T) + threadIdx.x;
+        keep[r] = t < n && keeps<MODE>(v, t, max_hash, off, nseg);
+        x[r] = t < n ? v[t] : 0;
+        const uint64_t bal = __ballot(keep[r]);
+        rank[r] = lanes_below(bal);
+        if ((threadIdx.x & 63) == 0) wcnt[r * (KEEP_T / 64) + wave] = (uint32_t)__popcll(bal);
+    }
+    __syncthreads();
+    const uint64_t first = pre[blockIdx.x];
+    uint32_t before = 0;
+    for (int r = 0; r < KEEP_ROUNDS; ++r)
+        for (uint32_t w = 0; w < KEEP_T / 64; ++w) {
+            if (w == wave && keep[r]) {
+                const uint64_t at = first + before + rank[r];
+                if (at < out_cap) out[at] = x[r]; // (always: out holds pre[nblocks] values)
+            }
+            before += wcnt[r * (KEEP_T / 64) + w];
+        }
+}
+
+template <int MODE>
+int keep_counts(rk_ctx* c, const uint64_t* v, uint64_t n, uint64_t max_hash, const uint64_t* d_off, uint32_t nseg, uint64_t* d_out_off) {
+    const uint64_t nblocks = (n + KEEP_BLK - 1) / KEEP_BLK;
+    if (nblocks > 0x7fffffffull) return fail(RK_ERR_LIMIT, "%llu hashes are more than one compaction takes", (unsigned long long)n);
+    RKCHK(c->w_sc_cnt.reserve((size_t)(nblocks + 1) * 4));
+    RKCHK(c->w_sc_pre.reserve((size_t)(nblocks + 1) * 8));
+    if (nblocks) hipLaunchKernelGGL(k_keep_count<MODE>, dim3((uint32_t)nblocks), dim3(KEEP_T), 0, c->st, v, n, max_hash, d_off, nseg, c->w_sc_cnt.as<uint32_t>());
+    hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(1024), 0, c->st, c->w_sc_cnt.as<uint32_t>(), nblocks, c->w_sc_pre.as<uint64_t>());
+    hipLaunchKernelGGL(k_keep_bounds<MODE>, dim3((nseg + 1 + KEEP_T / 64 - 1) / (KEEP_T / 64)), dim3(KEEP_T), 0, c->st, v, n, max_hash, d_off, nseg,
+                       c->w_sc_pre.as<uint64_t>(), d_out_off);
+    HIPCHK(hipGetLastError());
+    return RK_OK;
+}
+template <int MODE>
+int keep_scatter(rk_ctx* c, const uint64_t* v, uint64_t n, uint64_t max_hash, const uint64_t* d_off, uint32_t nseg, uint64_t* out, uint64_t out_cap) {
+    const uint64_t nblocks = (n + KEEP_BLK - 1) / KEEP_BLK;
+    if (!nblocks) return RK_OK;
+    hipLaunchKernelGGL(k_keep_scatter<MODE>, dim3((uint32_t)nblocks), dim3(KEEP_T), 0, c->st, v, n, max_hash, d_off, nseg, c->w_sc_pre.as<uint64_t>(), out, out_cap);
+    HIPCHK(hipGetLastError());
+    return RK_OK;
+}
+
+int grow_sink(ScaledSink& sink, size_t more) {
+    if (sink.len + more <= sink.cap) return RK_OK;
+    size_t cap = std::max(sink.len + more, sink.cap + sink.cap / 2) + 16;
+    uint64_t* p = (uint64_t*)realloc(sink.values, cap * 8);
+    if (!p) return fail(RK_ERR_NOMEM, "realloc of %zu scaled values", cap);
+    sink.values = p; sink.cap = cap;
+    return RK_OK;
+}
+
+} // namespace
+
+// One chunk of general_run: its hashes are in w_hashes, its segment offsets (seg[n + 1], also at w_segoff) say which belong to which
+// sequence.  Appends the scaled sketch of every sequence of the chunk to sink.values and sets sink.offsets[i0 + 1 ..].  Synchronises.
+int scaled_keep_chunk(rk_ctx* c, const std::vector<uint64_t>& seg, uint64_t nhashes, int64_t i0, ScaledSink& sink) {
+    const size_t cn = seg.size() - 1;
+    if (cn > 0x7ffffffeull) return fail(RK_ERR_LIMIT, "more than 2^31-2 sequences in one chunk");
+    const uint32_t nseg = (uint32_t)cn;
+    if (nhashes == 0) {
+        for (size_t q = 0; q < cn; ++q) sink.offsets[i0 + q + 1] = sink.len;
+        return RK_OK;
+    }
+    // 1. keep: 0 < h <= max_hash, compacted; koff1 = where each sequence's kept values begin
+    RKCHK(c->w_sc_off.reserve((cn + 1) * 8 * 2));
+    uint64_t* d_koff1 = c->w_sc_off.as<uint64_t>();
+    uint64_t* d_koff2 = d_koff1 + cn + 1;
+    const uint64_t* d_hashes = c->w_hashes.as<uint64_t>();
+    const uint64_t* d_seg = c->w_segoff.as<uint64_t>();
+    RKCHK(keep_counts<KEEP_HASH>(c, d_hashes, nhashes, sink.max_hash, d_seg, nseg, d_koff1));
+    std::vector<uint64_t> koff(cn + 1);
+    HIPCHK(hipMemcpyAsync(koff.data(), d_koff1, (cn + 1) * 8, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(hipStreamSynchronize(c->st));
+    const uint64_t total1 = koff[cn];
+    if (total1 > nhashes) return fail(RK_ERR_HIP, "scaled keep: %llu values kept of %llu hashes", (unsigned long long)total1, (unsigned long long)nhashes);
+    if (total1 == 0) {
+        for (size_t q = 0; q < cn; ++q) sink.offsets[i0 + q + 1] = sink.len;
+        return RK_OK;
+    }
+    RKCHK(c->w_sc_a.reserve((size_t)total1 * 8));
+    RKCHK(c->w_sc_b.reserve((size_t)total1 * 8));
+    uint64_t* d_a = c->w_sc_a.as<uint64_t>();
+    uint64_t* d_b = c->w_sc_b.as<uint64_t>();
+    RKCHK(keep_scatter<KEEP_HASH>(c, d_hashes, nhashes, sink.max_hash, d_seg, nseg, d_a, total1));
+    // 2. sort every sequence's kept values in place: up to SORT_MAX_P by the in-LDS sorter, one launch per power of two (the general
+    // path's size classes); longer ones by the whole-array radix sort, one call each.  0 or 1 values need no sort.
+    std::vector<std::vector<uint32_t>> classes(32);
+    std::vector<uint32_t> long_ids;
+    uint64_t longest = 0;
+    size_t nids = 0;
+    for (size_t q = 0; q < cn; ++q) {
+        const uint64_t m = koff[q + 1] - koff[q];
+        if (m < 2) continue;
+        if (m > (uint64_t)SORT_MAX_P) { long_ids.push_back((uint32_t)q); longest = std::max(longest, m); continue; }
+        int cls = 0; while ((64u << cls) < m) ++cls;
+        classes[cls].push_back((uint32_t)q); ++nids;
+    }
+    RKCHK(c->w_ids.reserve((nids + 1) * 4));
+    uint32_t* d_ids = c->w_ids.as<uint32_t>();
+    for (int cls = 0; cls < 32; ++cls) {
+        const std::vector<uint32_t>& ids = classes[cls];
+        if (ids.empty()) continue;
+        HIPCHK(hipMemcpyAsync(d_ids, ids.data(), ids.size() * 4, hipMemcpyHostToDevice, c->st));
+        SortArgs a{};
+        a.hashes = d_a; a.seg_off = d_koff1; a.seq_ids = d_ids; a.nlist = (uint32_t)ids.size(); a.P = 64u << cls; a.S = 1;
+        a.write_back = 1; a.slots = 1; a.filter_mode = FILTER_NONE;
+        HIPCHK(launch_sort_intersect(a, nullptr, c->pol, c->st));
+        d_ids += ids.size();
+    }
+    if (!long_ids.empty()) {
+        size_t tmp_bytes = 0;
+        HIPCHK(sort_u64_temp_bytes(longest, &tmp_bytes));
+        RKCHK(c->w_misc.reserve(tmp_bytes));
+        for (uint32_t q : long_ids) HIPCHK(launch_sort_u64(d_a + koff[q], koff[q + 1] - koff[q], c->w_misc.p, tmp_bytes, c->st));
+    }
+    // 3. drop repeats: the first of every value in its segment stays
+    RKCHK(keep_counts<KEEP_FIRST>(c, d_a, total1, 0, d_koff1, nseg, d_koff2));
+    RKCHK(keep_scatter<KEEP_FIRST>(c, d_a, total1, 0, d_koff1, nseg, d_b, total1));
+    std::vector<uint64_t> koff2(cn + 1);
+    HIPCHK(hipMemcpyAsync(koff2.data(), d_koff2, (cn + 1) * 8, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(hipStreamSynchronize(c->st)); // (the id vectors of step 2 live until here)
+    const uint64_t total2 = koff2[cn];
+    if (total2 > total1) return fail(RK_ERR_HIP, "scaled keep: %llu distinct values of %llu", (unsigned long long)total2, (unsigned long long)total1);
+    RKCHK(grow_sink(sink, (size_t)total2));
+    if (total2) HIPCHK(hipMemcpyAsync(sink.values + sink.len, d_b, (size_t)total2 * 8, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(hipStreamSynchronize(c->st));
+    for (size_t q = 0; q < cn; ++q) sink.offsets[i0 + q + 1] = sink.len + koff2[q + 1];
+    sink.len += (size_t)total2;
+    return RK_OK;
+}
+
+extern "C" int rk_sketch_scaled_batch(rk_ctx* c, const uint8_t* bases, const uint64_t* offsets, int64_t nseq, const int* ks, int nks,
+                                      uint64_t max_hash, uint64_t** values, uint64_t* sk_offsets) {
+    if (!c || !offsets || nseq < 0 || !values || !sk_offsets) return fail(RK_ERR_ARG, "bad arguments");
+    GeneralCfg cfg;
+    RKCHK(check_ks(ks, nks, &cfg.ks));
+    ScaledSink sink;
+    sink.max_hash = max_hash; sink.offsets = sk_offsets;
+    sink.values = (uint64_t*)malloc(8 * 16); sink.cap = 16;
+    if (!sink.values) return fail(RK_ERR_NOMEM, "malloc");
+    sk_offsets[0] = 0;
+    GeneralOut go; go.scaled = &sink;
+    const int r = general_run(c, bases, nullptr, offsets, nseq, cfg, go);
+    if (r != RK_OK) { free(sink.values); return r; }
+    *values = sink.values;
+    return RK_OK;
+}
+
+// ---- pairs ---------------------------------------------------------------------------------------------------------------
+namespace {
+
+constexpr int PAIRS_T = 256;
+
+// L lanes per pair, 64 / L pairs per wave.  The shorter row X is cut into L contiguous slices, lane `sub` owns X[s0, s1): it finds the
+// first element of the other row Y that is not below X[s0] (binary search, at most 32 halvings) and walks a two-pointer merge from
+// there until its slice or Y ends, counting equal values.  Every element of X belongs to exactly one lane, so a value at a slice
+// boundary is counted once.  Every step advances an index below its length; every read is at an index of a row clamped to
+// [0, nvalues]; compares are 64-bit unsigned.  Rows that are not ascending give meaningless counts and nothing worse.  The L partial
+// counts are added with shuffles inside the group of L lanes; no LDS, no atomics; the group's first lane stores the int32.
+template <int L>
+__global__ __launch_bounds__(PAIRS_T) void k_scaled_pairs(const uint64_t* __restrict__ av, const uint64_t* __restrict__ aoff, int na, uint64_t an,
+                                                          const uint64_t* __restrict__ bv, const uint64_t* __restrict__ boff, int nb, uint64_t bn,
+                                                          int32_t* __restrict__ out) {
+    const uint64_t npairs = (uint64_t)na * (uint64_t)nb;
+    const uint64_t p = (uint64_t)blockIdx.x * (PAIRS_T / L) + threadIdx.x / L;
+    const uint32_t sub = threadIdx.x % L;
+    const bool live = p < npairs; // lanes without a pair still take part in the shuffles
+    int cnt = 0;
+    if (live) {
+        const uint64_t i = p / (uint64_t)nb, j = p % (uint64_t)nb;
+        const uint64_t a0 = min(aoff[i], an), a1 = max(min(aoff[i + 1], an), a0);
+        const uint64_t b0 = min(boff[j], bn), b1 = max(min(boff[j + 1], bn), b0);
+        const uint32_t la = (uint32_t)min(a1 - a0, (uint64_t)0x7fffffffu), lb = (uint32_t)min(b1 - b0, (uint64_t)0x7fffffffu);
+        const bool a_short = la <= lb;
+        const uint64_t* __restrict__ X = a_short ? av + a0 : bv + b0;
+        const uint64_t* __restrict__ Y = a_short ? bv + b0 : av + a0;
+        const uint32_t lx = a_short ? la : lb, ly = a_short ? lb : la;
+        const uint32_t s0 = (uint32_t)((uint64_t)lx * sub / L), s1 = (uint32_t)((uint64_t)lx * (sub + 1) / L);
+        if (s0 < s1 && ly > 0) {
+            uint64_t x = X[s0];
+            uint32_t lo = 0, hi = ly; // first Y >= x
+            if (L > 1 && s0 > 0)
+                while (lo < hi) {
+                    const uint32_t mid = lo + ((hi - lo) >> 1);
+                    if (Y[mid] < x) lo = mid + 1; else hi = mid;
+                }
+            uint32_t ii = s0, jj = lo;
+            if (jj < ly) {
+                uint64_t y = Y[jj];
+                for (;;) {
+                    const bool ax = x <= y, ay = y <= x;
+                    cnt += (ax && ay) ? 1 : 0;
+                    ii += ax ? 1u : 0u;
+                    jj += ay ? 1u : 0u;
+                    if (ii >= s1 || jj >= ly) break;
+                    if (ax) x = X[ii];
+                    if (ay) y = Y[jj];
+                }
+            }
+        }
+    }
+    for (int d = L >> 1; d > 0; d >>= 1) cnt += __shfl_xor(cnt, d, 64);
+    if (live && sub == 0) out[p] = cnt;
+}
+
+// The lane rule of lanes = 0: a function of the mean length of the shorter side alone (measured at 800 and 5 000 values: DESIGN.md section 11).
+int auto_lanes(uint64_t an, int na, uint64_t bn, int nb) {
+    const uint64_t mean = std::min(an / (uint64_t)na, bn / (uint64_t)nb);
+    return mean < 16384 ? 1 : mean < 262144 ? 8 : 64;
+}
+
+int launch_scaled_pairs(const uint64_t* av, const uint64_t* aoff, int na, uint64_t an, const uint64_t* bv, const uint64_t* boff, int nb, uint64_t bn,
+                        int lanes, int32_t* out, hipStream_t st) {
+    const int L = lanes ? lanes : auto_lanes(an, na, bn, nb);
+    const uint64_t per = (uint64_t)(PAIRS_T / L), blocks = ((uint64_t)na * (uint64_t)nb + per - 1) / per;
+    if (blocks > 0x7fffffffull) return fail(RK_ERR_LIMIT, "%d x %d sketches are more pairs than one launch takes", na, nb);
+    const dim3 grid((uint32_t)blocks), block(PAIRS_T);
+    if (L == 1) hipLaunchKernelGGL(k_scaled_pairs<1>, grid, block, 0, st, av, aoff, na, an, bv, boff, nb, bn, out);
+    else if (L == 8) hipLaunchKernelGGL(k_scaled_pairs<8>, grid, block, 0, st, av, aoff, na, an, bv, boff, nb, bn, out);
+    else hipLaunchKernelGGL(k_scaled_pairs<64>, grid, block, 0, st, av, aoff, na, an, bv, boff, nb, bn, out);
+    HIPCHK(hipGetLastError());
+    return RK_OK;
+}
+
+int check_pairs_shape(int na, int nb, int lanes) {
+    if (na < 1 || nb < 1) return fail(RK_ERR_ARG, "need at least one sketch on each side, got %d x %d", na, nb);
+    if (lanes != 0 && lanes != 1 && lanes != 8 && lanes != 64) return fail(RK_ERR_ARG, "lanes %d is none of 0, 1, 8, 64", lanes);
+    return RK_OK;
+}
+int check_csr(const uint64_t* off, int n, const char* side) {
+    for (int i = 0; i < n; ++i) {
+        if (off[i + 1] < off[i]) return fail(RK_ERR_ARG, "offsets of %s decrease at sketch %d", side, i);
+        if (off[i + 1] - off[i] > 0x7fffffffull) return fail(RK_ERR_ARG, "sketch %d of %s holds 2^31 values or more", i, side);
+    }
+    return RK_OK;
+}
+
+} // namespace
+
+extern "C" int rk_compare_scaled_device(rk_ctx* c, const void* d_a_values, const void* d_a_offsets, int na, uint64_t a_nvalues,
+                                        const void* d_b_values, const void* d_b_offsets, int nb, uint64_t b_nvalues, int lanes,
+                                        void* d_shared, void* hip_stream) {
+    if (!c || !d_a_offsets || !d_b_offsets || !d_shared || (!d_a_values && a_nvalues) || (!d_b_values && b_nvalues)) return fail(RK_ERR_ARG, "bad arguments");
+    RKCHK(check_pairs_shape(na, nb, lanes));
+    RKCHK(set_dev(c));
+    return launch_scaled_pairs((const uint64_t*)d_a_values, (const uint64_t*)d_a_offsets, na, a_nvalues, (const uint64_t*)d_b_values,
+                               (const uint64_t*)d_b_offsets, nb, b_nvalues, lanes, (int32_t*)d_shared, (hipStream_t)hip_stream);
+}
+
+extern "C" int rk_compare_scaled(rk_ctx* c, const uint64_t* a_values, const uint64_t* a_offsets, int na, const uint64_t* b_values,
+                                 const uint64_t* b_offsets, int nb, int lanes, int32_t* shared) {
+    if (!c || !a_offsets || !b_offsets || !shared) return fail(RK_ERR_ARG, "bad arguments");
+    RKCHK(check_pairs_shape(na, nb, lanes));
+    RKCHK(check_csr(a_offsets, na, "a"));
+    RKCHK(check_csr(b_offsets, nb, "b"));
+    const uint64_t an = a_offsets[na], bn = b_offsets[nb];
+    if ((an && !a_values) || (bn && !b_values)) return fail(RK_ERR_ARG, "bad arguments");
+    RKCHK(set_dev(c));
+    std::lock_guard<std::mutex> lk(c->general_mu); // the general path's work buffers serve here too
+    const bool self = a_values == b_values && a_offsets == b_offsets && na == nb;
+    RKCHK(c->w_sk.reserve((size_t)(an + (self ? 0 : bn)) * 8 + 8));
+    RKCHK(c->w_sc_off.reserve(((size_t)na + 1 + (self ? 0 : (size_t)nb + 1)) * 8));
+    uint64_t* d_av = c->w_sk.as<uint64_t>();
+    uint64_t* d_bv = self ? d_av : d_av + an;
+    uint64_t* d_ao = c->w_sc_off.as<uint64_t>();
+    uint64_t* d_bo = self ? d_ao : d_ao + na + 1;
+    if (an) HIPCHK(hipMemcpyAsync(d_av, a_values, (size_t)an * 8, hipMemcpyHostToDevice, c->st));
+    HIPCHK(hipMemcpyAsync(d_ao, a_offsets, ((size_t)na + 1) * 8, hipMemcpyHostToDevice, c->st));
+    if (!self) {
+        if (bn) HIPCHK(hipMemcpyAsync(d_bv, b_values, (size_t)bn * 8, hipMemcpyHostToDevice, c->st));
+        HIPCHK(hipMemcpyAsync(d_bo, b_offsets, ((size_t)nb + 1) * 8, hipMemcpyHostToDevice, c->st));
+    }
+    const int L = lanes ? lanes : auto_lanes(an, na, bn, nb); // one choice for all row blocks
+    // the rows of the answer leave in blocks of at most 64 MB (one row when nb alone is wider than that)
+    const size_t row_bytes = (size_t)nb * 4;
+    size_t rows = std::max<size_t>(1, ((size_t)64 << 20) / row_bytes);
+    if (rows > (size_t)na) rows = (size_t)na;
+    RKCHK(c->w_out.reserve(rows * row_bytes));
+    for (size_t r0 = 0; r0 < (size_t)na; r0 += rows) {
+        const int n = (int)std::min(rows, (size_t)na - r0);
+        RKCHK(launch_scaled_pairs(d_av, d_ao + r0, n, an, d_bv, d_bo, nb, bn, L, c->w_out.as<int32_t>(), c->st));
+        HIPCHK(hipMemcpyAsync(shared + r0 * (size_t)nb, c->w_out.p, (size_t)n * row_bytes, hipMemcpyDeviceToHost, c->st));
+        HIPCHK(hipStreamSynchronize(c->st));
+    }
+    return RK_OK;
+}

@@ -353,6 +353,7 @@ int main_stream(int argc, char** argv) {
     LoadedSketches pre;
     if (pre_refs) {
         if (!load_sketch_json(pre_refs, pre)) { fprintf(stderr, "rkmh: cannot load sketches from %s\n", pre_refs); exit(1); }
+        refuse_scaled(pre, pre_refs, "-R");
         // sketches hashed under another policy would meet read hashes they can never equal: refused, not classified against
         rk_policy theirs;
         rk_default_policy(&theirs);

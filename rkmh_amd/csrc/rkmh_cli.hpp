@@ -58,7 +58,15 @@ std::string policy_text(const rk_policy& p);
     "                          is the smaller string, dedup=distinct sketches distinct values: the rules of Mash and sourmash;\n" \
     "                          `sourmash` = mash,canon=lexmin,dedup=distinct.  RKMH_POLICY: the same, read first\n"
 void print_help();
-struct LoadedSketches { std::vector<std::string> names; std::vector<uint64_t> sk; std::vector<int32_t> lens; std::vector<int> ks; int S = 0; std::string policy; };
+struct LoadedSketches {
+    std::vector<std::string> names; std::vector<uint64_t> sk; std::vector<int32_t> lens; std::vector<int> ks; int S = 0; std::string policy;
+    // a file of scaled sketches (`rkmh sketch --scaled`): scaled > 0, S = 0, sk holds the values of all sketches one after the other and
+    // sketch i is sk[off[i], off[i + 1]).  Only `dist` compares such sketches: every other reader refuses them (refuse_scaled).
+    uint64_t scaled = 0;
+    std::vector<uint64_t> off;
+    std::string err; // why load_sketch_json returned false, where it knows more than "cannot load"
+};
+void refuse_scaled(const LoadedSketches& L, const char* path, const char* command); // exits when L holds scaled sketches
 bool load_sketch_json(const char* path, LoadedSketches& L, int max_S = 0); // max_S > 0: a larger "length" is refused before anything of that size is allocated
 
 // ---- the sub-commands

@@ -6,6 +6,7 @@
 #include <set>
 
 #include "rkmh_cli.hpp"
+#include <cerrno>
 
 // The hashing policy of this run: the build's defaults, then RKMH_POLICY, then --hash-policy (rk_policy_parse: presets `default`
 // `mash` and `sourmash`, or fold= / windows= / zero= / mask= / freqmax= / canon= / dedup= / seed=).  The arithmetic behind these switches is mkmh's, which the
@@ -29,8 +30,8 @@ void print_help() {
             "  call                call SNPs / 1-bp deletions from k-mer depth along a reference\n"
             "  hash                print the k-mer hashes of every sequence\n"
             "  hpv16               HPV type and HPV16 lineage / sublineage k-mer matches of every read\n"
-            "  sketch              write MinHash sketches as JSON (load them with stream -R)\n"
-            "  dist                Mash distance between every query sketch and every reference sketch\n"
+            "  sketch              write MinHash sketches as JSON (load them with stream -R); --scaled: scaled (FracMinHash) sketches for dist\n"
+            "  dist                Mash distance between every query sketch and every reference sketch; --scaled: Jaccard and containment of scaled sketches\n"
             "  pack                write reads as a packed file (2 bits per base + names): stream|filter -F <file> classifies it without parsing\n"
             "Run a command without options for its help text.\n");
 }
@@ -264,9 +265,11 @@ static void json_escape(std::string& out, const char* s) {
 }
 static void help_sketch() {
     fprintf(stderr,
-            "rkmh sketch -f <seqs.fa|fq> [-k <k>]... [-s <sketch>] [-g] [-o <out.json>] [--kmer-cache <file>]\n"
+            "rkmh sketch -f <seqs.fa|fq> [-k <k>]... [-s <sketch> | --scaled <n>] [-g] [-o <out.json>] [--kmer-cache <file>]\n"
             "  writes a JSON array with one MinHash sketch per sequence (schema of the reference's dump_hash_json);\n"
             "  -g: one sketch per input FILE (named by its path; no k-mer spans two of its records), as Mash sketches an assembly;\n"
+            "  --scaled <n>: scaled (FracMinHash) sketches instead of bottom-s ones: every distinct hash up to (2^64 - 1) / n, so the size\n"
+            "  grows with the sequence; objects gain \"scaled\" and \"maxHash\"; such files serve `rkmh dist` only\n"
             "  `rkmh stream -R <out.json>` loads it instead of sketching references again;\n"
             "  --kmer-cache <file>: also enumerates the k-mers behind these sketches (k 8 .. 18) into <file>, which\n"
             "  `rkmh stream -R <out.json> --kmer-cache <file>` then loads instead of enumerating them at every start\n"
@@ -308,28 +311,82 @@ static void sketch_files(rk_ctx* ctx, const std::vector<const char*>& files, con
         rk_seqset_free(&s);
     }
 }
+// --scaled: a number of at least 1, nothing else
+static bool parse_scaled(const char* text, uint64_t& scaled) {
+    if (!text || !isdigit((unsigned char)*text)) return false;
+    char* e = nullptr;
+    errno = 0;
+    const unsigned long long v = strtoull(text, &e, 10);
+    if (errno != 0 || *e != 0 || v == 0) return false;
+    scaled = (uint64_t)v;
+    return true;
+}
+// Scaled sketches as `sketch --scaled` writes and `dist --scaled` compares them: CSR, sketch i = values[off[i], off[i + 1]).  One per
+// sequence of the files -- or, whole_files (-g), one per FILE: its records are sketched one by one and united (rk_merge_scaled).
+struct ScaledSet { std::vector<std::string> names; std::vector<uint64_t> seq_len; std::vector<uint64_t> values; std::vector<uint64_t> off = std::vector<uint64_t>(1, 0); };
+static void sketch_files_scaled(rk_ctx* ctx, const std::vector<const char*>& files, const std::vector<int>& ks, uint64_t max_hash, bool whole_files, ScaledSet& out) {
+    auto sketch_records = [&](const rk_seqset& s, uint64_t** v, std::vector<uint64_t>& off) {
+        off.assign((size_t)s.nseq + 1, 0);
+        CK(rk_sketch_scaled_batch(ctx, s.bases, s.offsets, s.nseq, ks.data(), (int)ks.size(), max_hash, v, off.data()));
+    };
+    std::vector<uint64_t> off;
+    if (!whole_files) {
+        rk_seqset s;
+        CK(rk_parse_files(files.data(), (int)files.size(), &s));
+        uint64_t* v = nullptr;
+        sketch_records(s, &v, off);
+        for (int64_t i = 0; i < s.nseq; ++i) {
+            out.names.push_back(s.names + s.name_offsets[i]);
+            out.seq_len.push_back(s.offsets[i + 1] - s.offsets[i]);
+            out.values.insert(out.values.end(), v + off[(size_t)i], v + off[(size_t)i + 1]);
+            out.off.push_back(out.values.size());
+        }
+        rk_free(v);
+        rk_seqset_free(&s);
+        return;
+    }
+    for (size_t f = 0; f < files.size(); ++f) {
+        rk_seqset s;
+        CK(rk_parse_files(&files[f], 1, &s));
+        if (s.nseq > 0x7fffffffll) { fprintf(stderr, "rkmh: %s holds more than 2^31-1 records\n", files[f]); exit(1); }
+        uint64_t* v = nullptr;
+        sketch_records(s, &v, off);
+        uint64_t* u = nullptr;
+        uint64_t nu = 0;
+        CK(rk_merge_scaled(v, off.data(), (int)s.nseq, max_hash, &u, &nu));
+        out.names.push_back(files[f]);
+        out.seq_len.push_back(s.nseq ? s.offsets[s.nseq] - s.offsets[0] : 0);
+        out.values.insert(out.values.end(), u, u + nu);
+        out.off.push_back(out.values.size());
+        rk_free(u);
+        rk_free(v);
+        rk_seqset_free(&s);
+    }
+}
 int main_sketch(int argc, char** argv) {
     std::vector<const char*> files;
     std::vector<int> ks;
     int S = 1000, device = 0;
     const char* outp = nullptr;
     const char* kmer_cache = nullptr;
-    bool whole_files = false;
+    bool whole_files = false, s_given = false, scaled_given = false, scaled_ok = true;
+    uint64_t scaled = 0;
     if (argc <= 2) { help_sketch(); exit(1); }
     optind = 2;
     int c;
     static struct option long_options[] = {{"help", no_argument, 0, 'h'}, {"kmer", required_argument, 0, 'k'},
         {"fasta", required_argument, 0, 'f'}, {"reference", required_argument, 0, 'r'}, {"sketch-size", required_argument, 0, 's'},
         {"output", required_argument, 0, 'o'}, {"device", required_argument, 0, 1000}, {"kmer-cache", required_argument, 0, 1003},
-        {"whole-files", no_argument, 0, 'g'}, HASH_POLICY_OPTION, {0, 0, 0, 0}};
+        {"whole-files", no_argument, 0, 'g'}, {"scaled", required_argument, 0, 1005}, HASH_POLICY_OPTION, {0, 0, 0, 0}};
     while ((c = getopt_long(argc, argv, "hgk:f:r:s:o:t:", long_options, nullptr)) != -1) {
         switch (c) {
             case 1004: policy_apply(optarg, "--hash-policy"); break;
+            case 1005: scaled_given = true; scaled_ok = parse_scaled(optarg, scaled); break;
             case 1003: kmer_cache = optarg; break;
             case 'g': whole_files = true; break;
             case 'f': case 'r': files.push_back(optarg); break;
             case 'k': ks.push_back(atoi(optarg)); break;
-            case 's': S = atoi(optarg); break;
+            case 's': S = atoi(optarg); s_given = true; break;
             case 'o': outp = optarg; break;
             case 't': break;
             case 1000: device = atoi(optarg); break;
@@ -338,9 +395,48 @@ int main_sketch(int argc, char** argv) {
     }
     if (ks.empty()) { fprintf(stderr, "No kmer size(s) provided. Will use a default kmer size of 16.\n"); ks.push_back(16); }
     if (files.empty()) { fprintf(stderr, "rkmh: -f <file> is required\n"); exit(1); }
-    if (whole_files && (S < 1 || S > RK_MAX_SKETCH)) { fprintf(stderr, "rkmh sketch: -g needs a sketch size of 1 .. %d\n", RK_MAX_SKETCH); exit(1); }
+    if (scaled_given) {
+        if (!scaled_ok) { fprintf(stderr, "rkmh sketch: --scaled takes a number of at least 1\n"); exit(1); }
+        if (s_given) { fprintf(stderr, "rkmh sketch: --scaled and -s are two kinds of sketch; give one of them\n"); exit(1); }
+        if (kmer_cache) { fprintf(stderr, "rkmh sketch: --kmer-cache serves `stream -R`; scaled sketches serve `rkmh dist` only\n"); exit(1); }
+    }
+    if (!scaled_given && whole_files && (S < 1 || S > RK_MAX_SKETCH)) { fprintf(stderr, "rkmh sketch: -g needs a sketch size of 1 .. %d\n", RK_MAX_SKETCH); exit(1); }
     rk_ctx* ctx = nullptr;
     CK(rk_ctx_create(device, &g_policy, &ctx));
+    if (scaled_given) {
+        uint64_t max_hash = 0;
+        CK(rk_scaled_max_hash(scaled, &max_hash));
+        ScaledSet set;
+        sketch_files_scaled(ctx, files, ks, max_hash, whole_files, set);
+        FILE* fo = outp ? fopen(outp, "w") : stdout;
+        if (!fo) { fprintf(stderr, "rkmh: cannot write %s\n", outp); exit(1); }
+        std::string kstr;
+        for (size_t i = 0; i < ks.size(); ++i) { kstr += std::to_string(ks[i]); if (i + 1 < ks.size()) kstr += ' '; }
+        const std::string pol_text = policy_text(g_policy);
+        std::string o = "[";
+        char num[32];
+        // today's keys in their alphabetical places, plus "maxHash" and "scaled"; "length" is the sketch's own number of hashes
+        for (size_t i = 0; i < set.names.size(); ++i) {
+            std::string name;
+            json_escape(name, set.names[i].c_str());
+            if (i) o += ',';
+            o += "{\"alphabet\":\"ATGC\",\"canonical\":\"true\",\"hashBits\":64,\"hashPolicy\":\"" + pol_text + "\",\"hashSeed\":" + std::to_string(g_policy.seed) +
+                 ",\"hashType\":\"MurmurHash3_x64_128\",\"kmer\":\"" + kstr + "\",\"maxHash\":" + std::to_string(max_hash) +
+                 ",\"name\":\"" + name + "\",\"preserveCase\":\"false\",\"scaled\":" + std::to_string(scaled) + ",\"seqLen\":" + std::to_string(set.seq_len[i]) +
+                 ",\"sketches\":{\"comment\":\"\",\"hashes\":[";
+            for (uint64_t j = set.off[i]; j < set.off[i + 1]; ++j) {
+                int n = snprintf(num, sizeof num, j > set.off[i] ? ",%llu" : "%llu", (unsigned long long)set.values[(size_t)j]);
+                o.append(num, (size_t)n);
+            }
+            o += "],\"length\":" + std::to_string(set.off[i + 1] - set.off[i]) + ",\"name\":\"" + name + "\"}}";
+            if (o.size() > (1u << 22)) { fwrite(o.data(), 1, o.size(), fo); o.clear(); }
+        }
+        o += "]\n";
+        fwrite(o.data(), 1, o.size(), fo);
+        if (fo != stdout) fclose(fo);
+        rk_ctx_destroy(ctx);
+        return 0;
+    }
     SketchSet set;
     sketch_files(ctx, files, ks, S, whole_files, set);
     const std::vector<uint64_t>& sk = set.sk;
@@ -427,13 +523,27 @@ bool load_sketch_json(const char* path, LoadedSketches& L, int max_S) {
             if (json_find(t, pos, end, "hashPolicy", v)) pol = json_string_at(t, v);
             if (L.names.empty()) L.policy = pol; else if (pol != L.policy) return false;
         }
-        if (!json_find(t, pos, end, "name", v)) return false;
-        L.names.push_back(json_string_at(t, v));
         size_t sp;
         if (!json_find(t, pos, end, "sketches", sp)) return false;
+        // "scaled" / "maxHash" (`sketch --scaled`): all objects of a file or none, and all the same
+        uint64_t scaled = 0, max_hash = 0;
+        if (json_find(t, pos, sp, "scaled", v)) {
+            scaled = strtoull(t.c_str() + v, nullptr, 10);
+            uint64_t expect = 0;
+            if (scaled == 0 || !json_find(t, pos, sp, "maxHash", v) || rk_scaled_max_hash(scaled, &expect) != RK_OK ||
+                (max_hash = strtoull(t.c_str() + v, nullptr, 10)) != expect) {
+                L.err = "sketch " + std::to_string(all.size()) + ": \"scaled\" must be at least 1 and \"maxHash\" = (2^64 - 1) / scaled";
+                return false;
+            }
+        }
+        if (!all.empty() && scaled != L.scaled) { L.err = "its sketches disagree in scaled"; return false; }
+        L.scaled = scaled;
+        if (!json_find(t, pos, end, "name", v)) return false;
+        L.names.push_back(json_string_at(t, v));
         if (!json_find(t, sp, end, "length", v)) return false;
         int S = (int)strtol(t.c_str() + v, nullptr, 10);
-        if (L.S == 0) L.S = S; else if (S != L.S) return false;
+        if (scaled) S = 0; // (a scaled sketch's "length" is its own number of hashes)
+        else if (L.S == 0) L.S = S; else if (S != L.S) return false;
         if (!json_find(t, sp, end, "hashes", v)) return false;
         std::vector<uint64_t> h;
         const char* q = t.c_str() + v;
@@ -447,8 +557,24 @@ bool load_sketch_json(const char* path, LoadedSketches& L, int max_S) {
             if (e == q) return false;
             q = e;
         }
+        if (scaled)
+            for (size_t j = 0; j < h.size(); ++j)
+                if (h[j] == 0 || h[j] > max_hash || (j && h[j] <= h[j - 1])) {
+                    L.err = "sketch " + std::to_string(all.size()) + ": the hashes of a scaled sketch are ascending, distinct and at most its maxHash";
+                    return false;
+                }
         all.push_back(h);
         pos = end;
+    }
+    if (!all.empty() && L.scaled) {
+        L.off.assign(1, 0);
+        for (const auto& h : all) {
+            if (h.size() > 0x7fffffffull) return false;
+            L.lens.push_back((int32_t)h.size());
+            L.sk.insert(L.sk.end(), h.begin(), h.end());
+            L.off.push_back(L.sk.size());
+        }
+        return true;
     }
     if (all.empty() || L.S <= 0) return false;
     if (max_S > 0 && L.S > max_S) return false; // (before the rows are allocated: L.S tells the caller why)
@@ -461,35 +587,48 @@ bool load_sketch_json(const char* path, LoadedSketches& L, int max_S) {
     return true;
 }
 
+void refuse_scaled(const LoadedSketches& L, const char* path, const char* command) {
+    if (!L.scaled) return;
+    fprintf(stderr, "rkmh: %s holds scaled sketches (scaled = %llu); scaled sketches serve `rkmh dist`, not %s, which needs bottom-s sketches\n", path,
+            (unsigned long long)L.scaled, command);
+    exit(1);
+}
+
 // ------------------------------------------------------------------------------------------------------------------------
 // dist: the Mash distance of every (query, reference) pair of sketches -- `mash dist`, which the reference has no command for.  The
 // four counts of a pair come from one launch over all pairs (rk_compare_sketches); the floating point is rk_mash_distance's.
 // Everything that can be refused is refused before a context exists: nothing is printed by a run that fails.
 static void help_dist() {
     fprintf(stderr,
-            "rkmh dist (-r <refs.fa> ... | -R <refs.json>) [-f <queries.fa|fq> ... | -Q <queries.json>] [-k <k>] [-s <sketch>] [-g] [-d <maxdist>]\n"
+            "rkmh dist (-r <refs.fa> ... | -R <refs.json>) [-f <queries.fa|fq> ... | -Q <queries.json>] [-k <k>] [-s <sketch> | --scaled <n>] [-g] [-d <maxdist>]\n"
             "  prints one line per (query, reference) pair, query by query: reference, query, Mash distance, common/denom of the merged\n"
             "  bottom-s sketch, shared hashes (the multiset intersection `stream` counts); without -f / -Q every reference is compared\n"
             "  with every reference\n"
             "  -R / -Q: sketches written by `rkmh sketch` (their k-mer size, sketch size and hashing policy must agree with each other and the run)\n"
+            "  --scaled <n>: compare scaled (FracMinHash) sketches, every distinct hash up to (2^64 - 1) / n: -r / -f files are sketched at n,\n"
+            "  -R / -Q files hold sketches of `rkmh sketch --scaled <m>`, m <= n, and are cut down to n (without --scaled: to the largest m\n"
+            "  among them); a line is then: reference, query, distance from shared/union, shared/union, shared/|query|, shared/|reference|\n"
+            "  (the last two: how much of the query is contained in the reference, and the reverse); not with -s\n"
             "  -g: one sketch per input FILE, as Mash sketches an assembly;  -d <x>: only pairs at distance <= x;  --device <id>: GPU to use\n" HASH_POLICY_HELP);
 }
 int main_dist(int argc, char** argv) {
     std::vector<const char*> ref_files, query_files, ref_json, query_json;
     std::vector<int> ks;
     int S = 0, device = 0;
-    bool whole_files = false;
+    bool whole_files = false, scaled_given = false, scaled_ok = true;
+    uint64_t scaled = 0; // --scaled, or the largest "scaled" of the files loaded
     double max_dist = 2.0;
     if (argc <= 2) { help_dist(); exit(1); }
     static struct option long_options[] = {{"help", no_argument, 0, 'h'}, {"kmer", required_argument, 0, 'k'}, {"fasta", required_argument, 0, 'f'},
         {"reference", required_argument, 0, 'r'}, {"pre-references", required_argument, 0, 'R'}, {"pre-queries", required_argument, 0, 'Q'},
         {"sketch-size", required_argument, 0, 's'}, {"whole-files", no_argument, 0, 'g'}, {"max-dist", required_argument, 0, 'd'},
-        {"threads", required_argument, 0, 't'}, {"device", required_argument, 0, 1000}, HASH_POLICY_OPTION, {0, 0, 0, 0}};
+        {"threads", required_argument, 0, 't'}, {"device", required_argument, 0, 1000}, {"scaled", required_argument, 0, 1005}, HASH_POLICY_OPTION, {0, 0, 0, 0}};
     optind = 2;
     int c;
     while ((c = getopt_long(argc, argv, "hgk:f:r:R:Q:s:d:t:", long_options, nullptr)) != -1) {
         switch (c) {
             case 1004: policy_apply(optarg, "--hash-policy"); break;
+            case 1005: scaled_given = true; scaled_ok = parse_scaled(optarg, scaled); break;
             case 'r': ref_files.push_back(optarg); break;
             case 'f': query_files.push_back(optarg); break;
             case 'R': ref_json.push_back(optarg); break;
@@ -509,6 +648,8 @@ int main_dist(int argc, char** argv) {
         for (int k : ks) given += " " + std::to_string(k);
         refuse("a distance needs one k-mer size; sizes provided:" + given);
     }
+    if (scaled_given && !scaled_ok) refuse("--scaled takes a number of at least 1");
+    if (scaled_given && S != 0) refuse("--scaled and -s are two kinds of sketch; give one of them");
     if (S != 0 && (S < 1 || S > RK_MAX_SKETCH)) refuse("sketch size outside 1 .. " + std::to_string(RK_MAX_SKETCH));
     if (ref_files.empty() == ref_json.empty()) refuse("references come from -r <fasta> ... or from -R <sketches.json> ..., one of the two");
     if (!query_files.empty() && !query_json.empty()) refuse("queries come from -f <fasta|fastq> ... or from -Q <sketches.json> ..., not both");
@@ -516,10 +657,17 @@ int main_dist(int argc, char** argv) {
     const bool self = query_files.empty() && query_json.empty();
     // sketch files: each agrees in itself (load_sketch_json), with the others, with -k / -s where given, and with the run's policy
     int k = ks.empty() ? 0 : ks[0];
-    auto load = [&](const std::vector<const char*>& paths, SketchSet& into) {
+    // scaled files: kept as loaded (each at its own "scaled") until the run's value is known, then cut down to it
+    struct ScaledFile { std::string path; LoadedSketches L; };
+    std::vector<ScaledFile> sc_refs, sc_queries;
+    bool any_bottom = false, any_scaled = false;
+    uint64_t largest_scaled = 0;
+    const int s_option = S;
+    auto load = [&](const std::vector<const char*>& paths, SketchSet& into, std::vector<ScaledFile>& sc_into) {
         for (const char* path : paths) {
             LoadedSketches L;
             if (!load_sketch_json(path, L, RK_MAX_SKETCH)) {
+                if (!L.err.empty()) refuse(std::string(path) + ": " + L.err);
                 if (L.S > RK_MAX_SKETCH) refuse(std::string(path) + ": sketch size outside 1 .. " + std::to_string(RK_MAX_SKETCH));
                 refuse(std::string("cannot load sketches from ") + path + " (unreadable, or its sketches disagree in kmer, hashPolicy or length)");
             }
@@ -530,6 +678,18 @@ int main_dist(int argc, char** argv) {
                 refuse(std::string(path) + " holds sketches hashed with " + policy_text(theirs) + ", this run hashes with " + policy_text(g_policy) + ": pass --hash-policy " + policy_text(theirs));
             if (L.ks.size() != 1) refuse(std::string(path) + " holds sketches of " + std::to_string(L.ks.size()) + " k-mer sizes; a distance needs one");
             if (k != 0 && L.ks[0] != k) refuse(std::string(path) + " holds sketches of k = " + std::to_string(L.ks[0]) + ", the others (or -k) say " + std::to_string(k));
+            (L.scaled ? any_scaled : any_bottom) = true;
+            if (any_scaled && any_bottom) refuse(std::string(path) + ": scaled and bottom-s sketches cannot be compared with each other");
+            if (L.scaled) {
+                if (s_option != 0) refuse(std::string(path) + " holds scaled sketches (scaled = " + std::to_string(L.scaled) + "); -s is for bottom-s sketches");
+                if (scaled_given && L.scaled > scaled)
+                    refuse(std::string(path) + " holds sketches of scaled = " + std::to_string(L.scaled) + ": they cannot be made finer, --scaled must be at least that");
+                largest_scaled = std::max(largest_scaled, L.scaled);
+                k = L.ks[0];
+                sc_into.push_back(ScaledFile{path, std::move(L)});
+                continue;
+            }
+            if (scaled_given) refuse(std::string(path) + " holds bottom-s sketches; --scaled compares scaled ones (rkmh sketch --scaled)");
             if (S != 0 && L.S != S) refuse(std::string(path) + " holds sketches of size " + std::to_string(L.S) + ", the others (or -s) say " + std::to_string(S));
             k = L.ks[0]; S = L.S;
             into.names.insert(into.names.end(), L.names.begin(), L.names.end());
@@ -538,10 +698,60 @@ int main_dist(int argc, char** argv) {
         }
     };
     SketchSet refs, queries;
-    load(ref_json, refs);
-    load(query_json, queries);
+    load(ref_json, refs, sc_refs);
+    load(query_json, queries, sc_queries);
     if (k == 0) { fprintf(stderr, "No kmer size(s) provided. Will use a default kmer size of 16.\n"); k = 16; }
     if (k < 1 || k > RK_MAX_K) refuse("k-mer size outside 1 .. " + std::to_string(RK_MAX_K));
+    if (scaled_given || any_scaled) {
+        if (!scaled_given) scaled = largest_scaled;
+        uint64_t max_hash = 0;
+        CK(rk_scaled_max_hash(scaled, &max_hash));
+        ScaledSet sr, sq;
+        auto cut = [&](const std::vector<ScaledFile>& from, ScaledSet& into) { // a prefix of every row: rows ascend, max_hash is monotone
+            for (const ScaledFile& f : from)
+                for (size_t i = 0; i < f.L.names.size(); ++i) {
+                    const uint64_t* b = f.L.sk.data() + f.L.off[i];
+                    const uint64_t* e = std::upper_bound(b, f.L.sk.data() + f.L.off[i + 1], max_hash);
+                    into.names.push_back(f.L.names[i]);
+                    into.values.insert(into.values.end(), b, e);
+                    into.off.push_back(into.values.size());
+                }
+        };
+        cut(sc_refs, sr);
+        cut(sc_queries, sq);
+        // sides that come from sketch files alone are known now: refused before a context exists, like everything above
+        if (ref_files.empty() && sr.names.empty()) refuse("no reference sketches");
+        if (!self && query_files.empty() && sq.names.empty()) refuse("no query sketches");
+        if (sr.names.size() > 0x7fffffffull || sq.names.size() > 0x7fffffffull) refuse("more than 2^31-1 sketches on one side");
+        rk_ctx* sctx = nullptr;
+        CK(rk_ctx_create(device, &g_policy, &sctx));
+        const std::vector<int> kk(1, k);
+        if (!ref_files.empty()) sketch_files_scaled(sctx, ref_files, kk, max_hash, whole_files, sr);
+        if (!query_files.empty()) sketch_files_scaled(sctx, query_files, kk, max_hash, whole_files, sq);
+        const ScaledSet& q = self ? sr : sq;
+        const size_t nq = q.names.size(), nr = sr.names.size();
+        if (nr == 0 || nq == 0) { fprintf(stderr, "rkmh dist: no %s sketches\n", nr == 0 ? "reference" : "query"); exit(1); }
+        if (nq > 0x7fffffffull || nr > 0x7fffffffull) refuse("more than 2^31-1 sketches on one side");
+        std::vector<int32_t> shared(nq * nr);
+        CK(rk_compare_scaled(sctx, q.values.data(), q.off.data(), (int)nq, sr.values.data(), sr.off.data(), (int)nr, 0, shared.data()));
+        std::string o;
+        char num[160];
+        for (size_t i = 0; i < nq; ++i)
+            for (size_t j = 0; j < nr; ++j) {
+                const long long sh = shared[i * nr + j], lq = (long long)(q.off[i + 1] - q.off[i]), lr = (long long)(sr.off[j + 1] - sr.off[j]);
+                double jac = 0, d = 1;
+                CK(rk_scaled_distance(sh, lq, lr, k, &jac, &d));
+                if (d > max_dist) continue;
+                o += sr.names[j]; o += '\t'; o += q.names[i];
+                const int n = snprintf(num, sizeof num, "\t%.6g\t%lld/%lld\t%lld/%lld\t%lld/%lld\n", d, sh, lq + lr - sh, sh, lq, sh, lr);
+                o.append(num, (size_t)n);
+                if (o.size() > (1u << 22)) { fwrite(o.data(), 1, o.size(), stdout); o.clear(); }
+            }
+        fwrite(o.data(), 1, o.size(), stdout);
+        fflush(stdout);
+        rk_ctx_destroy(sctx);
+        return 0;
+    }
     if (S == 0) S = 1000;
     rk_ctx* ctx = nullptr;
     CK(rk_ctx_create(device, &g_policy, &ctx));
