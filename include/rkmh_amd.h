@@ -102,6 +102,12 @@ void rk_free(void* p);
  * host, src/rkmh.cpp:845-898); pageable buffers keep working through the library's own pinned staging buffers. */
 int rk_host_alloc(size_t bytes, void** out);
 void rk_host_free(void* p);
+/* Device memory on the context's GPU, for callers that keep arrays resident between calls of the *_device entries and have no HIP
+ * runtime of their own (`rkmh gather` uploads its references once).  The copies run on the context's stream and return when done. */
+int rk_device_alloc(rk_ctx* ctx, size_t bytes, void** out);
+void rk_device_free(rk_ctx* ctx, void* p);
+int rk_device_upload(rk_ctx* ctx, void* d_dst, const void* src, size_t bytes);
+int rk_device_download(rk_ctx* ctx, void* dst, const void* d_src, size_t bytes);
 
 /* ------------------------------------------------------------------------------------------------
  * INNER boundary: one-sequence mirrors of the mkmh calls (replaces, file:line of the call site):
@@ -643,6 +649,42 @@ int rk_compare_scaled_device(rk_ctx* ctx, const void* d_a_values, const void* d_
                              void* d_shared, void* hip_stream);
 int rk_merge_scaled(const uint64_t* values, const uint64_t* offsets, int n, uint64_t max_hash, uint64_t** out, uint64_t* out_len);
 int rk_scaled_distance(int64_t shared, int64_t la, int64_t lb, int k, double* jaccard, double* distance);
+
+/* ------------------------------------------------------------------------------------------------
+ * GATHER (`rkmh gather`; the greedy minimum-set-cover that sourmash calls `gather`: which references make up a sample, and how much
+ * of it each explains once the better matches are taken out).  These are this library's own definitions.
+ *   Inputs: a query set Q of nq ascending, distinct, non-zero uint64; nref reference sets in CSR (values, offsets[nref + 1]), each
+ *   ascending and distinct; min_shared >= 1; max_rounds >= 1.
+ *   State: alive = Q; total[r] = |Q & R_r|.
+ *   Round t = 0, 1, ...: count[r] = |alive & R_r| for every r; the pick is the r with the largest count, among equals the LOWEST
+ *   reference index; if that count is below min_shared, stop; otherwise the row
+ *     out4[t] = (ref, unique = count[ref], total[ref], remaining = |alive| after the removal), four int32,
+ *   is written and alive -= R_ref; stop after max_rounds rows.  *nrounds = the number of rows written.
+ *   It follows that unique never increases from row to row, that no reference is picked twice, that nq - sum(unique) = remaining of
+ *   the last row, and that a reference whose total is below min_shared is never picked.  Abundance, base-pair estimates and
+ *   weighting are not part of it.
+ * All three entries refuse (RK_ERR_ARG, a size beyond the limit RK_ERR_LIMIT) before anything is launched: NULL, nref < 1,
+ * min_shared < 1, max_rounds < 1, nq > 2^31 - 1.
+ * rk_gather_scaled: host arrays; additionally refuses a query that is not strictly ascending or holds 0, offsets that decrease and a
+ * row of 2^31 values or more.  out4 holds min(max_rounds, nref) rows.
+ * rk_gather_scaled_device: resident arrays (r_nvalues = the number of uint64 behind d_r_values), so a database stays resident while
+ * many queries are gathered against it; d_out4 takes at most max_rounds rows (min(max_rounds, nref) are all there can be).  It runs on
+ * hip_stream (NULL = HIP's null stream; rk_ctx_stream() = the context's own) and SYNCHRONISES it: the setup needs the hit counts on
+ * the host to lay out the candidates' hit lists, and every group of RK_GATHER_BATCH rounds ends with a look at the state.  Every row
+ * is clamped on the device to lie inside [0, r_nvalues] and every index is checked before it is used; rows or a query that are not
+ * ascending give meaningless rows and nothing worse.  The work buffers are the context's: calls on one context take turns.
+ * The kernels (rk_gather.hip): k_gather_probe and k_gather_compact once per call (each reference value looked up in Q; the hits
+ * of every candidate -- a reference with total >= min_shared -- as a list of query indices), then per round k_gather_count,
+ * k_gather_pick, k_gather_remove on one byte per query value, without a host round trip inside a group of rounds.
+ * rk_gather_scaled_host: host code, usable without a GPU (rk_scaled_host.cpp): the same rows from the same loop on `threads` host
+ * threads (below 1: one); the checks of rk_gather_scaled. */
+#define RK_GATHER_BATCH 16 /* rounds enqueued between two looks at the state; the rows never depend on it */
+int rk_gather_scaled(rk_ctx* ctx, const uint64_t* q_values, uint64_t nq, const uint64_t* r_values, const uint64_t* r_offsets, int nref,
+                     int min_shared, int max_rounds, int32_t* out4, int* nrounds);
+int rk_gather_scaled_device(rk_ctx* ctx, const void* d_q_values, uint64_t nq, const void* d_r_values, const void* d_r_offsets, int nref,
+                            uint64_t r_nvalues, int min_shared, int max_rounds, void* d_out4, int* nrounds, void* hip_stream);
+int rk_gather_scaled_host(const uint64_t* q_values, uint64_t nq, const uint64_t* r_values, const uint64_t* r_offsets, int nref,
+                          int min_shared, int max_rounds, int threads, int32_t* out4, int* nrounds);
 
 #ifdef __cplusplus
 }

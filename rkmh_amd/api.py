@@ -91,6 +91,10 @@ _SIGS = {
     "rk_counter_copy": (C.c_int, [C.c_void_p, C.c_void_p]),
     "rk_host_alloc": (C.c_int, [C.c_size_t, C.POINTER(C.c_void_p)]),
     "rk_host_free": (None, [C.c_void_p]),
+    "rk_device_alloc": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
+    "rk_device_free": (None, [C.c_void_p, C.c_void_p]),
+    "rk_device_upload": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
+    "rk_device_download": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     "rk_to_upper": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
     "rk_calc_hashes": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, _ip, C.c_int, C.POINTER(_u64p), _ip]),
     "rk_calc_hashes_counted": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, _ip, C.c_int, C.POINTER(_u64p), _ip, C.c_void_p]),
@@ -232,6 +236,10 @@ _SIGS = {
                                            C.c_int, C.c_void_p, C.c_void_p]),
     "rk_merge_scaled": (C.c_int, [_u64p, _u64p, C.c_int, C.c_uint64, C.POINTER(_u64p), C.POINTER(C.c_uint64)]),
     "rk_scaled_distance": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "rk_gather_scaled": (C.c_int, [C.c_void_p, _u64p, C.c_uint64, _u64p, _u64p, C.c_int, C.c_int, C.c_int, _i32p, _ip]),
+    "rk_gather_scaled_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_int, C.c_int,
+                                          C.c_void_p, _ip, C.c_void_p]),
+    "rk_gather_scaled_host": (C.c_int, [_u64p, C.c_uint64, _u64p, _u64p, C.c_int, C.c_int, C.c_int, C.c_int, _i32p, _ip]),
 }
 
 
@@ -946,6 +954,26 @@ def scaled_distance(shared, la, lb, k):
     return j.value, d.value
 
 
+RK_GATHER_BATCH = 16  # include/rkmh_amd.h: rounds of gather enqueued between two looks at the state
+
+
+def _gather_args(q, r_values, r_offsets, max_rounds):
+    q = np.ascontiguousarray(q, dtype=np.uint64)
+    r_values, r_offsets = _csr(r_values, r_offsets)
+    nref = len(r_offsets) - 1
+    max_rounds = nref if max_rounds is None else int(max_rounds)
+    return q, r_values, r_offsets, nref, max_rounds, np.zeros((max(min(max_rounds, nref), 0), 4), dtype=np.int32)
+
+
+def gather_scaled_host(q, r_values, r_offsets, min_shared=1, max_rounds=None, threads=1):
+    """rk_gather_scaled_host (host code, no GPU): the rows of Context.gather_scaled from the same loop on `threads` host threads."""
+    q, r_values, r_offsets, nref, max_rounds, out = _gather_args(q, r_values, r_offsets, max_rounds)
+    n = C.c_int(0)
+    _chk(load_library().rk_gather_scaled_host(_p(q, C.c_uint64), len(q), _p(r_values, C.c_uint64), _p(r_offsets, C.c_uint64), nref, int(min_shared),
+                                              max_rounds, int(threads), _p(out, C.c_int32), C.byref(n)))
+    return out[: n.value].copy()
+
+
 class Context:
     """One GPU. Methods are named after the reference's functions they replace."""
 
@@ -1107,6 +1135,30 @@ class Context:
         _chk(self._lib.rk_compare_scaled_device(self._h, C.c_void_p(d_a_values_ptr), C.c_void_p(d_a_offsets_ptr), na, C.c_uint64(int(a_nvalues)),
                                                 C.c_void_p(d_b_values_ptr), C.c_void_p(d_b_offsets_ptr), nb, C.c_uint64(int(b_nvalues)),
                                                 int(lanes), C.c_void_p(d_shared_ptr), C.c_void_p(stream)))
+
+    # ---- gather ----------------------------------------------------------------------------------
+    def gather_scaled(self, q, r_values, r_offsets, min_shared=1, max_rounds=None):
+        """rk_gather_scaled: the greedy decomposition of the scaled sketch q (ascending, distinct, non-zero) into the CSR reference
+        sketches -> int32 [n, 4], one row per pick: (reference, unique = values of what is left of q that it holds, total = |q & ref|,
+        remaining = values of q left after it).  Stops when the best reference holds fewer than min_shared of what is left, or after
+        max_rounds rows (None: the number of references)."""
+        q, r_values, r_offsets, nref, max_rounds, out = _gather_args(q, r_values, r_offsets, max_rounds)
+        n = C.c_int(0)
+        _chk(self._lib.rk_gather_scaled(self._h, _p(q, C.c_uint64), len(q), _p(r_values, C.c_uint64), _p(r_offsets, C.c_uint64), nref,
+                                        int(min_shared), max_rounds, _p(out, C.c_int32), C.byref(n)))
+        return out[: n.value].copy()
+
+    def gather_scaled_device(self, d_q_ptr, nq, d_r_values_ptr, d_r_offsets_ptr, nref, r_nvalues, d_out4_ptr, min_shared=1, max_rounds=None,
+                             stream=None):
+        """Resident arrays (raw device pointers; d_out4: max_rounds rows of 4 int32, None: nref rows) -> the number of rows written.
+        Runs on `stream` (as for compare_sketches_device) and synchronises it.  Rows are clamped to [0, r_nvalues] on the device."""
+        if stream is None:
+            stream = self.stream
+        n = C.c_int(0)
+        _chk(self._lib.rk_gather_scaled_device(self._h, C.c_void_p(d_q_ptr), C.c_uint64(int(nq)), C.c_void_p(d_r_values_ptr), C.c_void_p(d_r_offsets_ptr),
+                                               int(nref), C.c_uint64(int(r_nvalues)), int(min_shared), int(nref if max_rounds is None else max_rounds),
+                                               C.c_void_p(d_out4_ptr), C.byref(n), C.c_void_p(stream)))
+        return n.value
 
     # ---- outer boundary (batches) ------------------------------------------------------------
     def hash_batch(self, bases, offsets, ks):

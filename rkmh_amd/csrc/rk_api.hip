@@ -84,7 +84,8 @@ extern "C" void rk_ctx_destroy(rk_ctx* c) {
     e = hipDeviceSynchronize(); (void)e;
     for (DevBuf* b : {&c->d_fpb, &c->d_base, &c->d_kv, &c->d_post, &c->d_pre, &c->d_keepbits, &c->d_kpost, &c->d_kbase, &c->d_kkeys, &c->d_kslots, &c->w_bases, &c->w_tiles, &c->w_hashes, &c->w_segoff,
                       &c->w_ids, &c->w_sk, &c->w_lens, &c->w_out, &c->w_misc, &c->w_sel, &c->w_selstate, &c->w_table, &c->w_gcount, &c->w_tail, &c->w_dedup,
-                      &c->w_sc_cnt, &c->w_sc_pre, &c->w_sc_off, &c->w_sc_a, &c->w_sc_b}) b->release();
+                      &c->w_sc_cnt, &c->w_sc_pre, &c->w_sc_off, &c->w_sc_a, &c->w_sc_b,
+                      &c->w_g_hit, &c->w_g_total, &c->w_g_alive, &c->w_g_state, &c->w_g_cand, &c->w_g_coff, &c->w_g_count, &c->w_g_list}) b->release();
     for (int j = 0; j < KM_MAX_KS; ++j) { c->d_kf4[j].release(); c->d_km1[j].release(); c->d_km1v[j].release(); c->d_km1m[j].release(); c->d_km1cells[j].release(); }
     c->d_keepkey.release(); c->d_kvm.release();
     for (auto& s : c->slot) {
@@ -210,6 +211,36 @@ extern "C" int rk_host_register_readonly(const void* p, size_t bytes) {
 }
 extern "C" void rk_host_unregister(const void* p) { if (p) { hipError_t e = hipHostUnregister(const_cast<void*>(p)); (void)e; } }
 extern "C" void rk_host_free(void* p) { if (p) { hipError_t e = hipHostFree(p); (void)e; } }
+
+// device memory for callers that keep arrays resident between calls of the *_device entries without a HIP runtime of their own (the
+// command line: `rkmh gather` uploads its references once); the copies run on the context's stream and return when they are done
+extern "C" int rk_device_alloc(rk_ctx* c, size_t bytes, void** out) {
+    if (!c || !out) return fail(RK_ERR_ARG, "bad arguments");
+    *out = nullptr;
+    RKCHK(set_dev(c));
+    hipError_t e = hipMalloc(out, bytes ? bytes : 1);
+    if (e != hipSuccess) { *out = nullptr; return fail(RK_ERR_NOMEM, "hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e)); }
+    return RK_OK;
+}
+extern "C" void rk_device_free(rk_ctx* c, void* p) {
+    if (!c || !p) return;
+    hipError_t e = hipSetDevice(c->device); (void)e;
+    e = hipFree(p); (void)e;
+}
+extern "C" int rk_device_upload(rk_ctx* c, void* d_dst, const void* src, size_t bytes) {
+    if (!c || ((!d_dst || !src) && bytes)) return fail(RK_ERR_ARG, "bad arguments");
+    RKCHK(set_dev(c));
+    if (bytes) HIPCHK(hipMemcpyAsync(d_dst, src, bytes, hipMemcpyHostToDevice, c->st));
+    HIPCHK(hipStreamSynchronize(c->st));
+    return RK_OK;
+}
+extern "C" int rk_device_download(rk_ctx* c, void* dst, const void* d_src, size_t bytes) {
+    if (!c || ((!dst || !d_src) && bytes)) return fail(RK_ERR_ARG, "bad arguments");
+    RKCHK(set_dev(c));
+    if (bytes) HIPCHK(hipMemcpyAsync(dst, d_src, bytes, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(hipStreamSynchronize(c->st));
+    return RK_OK;
+}
 
 // ---- inner boundary: the mirrors that are one copy-launch-copy ----------------------------------
 extern "C" int rk_to_upper(rk_ctx* c, char* seq, int len) {

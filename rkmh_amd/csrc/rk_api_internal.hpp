@@ -9,6 +9,7 @@
 //   rk_call.hip      `call`
 //   rk_pairs.hip     all-pairs comparison of bottom-S sketches
 //   rk_scaled.hip    scaled sketches: the keep step of the general path, all-pairs intersection of variable-length sets
+//   rk_gather.hip    gather: the greedy decomposition of a scaled sketch into reference sketches, its state resident across rounds
 #pragma once
 #include "../../include/rkmh_amd.h"
 #include "rk_kernels.hpp"
@@ -152,6 +153,7 @@ struct rk_ctx {
     // workspaces for the general path
     DevBuf w_bases, w_tiles, w_hashes, w_segoff, w_ids, w_sk, w_lens, w_out, w_misc, w_sel, w_selstate, w_table, w_gcount, w_tail, w_dedup;
     DevBuf w_sc_cnt, w_sc_pre, w_sc_off, w_sc_a, w_sc_b; // scaled sketches (rk_scaled.hip): block counts, their scan, CSR offsets, kept / distinct values
+    DevBuf w_g_hit, w_g_total, w_g_alive, w_g_state, w_g_cand, w_g_coff, w_g_count, w_g_list; // gather (rk_gather.hip): probe scratch, hit counts, alive bytes, round state, candidates, their offsets, counts and hit lists
     int ref_count_mode = 0; // -I counter fill: 0 per k-mer occurrence (stream), 1 once per distinct hash per reference (filter)
     Slot slot[2];
 };

@@ -8,7 +8,7 @@
 //   rkmh_packed.cpp     reads written by `rkmh pack` (-F)
 //   rkmh_refs.cpp       the -r files through the device
 //   rkmh_classify.cpp   stream / classify and filter: one driver, two thin commands
-//   rkmh_commands.cpp   call, sketch (and the JSON sketches stream -R reads), dist, hash, hpv16, pack; the hashing policy and help text
+//   rkmh_commands.cpp   call, sketch (and the JSON sketches stream -R reads), dist, gather, hash, hpv16, pack; the hashing policy and help text
 #pragma once
 #include <getopt.h>
 #include <sys/types.h>
@@ -75,6 +75,7 @@ int main_filter(int argc, char** argv);
 int main_call(int argc, char** argv);
 int main_sketch(int argc, char** argv);
 int main_dist(int argc, char** argv);
+int main_gather(int argc, char** argv);
 int main_hash(int argc, char** argv);
 int main_hpv16(int argc, char** argv);
 int main_pack(int argc, char** argv);

@@ -1,5 +1,5 @@
 // rkmh_commands.cpp -- the sub-commands of `rkmh` beside stream / filter: pack, call, sketch (and the JSON sketches stream -R reads),
-// dist, hash and hpv16; the hashing policy of the run and the help text they share.
+// dist, gather, hash and hpv16; the hashing policy of the run and the help text they share.
 #include <unistd.h>
 
 #include <algorithm>
@@ -32,6 +32,7 @@ void print_help() {
             "  hpv16               HPV type and HPV16 lineage / sublineage k-mer matches of every read\n"
             "  sketch              write MinHash sketches as JSON (load them with stream -R); --scaled: scaled (FracMinHash) sketches for dist\n"
             "  dist                Mash distance between every query sketch and every reference sketch; --scaled: Jaccard and containment of scaled sketches\n"
+            "  gather              decompose a sample's scaled sketch into references, greedily: what each explains once the better matches are taken out\n"
             "  pack                write reads as a packed file (2 bits per base + names): stream|filter -F <file> classifies it without parsing\n"
             "Run a command without options for its help text.\n");
 }
@@ -598,6 +599,19 @@ void refuse_scaled(const LoadedSketches& L, const char* path, const char* comman
 // dist: the Mash distance of every (query, reference) pair of sketches -- `mash dist`, which the reference has no command for.  The
 // four counts of a pair come from one launch over all pairs (rk_compare_sketches); the floating point is rk_mash_distance's.
 // Everything that can be refused is refused before a context exists: nothing is printed by a run that fails.
+// A loaded file of scaled sketches, kept at its own "scaled" until the run's value is known (dist, gather), and the cut down to it: a
+// prefix of every row, because rows ascend and max_hash is monotone in scaled.
+struct ScaledFile { std::string path; LoadedSketches L; };
+static void cut_scaled_files(const std::vector<ScaledFile>& from, uint64_t max_hash, ScaledSet& into) {
+    for (const ScaledFile& f : from)
+        for (size_t i = 0; i < f.L.names.size(); ++i) {
+            const uint64_t* b = f.L.sk.data() + f.L.off[i];
+            const uint64_t* e = std::upper_bound(b, f.L.sk.data() + f.L.off[i + 1], max_hash);
+            into.names.push_back(f.L.names[i]);
+            into.values.insert(into.values.end(), b, e);
+            into.off.push_back(into.values.size());
+        }
+}
 static void help_dist() {
     fprintf(stderr,
             "rkmh dist (-r <refs.fa> ... | -R <refs.json>) [-f <queries.fa|fq> ... | -Q <queries.json>] [-k <k>] [-s <sketch> | --scaled <n>] [-g] [-d <maxdist>]\n"
@@ -658,7 +672,6 @@ int main_dist(int argc, char** argv) {
     // sketch files: each agrees in itself (load_sketch_json), with the others, with -k / -s where given, and with the run's policy
     int k = ks.empty() ? 0 : ks[0];
     // scaled files: kept as loaded (each at its own "scaled") until the run's value is known, then cut down to it
-    struct ScaledFile { std::string path; LoadedSketches L; };
     std::vector<ScaledFile> sc_refs, sc_queries;
     bool any_bottom = false, any_scaled = false;
     uint64_t largest_scaled = 0;
@@ -707,18 +720,8 @@ int main_dist(int argc, char** argv) {
         uint64_t max_hash = 0;
         CK(rk_scaled_max_hash(scaled, &max_hash));
         ScaledSet sr, sq;
-        auto cut = [&](const std::vector<ScaledFile>& from, ScaledSet& into) { // a prefix of every row: rows ascend, max_hash is monotone
-            for (const ScaledFile& f : from)
-                for (size_t i = 0; i < f.L.names.size(); ++i) {
-                    const uint64_t* b = f.L.sk.data() + f.L.off[i];
-                    const uint64_t* e = std::upper_bound(b, f.L.sk.data() + f.L.off[i + 1], max_hash);
-                    into.names.push_back(f.L.names[i]);
-                    into.values.insert(into.values.end(), b, e);
-                    into.off.push_back(into.values.size());
-                }
-        };
-        cut(sc_refs, sr);
-        cut(sc_queries, sq);
+        cut_scaled_files(sc_refs, max_hash, sr);
+        cut_scaled_files(sc_queries, max_hash, sq);
         // sides that come from sketch files alone are known now: refused before a context exists, like everything above
         if (ref_files.empty() && sr.names.empty()) refuse("no reference sketches");
         if (!self && query_files.empty() && sq.names.empty()) refuse("no query sketches");
@@ -779,6 +782,163 @@ int main_dist(int argc, char** argv) {
         }
     fwrite(o.data(), 1, o.size(), stdout);
     fflush(stdout);
+    rk_ctx_destroy(ctx);
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------
+// gather: which references make up a sample, and how much of it each explains once the better matches are taken out (include/
+// rkmh_amd.h, "GATHER").  References and queries are scaled sketches, made or loaded as `dist --scaled` makes and loads them; the
+// references go to the device once, the queries are gathered against them one after the other (rk_gather_scaled_device).
+// Everything that can be refused is refused before a context exists.
+static void help_gather() {
+    fprintf(stderr,
+            "rkmh gather (-r <refs.fa> ... | -R <refs.json> ...) (-f <sample.fa|fq[.gz]> ... | -Q <queries.json> ...) [-k <k>] [--scaled <n>] [-g]\n"
+            "            [--min-shared <n>] [--max-rounds <n>] [--device <id>]\n"
+            "  decomposes every query into references, greedily: the reference that holds most of what is left of the query is printed and\n"
+            "  its hashes leave the query, until the best reference holds fewer than --min-shared (default 1) of them or --max-rounds lines\n"
+            "  are printed; one line per pick, query by query: query, rank (from 1), reference, unique/|query| (hashes only this pick\n"
+            "  explains at its turn), total/|query|, total/|reference| (total: all hashes the two share), remaining (hashes of the query\n"
+            "  left unexplained); a query that no reference matches prints nothing\n"
+            "  -f: every file is ONE query, the union of its records (a sample is a file of reads);  -Q: every sketch of the file is a query\n"
+            "  -r: one reference per record, with -g one per FILE;  -R / -Q: scaled sketches written by `rkmh sketch --scaled <m>`\n"
+            "  --scaled <n>: -r / -f files are sketched at n, -R / -Q files (m <= n) are cut down to n; without it: the largest m among the\n"
+            "  files; not with -s (bottom-s sketches cannot be decomposed)\n" HASH_POLICY_HELP);
+}
+static bool parse_at_least_1(const char* text, int& v) {
+    uint64_t u = 0;
+    if (!parse_scaled(text, u) || u > 0x7fffffffull) return false;
+    v = (int)u;
+    return true;
+}
+int main_gather(int argc, char** argv) {
+    std::vector<const char*> ref_files, query_files, ref_json, query_json;
+    std::vector<int> ks;
+    int device = 0, min_shared = 1, max_rounds = 0x7fffffff;
+    bool whole_files = false, scaled_given = false, scaled_ok = true, s_given = false, min_ok = true, rounds_ok = true;
+    uint64_t scaled = 0; // --scaled, or the largest "scaled" of the files loaded
+    if (argc <= 2) { help_gather(); exit(1); }
+    static struct option long_options[] = {{"help", no_argument, 0, 'h'}, {"kmer", required_argument, 0, 'k'}, {"fasta", required_argument, 0, 'f'},
+        {"reference", required_argument, 0, 'r'}, {"pre-references", required_argument, 0, 'R'}, {"pre-queries", required_argument, 0, 'Q'},
+        {"sketch-size", required_argument, 0, 's'}, {"whole-files", no_argument, 0, 'g'}, {"device", required_argument, 0, 1000},
+        {"scaled", required_argument, 0, 1005}, {"min-shared", required_argument, 0, 1006}, {"max-rounds", required_argument, 0, 1007},
+        HASH_POLICY_OPTION, {0, 0, 0, 0}};
+    optind = 2;
+    int c;
+    while ((c = getopt_long(argc, argv, "hgk:f:r:R:Q:s:", long_options, nullptr)) != -1) {
+        switch (c) {
+            case 1004: policy_apply(optarg, "--hash-policy"); break;
+            case 1005: scaled_given = true; scaled_ok = parse_scaled(optarg, scaled); break;
+            case 1006: min_ok = parse_at_least_1(optarg, min_shared); break;
+            case 1007: rounds_ok = parse_at_least_1(optarg, max_rounds); break;
+            case 'r': ref_files.push_back(optarg); break;
+            case 'f': query_files.push_back(optarg); break;
+            case 'R': ref_json.push_back(optarg); break;
+            case 'Q': query_json.push_back(optarg); break;
+            case 'k': ks.push_back(atoi(optarg)); break;
+            case 's': s_given = true; break;
+            case 'g': whole_files = true; break;
+            case 1000: device = atoi(optarg); break;
+            default: help_gather(); exit(1);
+        }
+    }
+    auto refuse = [](const std::string& why) { fprintf(stderr, "rkmh gather: %s\n", why.c_str()); exit(1); };
+    if (ks.size() > 1) {
+        std::string given;
+        for (int k : ks) given += " " + std::to_string(k);
+        refuse("gather needs one k-mer size; sizes provided:" + given);
+    }
+    if (s_given) refuse("-s makes bottom-s sketches, which cannot be decomposed; gather works on scaled ones (--scaled)");
+    if (scaled_given && !scaled_ok) refuse("--scaled takes a number of at least 1");
+    if (!min_ok) refuse("--min-shared takes a number of at least 1");
+    if (!rounds_ok) refuse("--max-rounds takes a number of at least 1");
+    if (ref_files.empty() == ref_json.empty()) refuse("references come from -r <fasta> ... or from -R <sketches.json> ..., one of the two");
+    if (query_files.empty() == query_json.empty()) refuse("queries come from -f <fasta|fastq> ... or from -Q <sketches.json> ..., one of the two");
+    if (whole_files && ref_files.empty()) refuse("-g says how -r files are sketched; sketches loaded with -R are what they are");
+    int k = ks.empty() ? 0 : ks[0];
+    std::vector<ScaledFile> sc_refs, sc_queries;
+    uint64_t largest_scaled = 0;
+    auto load = [&](const std::vector<const char*>& paths, std::vector<ScaledFile>& into) { // the checks of `dist`, scaled files only
+        for (const char* path : paths) {
+            LoadedSketches L;
+            if (!load_sketch_json(path, L, RK_MAX_SKETCH)) {
+                if (!L.err.empty()) refuse(std::string(path) + ": " + L.err);
+                refuse(std::string("cannot load sketches from ") + path + " (unreadable, or its sketches disagree in kmer, hashPolicy or length)");
+            }
+            rk_policy theirs;
+            rk_default_policy(&theirs);
+            if (rk_policy_parse(L.policy.c_str(), &theirs) != RK_OK) refuse(std::string(path) + ": " + rk_last_error());
+            if (!rk_policy_same_hashes(&theirs, &g_policy))
+                refuse(std::string(path) + " holds sketches hashed with " + policy_text(theirs) + ", this run hashes with " + policy_text(g_policy) + ": pass --hash-policy " + policy_text(theirs));
+            if (L.ks.size() != 1) refuse(std::string(path) + " holds sketches of " + std::to_string(L.ks.size()) + " k-mer sizes; gather needs one");
+            if (k != 0 && L.ks[0] != k) refuse(std::string(path) + " holds sketches of k = " + std::to_string(L.ks[0]) + ", the others (or -k) say " + std::to_string(k));
+            if (!L.scaled) refuse(std::string(path) + " holds bottom-s sketches; gather decomposes scaled ones (rkmh sketch --scaled)");
+            if (scaled_given && L.scaled > scaled)
+                refuse(std::string(path) + " holds sketches of scaled = " + std::to_string(L.scaled) + ": they cannot be made finer, --scaled must be at least that");
+            largest_scaled = std::max(largest_scaled, L.scaled);
+            k = L.ks[0];
+            into.push_back(ScaledFile{path, std::move(L)});
+        }
+    };
+    load(ref_json, sc_refs);
+    load(query_json, sc_queries);
+    if (!scaled_given && largest_scaled == 0) refuse("no sketch file says at which scaled to sketch: give --scaled <n>");
+    if (k == 0) { fprintf(stderr, "No kmer size(s) provided. Will use a default kmer size of 16.\n"); k = 16; }
+    if (k < 1 || k > RK_MAX_K) refuse("k-mer size outside 1 .. " + std::to_string(RK_MAX_K));
+    if (!scaled_given) scaled = largest_scaled;
+    uint64_t max_hash = 0;
+    CK(rk_scaled_max_hash(scaled, &max_hash));
+    ScaledSet sr, sq;
+    cut_scaled_files(sc_refs, max_hash, sr);
+    cut_scaled_files(sc_queries, max_hash, sq);
+    if (ref_files.empty() && sr.names.empty()) refuse("no reference sketches");
+    if (query_files.empty() && sq.names.empty()) refuse("no query sketches");
+    rk_ctx* ctx = nullptr;
+    CK(rk_ctx_create(device, &g_policy, &ctx));
+    const std::vector<int> kk(1, k);
+    if (!ref_files.empty()) sketch_files_scaled(ctx, ref_files, kk, max_hash, whole_files, sr);
+    if (!query_files.empty()) sketch_files_scaled(ctx, query_files, kk, max_hash, true, sq); // a sample: one sketch per file
+    const size_t nq = sq.names.size(), nr = sr.names.size();
+    if (nr == 0 || nq == 0) { fprintf(stderr, "rkmh gather: no %s sketches\n", nr == 0 ? "reference" : "query"); exit(1); }
+    if (nr > 0x7fffffffull) refuse("more than 2^31-1 reference sketches");
+    // the references go to the device once; every query follows them into the same two arrays
+    uint64_t longest = 0;
+    for (size_t i = 0; i < nq; ++i) longest = std::max(longest, sq.off[i + 1] - sq.off[i]);
+    if (longest > 0x7fffffffull) refuse("a query of more than 2^31-1 hashes");
+    const int rows = (int)std::min<size_t>((size_t)max_rounds, nr);
+    void *d_rv = nullptr, *d_ro = nullptr, *d_q = nullptr, *d_out = nullptr;
+    CK(rk_device_alloc(ctx, sr.values.size() * 8, &d_rv));
+    CK(rk_device_alloc(ctx, sr.off.size() * 8, &d_ro));
+    CK(rk_device_alloc(ctx, (size_t)longest * 8, &d_q));
+    CK(rk_device_alloc(ctx, (size_t)rows * 16, &d_out));
+    CK(rk_device_upload(ctx, d_rv, sr.values.data(), sr.values.size() * 8));
+    CK(rk_device_upload(ctx, d_ro, sr.off.data(), sr.off.size() * 8));
+    std::vector<int32_t> out4((size_t)rows * 4);
+    std::string o;
+    char num[200];
+    for (size_t i = 0; i < nq; ++i) {
+        const uint64_t lq = sq.off[i + 1] - sq.off[i];
+        int n = 0;
+        CK(rk_device_upload(ctx, d_q, sq.values.data() + sq.off[i], (size_t)lq * 8));
+        CK(rk_gather_scaled_device(ctx, d_q, lq, d_rv, d_ro, (int)nr, sr.values.size(), min_shared, rows, d_out, &n, rk_ctx_stream(ctx)));
+        CK(rk_device_download(ctx, out4.data(), d_out, (size_t)n * 16));
+        for (int t = 0; t < n; ++t) {
+            const int32_t* r = &out4[(size_t)t * 4];
+            const size_t ref = (size_t)r[0];
+            if (ref >= nr) { fprintf(stderr, "rkmh gather: row %d names reference %d of %zu\n", t, r[0], nr); exit(1); }
+            o += sq.names[i];
+            const int m = snprintf(num, sizeof num, "\t%d\t", t + 1);
+            o.append(num, (size_t)m);
+            o += sr.names[ref];
+            const int m2 = snprintf(num, sizeof num, "\t%d/%llu\t%d/%llu\t%d/%llu\t%d\n", r[1], (unsigned long long)lq, r[2], (unsigned long long)lq, r[2],
+                                    (unsigned long long)(sr.off[ref + 1] - sr.off[ref]), r[3]);
+            o.append(num, (size_t)m2);
+        }
+        if (o.size() > (1u << 22)) { fwrite(o.data(), 1, o.size(), stdout); o.clear(); }
+    }
+    fwrite(o.data(), 1, o.size(), stdout);
+    fflush(stdout);
+    for (void* p : {d_rv, d_ro, d_q, d_out}) rk_device_free(ctx, p);
     rk_ctx_destroy(ctx);
     return 0;
 }
