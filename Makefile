@@ -86,7 +86,7 @@ $(LIB): $(OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(OBJS) -lz -lpthread -ldl
 
 # the command line: one program from the rkmh_*.cpp files (what each holds: rkmh_cli.hpp)
-CLI_SRCS := $(CSRC)/rkmh_main.cpp $(CSRC)/rkmh_exit.cpp $(CSRC)/rkmh_frontends.cpp $(CSRC)/rkmh_rawreads.cpp $(CSRC)/rkmh_packed.cpp $(CSRC)/rkmh_refs.cpp $(CSRC)/rkmh_classify.cpp $(CSRC)/rkmh_commands.cpp
+CLI_SRCS := $(CSRC)/rkmh_main.cpp $(CSRC)/rkmh_exit.cpp $(CSRC)/rkmh_frontends.cpp $(CSRC)/rkmh_rawreads.cpp $(CSRC)/rkmh_packed.cpp $(CSRC)/rkmh_refs.cpp $(CSRC)/rkmh_classify.cpp $(CSRC)/rkmh_commands.cpp $(CSRC)/rkmh_sketch_json.cpp $(CSRC)/rkmh_sketches.cpp $(CSRC)/rkmh_compare.cpp $(CSRC)/rkmh_hpv16.cpp
 bin/rkmh: $(CLI_SRCS) $(CSRC)/rkmh_cli.hpp $(LIB) include/rkmh_amd.h
 	@mkdir -p bin
 	g++ -O2 -std=c++17 -Wall -o $@ $(CLI_SRCS) -Irkmh_amd/csrc -Lrkmh_amd/lib -lrkmh_amd -Wl,-rpath,'$$ORIGIN/../rkmh_amd/lib'

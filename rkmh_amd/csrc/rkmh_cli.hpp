@@ -5,10 +5,14 @@
 //                       protocol, the host scanner pipeline
 //   rkmh_rawreads.cpp   FASTQ read files through the device front end (plain / BGZF / gzip): the registry of input files, RawEngine,
 //                       stream_files_raw and two_pass_raw
-//   rkmh_packed.cpp     reads written by `rkmh pack` (-F)
+//   rkmh_packed.cpp     reads written by `rkmh pack` (-F), and `pack` itself
 //   rkmh_refs.cpp       the -r files through the device
 //   rkmh_classify.cpp   stream / classify and filter: one driver, two thin commands
-//   rkmh_commands.cpp   call, sketch (and the JSON sketches stream -R reads), dist, gather, hash, hpv16, pack; the hashing policy and help text
+//   rkmh_commands.cpp   the hashing policy and the help text; call and hash
+//   rkmh_sketch_json.cpp  the reader of the JSON sketches `sketch` writes (stream -R, dist, gather); stands alone
+//   rkmh_sketches.cpp   sketch sets: made from sequence files, written as JSON, loaded from -R / -Q files, cut to one scaled
+//   rkmh_compare.cpp    sketch, dist and gather
+//   rkmh_hpv16.cpp      hpv16
 #pragma once
 #include <getopt.h>
 #include <sys/types.h>
@@ -58,6 +62,9 @@ std::string policy_text(const rk_policy& p);
     "                          is the smaller string, dedup=distinct sketches distinct values: the rules of Mash and sourmash;\n" \
     "                          `sourmash` = mash,canon=lexmin,dedup=distinct.  RKMH_POLICY: the same, read first\n"
 void print_help();
+int default_k(); // "No kmer size(s) provided..." on stderr, and the 16 it announces
+
+// ---- the JSON sketches of `rkmh sketch`, read back (rkmh_sketch_json.cpp)
 struct LoadedSketches {
     std::vector<std::string> names; std::vector<uint64_t> sk; std::vector<int32_t> lens; std::vector<int> ks; int S = 0; std::string policy;
     // a file of scaled sketches (`rkmh sketch --scaled`): scaled > 0, S = 0, sk holds the values of all sketches one after the other and
@@ -66,8 +73,69 @@ struct LoadedSketches {
     std::vector<uint64_t> off;
     std::string err; // why load_sketch_json returned false, where it knows more than "cannot load"
 };
-void refuse_scaled(const LoadedSketches& L, const char* path, const char* command); // exits when L holds scaled sketches
 bool load_sketch_json(const char* path, LoadedSketches& L, int max_S = 0); // max_S > 0: a larger "length" is refused before anything of that size is allocated
+
+// ---- sketch sets (rkmh_sketches.cpp): what sketch, dist and gather make from sequence files, write, load and compare
+void refuse_scaled(const LoadedSketches& L, const char* path, const char* command); // exits when L holds scaled sketches
+struct OutBuf { // lines on their way to a file: written whenever a row ends with more than 4 MB waiting, and at flush()
+    FILE* to;
+    std::string s;
+    explicit OutBuf(FILE* f) : to(f) {}
+    void append(const std::string& t) { s += t; }
+    template <class... A> void appendf(const char* fmt, A... a) { char b[200]; s.append(b, (size_t)snprintf(b, sizeof b, fmt, a...)); } // up to 200 characters
+    void end_row() { if (s.size() > (1u << 22)) flush(); }
+    void flush() { fwrite(s.data(), 1, s.size(), to); s.clear(); }
+};
+// Bottom-s sketches, S values a row, and scaled ones as CSR (sketch i = values[off[i], off[i + 1])).  From sequence files: one per
+// record -- or, whole_files (-g), one per FILE: its records are sketched one by one (no window spans two contigs) and united
+// (rk_merge_sketches: the bottom S under the policy's dedup rule; rk_merge_scaled), named by the path as given, seqLen their sum.
+struct SketchSet { std::vector<std::string> names; std::vector<uint64_t> seq_len; std::vector<uint64_t> sk; std::vector<int32_t> lens; };
+struct ScaledSet { std::vector<std::string> names; std::vector<uint64_t> seq_len; std::vector<uint64_t> values; std::vector<uint64_t> off = std::vector<uint64_t>(1, 0); };
+void sketch_files(rk_ctx* ctx, const std::vector<const char*>& files, const std::vector<int>& ks, int S, bool whole_files, SketchSet& out);
+void sketch_files_scaled(rk_ctx* ctx, const std::vector<const char*>& files, const std::vector<int>& ks, uint64_t max_hash, bool whole_files, ScaledSet& out);
+struct SketchRow { const uint64_t* hashes; uint64_t n, length; }; // a sketch to write; "length": the S of a bottom-s sketch, a scaled one's own size
+void write_sketch_json(FILE* fo, const std::vector<std::string>& names, const std::vector<uint64_t>& seq_len, const std::string& kstr,
+                       const std::vector<SketchRow>& rows, uint64_t scaled, uint64_t max_hash); // scaled = 0: a bottom-s file
+bool parse_scaled(const char* text, uint64_t& scaled); // --scaled: a number of at least 1, nothing else
+bool parse_at_least_1(const char* text, int& v);
+// What dist and gather are told alike (-r -f -R -Q -k -s -g --scaled --device --hash-policy): the rows of their long_options, and
+// shared_option, which takes such an option (false: the command's own)
+struct CompareInputs {
+    std::vector<const char*> ref_files, query_files, ref_json, query_json;
+    std::vector<int> ks;
+    int S = 0, device = 0; // S: 0 without -s, -1 for a -s below 1
+    bool whole_files = false, scaled_given = false, scaled_ok = true;
+    uint64_t scaled = 0;
+    bool self() const { return query_files.empty() && query_json.empty(); }
+};
+#define COMPARE_OPTIONS \
+    {"help", no_argument, 0, 'h'}, {"kmer", required_argument, 0, 'k'}, {"fasta", required_argument, 0, 'f'}, {"reference", required_argument, 0, 'r'}, \
+    {"pre-references", required_argument, 0, 'R'}, {"pre-queries", required_argument, 0, 'Q'}, {"sketch-size", required_argument, 0, 's'}, \
+    {"whole-files", no_argument, 0, 'g'}, {"device", required_argument, 0, 1000}, {"scaled", required_argument, 0, 1005}, HASH_POLICY_OPTION
+bool shared_option(int c, CompareInputs& in);
+struct CompareRules { // where the two differ in what they accept and in their words
+    const char* command;         // "dist" / "gather": every refusal begins "rkmh <command>: "
+    const char* noun;            // "<noun> needs one k-mer size"
+    const char* no_bottom;       // what a bottom-s file is told after "<path> holds bottom-s sketches; "; nullptr: such files are welcome
+    bool file_is_one_query;      // every -f file is ONE query, whatever -g says of the -r files
+    const char* too_many_loaded; // refusal of more than 2^31-1 loaded sketches on a side before a context exists; nullptr: none
+};
+[[noreturn]] void refuse(const CompareRules& rules, const std::string& why);
+int one_k(const CompareInputs& in, const CompareRules& rules); // -k, 0 without one; several are refused
+// The -R and -Q files: each agrees in itself (load_sketch_json), with the others, with -k / -s / --scaled where given, and with the
+// run's policy.  Bottom-s files join refs / queries; scaled files are kept as loaded, each at its own "scaled", until the run's value
+// is known.  k: one_k()'s answer, then what the files said; S likewise (0: nobody said).
+struct LoadedSides {
+    SketchSet refs, queries;
+    std::vector<LoadedSketches> sc_refs, sc_queries;
+    int k = 0, S = 0;
+    uint64_t largest_scaled = 0; // 0: no scaled file
+};
+void load_sketch_files(const CompareInputs& in, const CompareRules& rules, LoadedSides& ld);
+// From the loaded scaled files and the -r / -f paths to the two sets of a scaled run, all at one scaled (--scaled, or the largest of
+// the files: a cut is a prefix of every row), and its context.  Sides known from files alone are refused before the context exists.
+struct ScaledRun { rk_ctx* ctx = nullptr; ScaledSet refs, own_queries; const ScaledSet* queries = nullptr; }; // queries: refs when there is no -f / -Q
+void start_scaled_run(const CompareInputs& in, const CompareRules& rules, const LoadedSides& ld, int k, ScaledRun& run);
 
 // ---- the sub-commands
 int main_stream(int argc, char** argv);

@@ -1,0 +1,284 @@
+// rkmh_compare.cpp -- the commands on sketch sets (rkmh_sketches.cpp): sketch writes them, dist compares all pairs, gather decomposes.
+#include <algorithm>
+
+#include "rkmh_cli.hpp"
+
+static void help_sketch() {
+    fprintf(stderr,
+            "rkmh sketch -f <seqs.fa|fq> [-k <k>]... [-s <sketch> | --scaled <n>] [-g] [-o <out.json>] [--kmer-cache <file>]\n"
+            "  writes a JSON array with one MinHash sketch per sequence (schema of the reference's dump_hash_json);\n"
+            "  -g: one sketch per input FILE (named by its path; no k-mer spans two of its records), as Mash sketches an assembly;\n"
+            "  --scaled <n>: scaled (FracMinHash) sketches instead of bottom-s ones: every distinct hash up to (2^64 - 1) / n, so the size\n"
+            "  grows with the sequence; objects gain \"scaled\" and \"maxHash\"; such files serve `rkmh dist` only\n"
+            "  `rkmh stream -R <out.json>` loads it instead of sketching references again;\n"
+            "  --kmer-cache <file>: also enumerates the k-mers behind these sketches (k 8 .. 18) into <file>, which\n"
+            "  `rkmh stream -R <out.json> --kmer-cache <file>` then loads instead of enumerating them at every start\n"
+            "  the file records the hashing policy (\"hashPolicy\"); stream -R refuses sketches hashed under another one\n" HASH_POLICY_HELP);
+}
+int main_sketch(int argc, char** argv) {
+    std::vector<const char*> files;
+    std::vector<int> ks;
+    int S = 1000, device = 0;
+    const char* outp = nullptr;
+    const char* kmer_cache = nullptr;
+    bool whole_files = false, s_given = false, scaled_given = false, scaled_ok = true;
+    uint64_t scaled = 0;
+    if (argc <= 2) { help_sketch(); exit(1); }
+    optind = 2;
+    int c;
+    static struct option long_options[] = {{"help", no_argument, 0, 'h'}, {"kmer", required_argument, 0, 'k'},
+        {"fasta", required_argument, 0, 'f'}, {"reference", required_argument, 0, 'r'}, {"sketch-size", required_argument, 0, 's'},
+        {"output", required_argument, 0, 'o'}, {"device", required_argument, 0, 1000}, {"kmer-cache", required_argument, 0, 1003},
+        {"whole-files", no_argument, 0, 'g'}, {"scaled", required_argument, 0, 1005}, HASH_POLICY_OPTION, {0, 0, 0, 0}};
+    while ((c = getopt_long(argc, argv, "hgk:f:r:s:o:t:", long_options, nullptr)) != -1) {
+        switch (c) {
+            case 1004: policy_apply(optarg, "--hash-policy"); break;
+            case 1005: scaled_given = true; scaled_ok = parse_scaled(optarg, scaled); break;
+            case 1003: kmer_cache = optarg; break;
+            case 'g': whole_files = true; break;
+            case 'f': case 'r': files.push_back(optarg); break;
+            case 'k': ks.push_back(atoi(optarg)); break;
+            case 's': S = atoi(optarg); s_given = true; break;
+            case 'o': outp = optarg; break;
+            case 't': break;
+            case 1000: device = atoi(optarg); break;
+            default: help_sketch(); exit(1);
+        }
+    }
+    if (ks.empty()) ks.push_back(default_k());
+    if (files.empty()) { fprintf(stderr, "rkmh: -f <file> is required\n"); exit(1); }
+    if (scaled_given) {
+        if (!scaled_ok) { fprintf(stderr, "rkmh sketch: --scaled takes a number of at least 1\n"); exit(1); }
+        if (s_given) { fprintf(stderr, "rkmh sketch: --scaled and -s are two kinds of sketch; give one of them\n"); exit(1); }
+        if (kmer_cache) { fprintf(stderr, "rkmh sketch: --kmer-cache serves `stream -R`; scaled sketches serve `rkmh dist` only\n"); exit(1); }
+    }
+    if (!scaled_given && whole_files && (S < 1 || S > RK_MAX_SKETCH)) { fprintf(stderr, "rkmh sketch: -g needs a sketch size of 1 .. %d\n", RK_MAX_SKETCH); exit(1); }
+    rk_ctx* ctx = nullptr;
+    CK(rk_ctx_create(device, &g_policy, &ctx));
+    SketchSet set;
+    ScaledSet sc;
+    std::vector<SketchRow> rows;
+    uint64_t max_hash = 0;
+    if (scaled_given) {
+        CK(rk_scaled_max_hash(scaled, &max_hash));
+        sketch_files_scaled(ctx, files, ks, max_hash, whole_files, sc);
+        for (size_t i = 0; i < sc.names.size(); ++i) rows.push_back({sc.values.data() + sc.off[i], sc.off[i + 1] - sc.off[i], sc.off[i + 1] - sc.off[i]});
+    } else {
+        sketch_files(ctx, files, ks, S, whole_files, set);
+        if (kmer_cache && *kmer_cache) {
+            // the index of these sketches is built once here, for its k-mer enumeration: the file's tag hashes the index keys, k and the
+            // hashing policy, so a later `stream -R <these sketches> --kmer-cache <file>` finds it -- and anything else does not use it
+            CK(rk_set_kmer_cache(ctx, kmer_cache));
+            CK(rk_set_reference_sketches(ctx, set.sk.data(), set.lens.data(), (int)set.names.size(), ks.data(), (int)ks.size(), S));
+            if (rk_kmer_cache_state(ctx) == 0) fprintf(stderr, "rkmh: no k-mer enumeration for these sketches (k-mer sizes outside 8 .. 18, or a hash with two k-mers): %s not written\n", kmer_cache);
+        }
+        for (size_t i = 0; i < set.names.size(); ++i) rows.push_back({set.sk.data() + i * (size_t)S, (uint64_t)set.lens[i], (uint64_t)S});
+    }
+    FILE* fo = outp ? fopen(outp, "w") : stdout;
+    if (!fo) { fprintf(stderr, "rkmh: cannot write %s\n", outp); exit(1); }
+    std::string kstr;
+    for (size_t i = 0; i < ks.size(); ++i) { kstr += std::to_string(ks[i]); if (i + 1 < ks.size()) kstr += ' '; }
+    write_sketch_json(fo, scaled_given ? sc.names : set.names, scaled_given ? sc.seq_len : set.seq_len, kstr, rows, scaled_given ? scaled : 0, max_hash);
+    if (fo != stdout) fclose(fo);
+    rk_ctx_destroy(ctx);
+    return 0;
+}
+
+// -k, or what the sketch files said, or the default; inside the library's range
+static int run_k(const CompareRules& rules, int k) {
+    if (k == 0) k = default_k();
+    if (k < 1 || k > RK_MAX_K) refuse(rules, "k-mer size outside 1 .. " + std::to_string(RK_MAX_K));
+    return k;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------
+// dist: the Mash distance of every (query, reference) pair of sketches -- `mash dist`, which the reference has no command for.  The
+// four counts of a pair come from one launch over all pairs (rk_compare_sketches); the floating point is rk_mash_distance's.  With
+// scaled sketches: their shared values (rk_compare_scaled) and rk_scaled_distance.
+// Everything that can be refused is refused before a context exists: nothing is printed by a run that fails.
+static void help_dist() {
+    fprintf(stderr,
+            "rkmh dist (-r <refs.fa> ... | -R <refs.json>) [-f <queries.fa|fq> ... | -Q <queries.json>] [-k <k>] [-s <sketch> | --scaled <n>] [-g] [-d <maxdist>]\n"
+            "  prints one line per (query, reference) pair, query by query: reference, query, Mash distance, common/denom of the merged\n"
+            "  bottom-s sketch, shared hashes (the multiset intersection `stream` counts); without -f / -Q every reference is compared\n"
+            "  with every reference\n"
+            "  -R / -Q: sketches written by `rkmh sketch` (their k-mer size, sketch size and hashing policy must agree with each other and the run)\n"
+            "  --scaled <n>: compare scaled (FracMinHash) sketches, every distinct hash up to (2^64 - 1) / n: -r / -f files are sketched at n,\n"
+            "  -R / -Q files hold sketches of `rkmh sketch --scaled <m>`, m <= n, and are cut down to n (without --scaled: to the largest m\n"
+            "  among them); a line is then: reference, query, distance from shared/union, shared/union, shared/|query|, shared/|reference|\n"
+            "  (the last two: how much of the query is contained in the reference, and the reverse); not with -s\n"
+            "  -g: one sketch per input FILE, as Mash sketches an assembly;  -d <x>: only pairs at distance <= x;  --device <id>: GPU to use\n" HASH_POLICY_HELP);
+}
+static const CompareRules dist_rules = {"dist", "a distance", nullptr, false, "more than 2^31-1 sketches on one side"};
+static int dist_scaled(const CompareInputs& in, const LoadedSides& ld, int k, double max_dist) {
+    ScaledRun run;
+    start_scaled_run(in, dist_rules, ld, k, run);
+    const ScaledSet &q = *run.queries, &sr = run.refs;
+    const size_t nq = q.names.size(), nr = sr.names.size();
+    if (nq > 0x7fffffffull || nr > 0x7fffffffull) refuse(dist_rules, "more than 2^31-1 sketches on one side");
+    std::vector<int32_t> shared(nq * nr);
+    CK(rk_compare_scaled(run.ctx, q.values.data(), q.off.data(), (int)nq, sr.values.data(), sr.off.data(), (int)nr, 0, shared.data()));
+    OutBuf o(stdout);
+    for (size_t i = 0; i < nq; ++i)
+        for (size_t j = 0; j < nr; ++j) {
+            const long long sh = shared[i * nr + j], lq = (long long)(q.off[i + 1] - q.off[i]), lr = (long long)(sr.off[j + 1] - sr.off[j]);
+            double jac = 0, d = 1;
+            CK(rk_scaled_distance(sh, lq, lr, k, &jac, &d));
+            if (d > max_dist) continue;
+            o.append(sr.names[j]); o.append("\t"); o.append(q.names[i]);
+            o.appendf("\t%.6g\t%lld/%lld\t%lld/%lld\t%lld/%lld\n", d, sh, lq + lr - sh, sh, lq, sh, lr);
+            o.end_row();
+        }
+    o.flush();
+    fflush(stdout);
+    rk_ctx_destroy(run.ctx);
+    return 0;
+}
+static int dist_bottom(const CompareInputs& in, LoadedSides& ld, int k, double max_dist) {
+    const int S = ld.S ? ld.S : 1000;
+    rk_ctx* ctx = nullptr;
+    CK(rk_ctx_create(in.device, &g_policy, &ctx));
+    const std::vector<int> k1(1, k);
+    if (!in.ref_files.empty()) sketch_files(ctx, in.ref_files, k1, S, in.whole_files, ld.refs);
+    if (!in.query_files.empty()) sketch_files(ctx, in.query_files, k1, S, in.whole_files, ld.queries);
+    const SketchSet &refs = ld.refs, &q = in.self() ? ld.refs : ld.queries;
+    const size_t nq = q.names.size(), nr = refs.names.size();
+    if (nr == 0 || nq == 0) refuse(dist_rules, std::string("no ") + (nr == 0 ? "reference" : "query") + " sketches");
+    if (nq > 0x7fffffffull || nr > 0x7fffffffull) refuse(dist_rules, "more than 2^31-1 sketches on one side");
+    std::vector<int32_t> out4(nq * nr * 4);
+    CK(rk_compare_sketches(ctx, q.sk.data(), q.lens.data(), (int)nq, refs.sk.data(), refs.lens.data(), (int)nr, S, out4.data()));
+    OutBuf o(stdout);
+    for (size_t i = 0; i < nq; ++i)
+        for (size_t j = 0; j < nr; ++j) {
+            const int32_t* r = &out4[(i * nr + j) * 4];
+            double jac = 0, d = 1;
+            CK(rk_mash_distance(r[2], r[3], k, &jac, &d));
+            if (d > max_dist) continue;
+            o.append(refs.names[j]); o.append("\t"); o.append(q.names[i]);
+            o.appendf("\t%.6g\t%d/%d\t%d\n", d, r[2], r[3], r[0]);
+            o.end_row();
+        }
+    o.flush();
+    fflush(stdout);
+    rk_ctx_destroy(ctx);
+    return 0;
+}
+int main_dist(int argc, char** argv) {
+    CompareInputs in;
+    double max_dist = 2.0;
+    if (argc <= 2) { help_dist(); exit(1); }
+    static struct option long_options[] = {COMPARE_OPTIONS, {"max-dist", required_argument, 0, 'd'}, {"threads", required_argument, 0, 't'}, {0, 0, 0, 0}};
+    optind = 2;
+    int c;
+    while ((c = getopt_long(argc, argv, "hgk:f:r:R:Q:s:d:t:", long_options, nullptr)) != -1) {
+        if (shared_option(c, in)) continue;
+        switch (c) {
+            case 'd': max_dist = atof(optarg); break;
+            case 't': break;
+            default: help_dist(); exit(1);
+        }
+    }
+    LoadedSides ld;
+    ld.k = one_k(in, dist_rules);
+    if (in.scaled_given && !in.scaled_ok) refuse(dist_rules, "--scaled takes a number of at least 1");
+    if (in.scaled_given && in.S != 0) refuse(dist_rules, "--scaled and -s are two kinds of sketch; give one of them");
+    if (in.S != 0 && (in.S < 1 || in.S > RK_MAX_SKETCH)) refuse(dist_rules, "sketch size outside 1 .. " + std::to_string(RK_MAX_SKETCH));
+    if (in.ref_files.empty() == in.ref_json.empty()) refuse(dist_rules, "references come from -r <fasta> ... or from -R <sketches.json> ..., one of the two");
+    if (!in.query_files.empty() && !in.query_json.empty()) refuse(dist_rules, "queries come from -f <fasta|fastq> ... or from -Q <sketches.json> ..., not both");
+    if (in.whole_files && in.ref_files.empty() && in.query_files.empty()) refuse(dist_rules, "-g says how -r / -f files are sketched; sketches loaded with -R / -Q are what they are");
+    load_sketch_files(in, dist_rules, ld);
+    const int k = run_k(dist_rules, ld.k);
+    return in.scaled_given || ld.largest_scaled ? dist_scaled(in, ld, k, max_dist) : dist_bottom(in, ld, k, max_dist);
+}
+
+// ------------------------------------------------------------------------------------------------------------------------
+// gather: which references make up a sample, and how much of it each explains once the better matches are taken out (include/
+// rkmh_amd.h, "GATHER").  References and queries are scaled sketches, made or loaded as `dist --scaled` makes and loads them; the
+// references go to the device once, the queries are gathered against them one after the other (rk_gather_scaled_device).
+// Everything that can be refused is refused before a context exists.
+static void help_gather() {
+    fprintf(stderr,
+            "rkmh gather (-r <refs.fa> ... | -R <refs.json> ...) (-f <sample.fa|fq[.gz]> ... | -Q <queries.json> ...) [-k <k>] [--scaled <n>] [-g]\n"
+            "            [--min-shared <n>] [--max-rounds <n>] [--device <id>]\n"
+            "  decomposes every query into references, greedily: the reference that holds most of what is left of the query is printed and\n"
+            "  its hashes leave the query, until the best reference holds fewer than --min-shared (default 1) of them or --max-rounds lines\n"
+            "  are printed; one line per pick, query by query: query, rank (from 1), reference, unique/|query| (hashes only this pick\n"
+            "  explains at its turn), total/|query|, total/|reference| (total: all hashes the two share), remaining (hashes of the query\n"
+            "  left unexplained); a query that no reference matches prints nothing\n"
+            "  -f: every file is ONE query, the union of its records (a sample is a file of reads);  -Q: every sketch of the file is a query\n"
+            "  -r: one reference per record, with -g one per FILE;  -R / -Q: scaled sketches written by `rkmh sketch --scaled <m>`\n"
+            "  --scaled <n>: -r / -f files are sketched at n, -R / -Q files (m <= n) are cut down to n; without it: the largest m among the\n"
+            "  files; not with -s (bottom-s sketches cannot be decomposed)\n" HASH_POLICY_HELP);
+}
+static const CompareRules gather_rules = {"gather", "gather", "gather decomposes scaled ones (rkmh sketch --scaled)", true, nullptr};
+int main_gather(int argc, char** argv) {
+    CompareInputs in;
+    int min_shared = 1, max_rounds = 0x7fffffff;
+    bool min_ok = true, rounds_ok = true;
+    if (argc <= 2) { help_gather(); exit(1); }
+    static struct option long_options[] = {COMPARE_OPTIONS, {"min-shared", required_argument, 0, 1006}, {"max-rounds", required_argument, 0, 1007}, {0, 0, 0, 0}};
+    optind = 2;
+    int c;
+    while ((c = getopt_long(argc, argv, "hgk:f:r:R:Q:s:", long_options, nullptr)) != -1) {
+        if (shared_option(c, in)) continue;
+        switch (c) {
+            case 1006: min_ok = parse_at_least_1(optarg, min_shared); break;
+            case 1007: rounds_ok = parse_at_least_1(optarg, max_rounds); break;
+            default: help_gather(); exit(1);
+        }
+    }
+    LoadedSides ld;
+    ld.k = one_k(in, gather_rules);
+    if (in.S != 0) refuse(gather_rules, "-s makes bottom-s sketches, which cannot be decomposed; gather works on scaled ones (--scaled)");
+    if (in.scaled_given && !in.scaled_ok) refuse(gather_rules, "--scaled takes a number of at least 1");
+    if (!min_ok) refuse(gather_rules, "--min-shared takes a number of at least 1");
+    if (!rounds_ok) refuse(gather_rules, "--max-rounds takes a number of at least 1");
+    if (in.ref_files.empty() == in.ref_json.empty()) refuse(gather_rules, "references come from -r <fasta> ... or from -R <sketches.json> ..., one of the two");
+    if (in.query_files.empty() == in.query_json.empty()) refuse(gather_rules, "queries come from -f <fasta|fastq> ... or from -Q <sketches.json> ..., one of the two");
+    if (in.whole_files && in.ref_files.empty()) refuse(gather_rules, "-g says how -r files are sketched; sketches loaded with -R are what they are");
+    load_sketch_files(in, gather_rules, ld);
+    if (!in.scaled_given && ld.largest_scaled == 0) refuse(gather_rules, "no sketch file says at which scaled to sketch: give --scaled <n>");
+    const int k = run_k(gather_rules, ld.k);
+    ScaledRun run;
+    start_scaled_run(in, gather_rules, ld, k, run);
+    rk_ctx* ctx = run.ctx;
+    const ScaledSet &sr = run.refs, &sq = *run.queries;
+    const size_t nq = sq.names.size(), nr = sr.names.size();
+    if (nr > 0x7fffffffull) refuse(gather_rules, "more than 2^31-1 reference sketches");
+    // the references go to the device once; every query follows them into the same two arrays
+    uint64_t longest = 0;
+    for (size_t i = 0; i < nq; ++i) longest = std::max(longest, sq.off[i + 1] - sq.off[i]);
+    if (longest > 0x7fffffffull) refuse(gather_rules, "a query of more than 2^31-1 hashes");
+    const int rows = (int)std::min<size_t>((size_t)max_rounds, nr);
+    void *d_rv = nullptr, *d_ro = nullptr, *d_q = nullptr, *d_out = nullptr;
+    CK(rk_device_alloc(ctx, sr.values.size() * 8, &d_rv));
+    CK(rk_device_alloc(ctx, sr.off.size() * 8, &d_ro));
+    CK(rk_device_alloc(ctx, (size_t)longest * 8, &d_q));
+    CK(rk_device_alloc(ctx, (size_t)rows * 16, &d_out));
+    CK(rk_device_upload(ctx, d_rv, sr.values.data(), sr.values.size() * 8));
+    CK(rk_device_upload(ctx, d_ro, sr.off.data(), sr.off.size() * 8));
+    std::vector<int32_t> out4((size_t)rows * 4);
+    OutBuf o(stdout);
+    for (size_t i = 0; i < nq; ++i) {
+        const uint64_t lq = sq.off[i + 1] - sq.off[i];
+        int n = 0;
+        CK(rk_device_upload(ctx, d_q, sq.values.data() + sq.off[i], (size_t)lq * 8));
+        CK(rk_gather_scaled_device(ctx, d_q, lq, d_rv, d_ro, (int)nr, sr.values.size(), min_shared, rows, d_out, &n, rk_ctx_stream(ctx)));
+        CK(rk_device_download(ctx, out4.data(), d_out, (size_t)n * 16));
+        for (int t = 0; t < n; ++t) {
+            const int32_t* r = &out4[(size_t)t * 4];
+            const size_t ref = (size_t)r[0];
+            if (ref >= nr) { fprintf(stderr, "rkmh gather: row %d names reference %d of %zu\n", t, r[0], nr); exit(1); }
+            o.append(sq.names[i]);
+            o.appendf("\t%d\t", t + 1);
+            o.append(sr.names[ref]);
+            o.appendf("\t%d/%llu\t%d/%llu\t%d/%llu\t%d\n", r[1], (unsigned long long)lq, r[2], (unsigned long long)lq, r[2], (unsigned long long)(sr.off[ref + 1] - sr.off[ref]), r[3]);
+        }
+        o.end_row();
+    }
+    o.flush();
+    fflush(stdout);
+    for (void* p : {d_rv, d_ro, d_q, d_out}) rk_device_free(ctx, p);
+    rk_ctx_destroy(ctx);
+    return 0;
+}

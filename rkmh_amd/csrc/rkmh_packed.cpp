@@ -1,4 +1,5 @@
-// rkmh_packed.cpp -- reads written by `rkmh pack` (stream / filter -F): the mapped file, its blocks through the devices, with or without -M.
+// rkmh_packed.cpp -- reads written by `rkmh pack` (stream / filter -F): the mapped file, its blocks through the devices, with or without -M;
+// and `pack`, the command that writes them.
 #include <fcntl.h>
 #include <sys/mman.h>
 #include <sys/stat.h>
@@ -167,4 +168,128 @@ void run_packed(DeviceGroup& g, const rk_seqset& refs, const Opts& o, const std:
     }
     stream_packed(g, refs, o, files, kind, nullptr);
     tick("packed reads: classify + format", t0);
+}
+
+// ------------------------------------------------------------------------------------------------------------------------
+// Packed reads: `rkmh pack` writes them, `stream|filter -F` reads them (include/rkmh_amd.h, "PACKED READS").  The reference parses
+// -F/--pre-reads and does nothing with it (src/rkmh.cpp:659-664); here it names reads that were parsed ONCE: 2 bits per base, the
+// names and (optionally) the quality strings kept for the host -- a run then moves ~42 bytes per 150-base read over the link
+// instead of 315 of FASTQ text, parses nothing, and formats its lines from the names where they lie in the mapped file.
+static void help_pack() {
+    fprintf(stderr,
+            "rkmh pack -f <reads.fq|fa[.gz]> [-f ...] -o <out.rkp> [--no-quals] [--block-reads <n>]\n"
+            "  writes the reads as a packed file (2 bits per base, names, quality strings unless --no-quals) that\n"
+            "  `rkmh stream|filter -F <out.rkp>` classifies without parsing; independent of k, sketch size and hashing policy\n");
+}
+int main_pack(int argc, char** argv) {
+    std::vector<const char*> files;
+    const char* outp = nullptr;
+    bool keep_quals = true;
+    long block_reads = 1 << 20;
+    if (argc <= 2) { help_pack(); exit(1); }
+    static struct option long_options[] = {{"help", no_argument, 0, 'h'}, {"fasta", required_argument, 0, 'f'}, {"output", required_argument, 0, 'o'},
+                                           {"no-quals", no_argument, 0, 1010}, {"block-reads", required_argument, 0, 1011}, {"threads", required_argument, 0, 't'}, {0, 0, 0, 0}};
+    optind = 2;
+    int c;
+    while ((c = getopt_long(argc, argv, "hf:o:t:", long_options, nullptr)) != -1) {
+        switch (c) {
+            case 'f': files.push_back(optarg); break;
+            case 'o': outp = optarg; break;
+            case 't': break;
+            case 1010: keep_quals = false; break;
+            case 1011: block_reads = atol(optarg); break;
+            default: help_pack(); exit(1);
+        }
+    }
+    if (files.empty() || !outp) { help_pack(); exit(1); }
+    if (block_reads < 1024 || block_reads > (16 << 20)) { fprintf(stderr, "rkmh pack: --block-reads must lie between 1024 and 16777216\n"); exit(1); }
+    FILE* fo = fopen(outp, "wb");
+    if (!fo) { fprintf(stderr, "rkmh pack: cannot write %s\n", outp); exit(1); }
+    rk_packed_header hdr;
+    memset(&hdr, 0, sizeof hdr);
+    memcpy(hdr.magic, RK_PACKED_MAGIC, 8);
+    hdr.version = 1;
+    std::vector<rk_packed_block> dir;
+    uint64_t at = 0;
+    bool quals_everywhere = keep_quals;
+    auto put = [&](const void* p, size_t n) { if (n && fwrite(p, 1, n, fo) != n) { fprintf(stderr, "rkmh pack: write error on %s\n", outp); exit(1); } at += n; };
+    auto align16 = [&]() { static const char z[16] = {0}; const size_t pad = (size_t)((16 - (at & 15)) & 15); put(z, pad); };
+    put(&hdr, sizeof hdr); // (rewritten at the end)
+    const int nt = std::max(1, std::min(granted_cpus_main(), 16));
+    std::vector<uint8_t> b2;
+    std::vector<std::vector<rk_packed_exception>> exc_t((size_t)nt);
+    std::vector<uint32_t> offs, noffs;
+    std::vector<char> names;
+    for (const char* path : files) {
+        rk_reader* rd = nullptr;
+        CK(rk_reader_open(path, &rd));
+        if (!keep_quals) rk_reader_set_options(rd, RK_READER_NO_QUALS);
+        for (;;) {
+            rk_seqset s;
+            CK(rk_reader_next(rd, block_reads, (uint64_t)3 << 30, &s));
+            if (s.nseq == 0) { rk_seqset_free(&s); break; }
+            const uint64_t b0 = s.offsets[0], nb = s.offsets[s.nseq] - b0;
+            if (nb >= ((uint64_t)1 << 32) - 64 || s.nseq > 0x7ffffff0ll) { fprintf(stderr, "rkmh pack: a block of more than 4 G bases\n"); exit(1); }
+            rk_packed_block blk;
+            memset(&blk, 0, sizeof blk);
+            blk.nrec = (uint32_t)s.nseq; blk.nbases = nb;
+            offs.resize((size_t)s.nseq + 1);
+            uint32_t maxlen = 0;
+            for (int64_t i = 0; i <= s.nseq; ++i) offs[(size_t)i] = (uint32_t)(s.offsets[i] - b0);
+            for (int64_t i = 0; i < s.nseq; ++i) maxlen = std::max(maxlen, offs[(size_t)i + 1] - offs[(size_t)i]);
+            blk.max_len = maxlen;
+            // 2-bit bases and exceptions: pieces of whole bytes (4 bases), a thread each
+            b2.assign((size_t)((nb + 3) / 4), 0);
+            {
+                std::vector<std::thread> th;
+                const uint64_t per = (((nb + (uint64_t)nt - 1) / (uint64_t)nt) + 3) & ~(uint64_t)3;
+                for (int t = 0; t < nt; ++t)
+                    th.emplace_back([&, t] {
+                        const uint64_t lo = std::min(nb, per * (uint64_t)t), hi = std::min(nb, lo + per);
+                        auto& ex = exc_t[(size_t)t];
+                        ex.resize((size_t)(hi - lo) + 1);
+                        const int64_t ne = rk_packed_encode(s.bases + b0 + lo, hi - lo, lo, b2.data() + lo / 4, ex.data(), ex.size());
+                        if (ne < 0) { fprintf(stderr, "rkmh pack: %s\n", rk_last_error()); fail_exit(); }
+                        ex.resize((size_t)ne);
+                    });
+                for (auto& t : th) t.join();
+            }
+            noffs.resize((size_t)s.nseq + 1);
+            names.clear();
+            for (int64_t i = 0; i < s.nseq; ++i) {
+                noffs[(size_t)i] = (uint32_t)names.size();
+                const char* nm = s.names + s.name_offsets[i];
+                names.insert(names.end(), nm, nm + (s.name_offsets[i + 1] - s.name_offsets[i] - 1)); // (the offsets include the NUL)
+            }
+            noffs[(size_t)s.nseq] = (uint32_t)names.size();
+            if (names.size() >= ((uint64_t)1 << 32)) { fprintf(stderr, "rkmh pack: more than 4 GB of names in one block\n"); exit(1); }
+            blk.name_bytes = names.size();
+            align16(); blk.offsets_off = at; put(offs.data(), offs.size() * 4);
+            align16(); blk.bases_off = at; put(b2.data(), b2.size());
+            { static const char z[16] = {0}; put(z, 16); } // (the bases are uploaded in whole dwords; the unpacked tail is never read)
+            align16(); blk.exc_off = at;
+            uint64_t nexc = 0;
+            for (auto& ex : exc_t) { put(ex.data(), ex.size() * sizeof(rk_packed_exception)); nexc += ex.size(); }
+            if (nexc > 0xffffffffull) { fprintf(stderr, "rkmh pack: too many non-ACGT bases in one block\n"); exit(1); }
+            blk.nexc = (uint32_t)nexc;
+            align16(); blk.name_offsets_off = at; put(noffs.data(), noffs.size() * 4);
+            align16(); blk.names_off = at; put(names.data(), names.size());
+            { static const char z[32] = {0}; put(z, 32); } // (the formatters copy names in 16-byte steps)
+            if (keep_quals && s.quals) { align16(); blk.quals_off = at; put(s.quals + b0, (size_t)nb); }
+            else quals_everywhere = false;
+            dir.push_back(blk);
+            hdr.nreads += (uint64_t)s.nseq; hdr.nbases += nb;
+            rk_seqset_free(&s);
+        }
+        rk_reader_close(rd);
+    }
+    if (!quals_everywhere) for (auto& b : dir) b.quals_off = 0; // (all or nothing: a file that keeps qualities keeps them for every read)
+    align16();
+    hdr.directory_off = at; hdr.nblocks = dir.size(); hdr.flags = quals_everywhere && !dir.empty() ? RK_PACKED_QUALS : 0u;
+    put(dir.data(), dir.size() * sizeof(rk_packed_block));
+    { static const char z[64] = {0}; put(z, 64); }
+    if (fseek(fo, 0, SEEK_SET) != 0 || fwrite(&hdr, sizeof hdr, 1, fo) != 1 || fclose(fo) != 0) { fprintf(stderr, "rkmh pack: write error on %s\n", outp); exit(1); }
+    fprintf(stderr, "rkmh pack: %llu reads, %llu bases in %zu blocks%s -> %s (%.1f bytes per read)\n", (unsigned long long)hdr.nreads, (unsigned long long)hdr.nbases, dir.size(),
+            hdr.flags & RK_PACKED_QUALS ? ", with qualities" : "", outp, hdr.nreads ? (double)(at + dir.size() * sizeof(rk_packed_block)) / (double)hdr.nreads : 0.0);
+    return 0;
 }
