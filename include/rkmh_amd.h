@@ -239,6 +239,35 @@ int rk_set_kmer_form(rk_ctx* ctx, int enable);
 int rk_set_kmer_cache(rk_ctx* ctx, const char* path);
 int rk_kmer_cache_state(const rk_ctx* ctx);
 
+/* What the index of this context was built as (host only, read only: counters that the last index build filled as it went).
+ * Every key of the index (a distinct sketch hash) takes one of several value forms, chosen by thresholds that the kernels decode
+ * again on their side ("Index value forms"); these counters say which form each key took, so a test can build a key
+ * at a threshold and prove on which side it fell.
+ *   hash-space index   keys, buckets; buckets_overflowed = buckets whose overflow flag is set; longest_chain = the largest number
+ *                      of buckets a stored key lies past its home bucket, plus one (1: every key is at home); chain_wrapped = 1
+ *                      when some key was stored in a lower-numbered bucket than its home (the chain ran past the last bucket)
+ *   values, per key    single_once (one reference, multiplicity 1), single_multi (one reference, 2 .. 511), pair (two references
+ *                      below 2048 once each, 11 + 11 bits), list (a posting list: everything else); list_longest = entries of the
+ *                      longest list, post_words = 32-bit words of the posting array
+ *   k-mer-space form   all zero when it is not built (rk_kmer_form returns 0).  kmer_form = 1; bases_kept = base lists in use;
+ *                      bases_dropped_by_share_rule = 1 when bases were chosen and the 5 % rule cleared them; per key found by the
+ *                      enumeration, as the value table classifies it: kv_reference (the value id is the reference), kv_single_multi,
+ *                      kv_pair, kv_inline_list (3 .. 6 references below 512 once each, tag 11), kv_base_inline (base and up to eight
+ *                      exceptions in the value, tag 111), kv_base_list (a (base, exceptions) list in the posting array),
+ *                      kv_plain_list; per k-mer size of the run, in the order given: km1_bits (log2 of the exact map's buckets),
+ *                      km1_longest_hop (buckets past its own of the farthest cell), kf4_sectors, found (k-mers enumerated)
+ * The caller sets out->struct_size = sizeof(rk_index_stats_t) as it was compiled; at most that many bytes are written, and
+ * struct_size comes back as the number written (the structure may grow at its end).  RK_ERR_STATE before any references are set. */
+typedef struct rk_index_stats_t {
+    uint32_t struct_size;
+    uint32_t keys, buckets, buckets_overflowed, longest_chain, chain_wrapped;
+    uint32_t single_once, single_multi, pair, list, list_longest, post_words;
+    uint32_t kmer_form, bases_kept, bases_dropped_by_share_rule;
+    uint32_t kv_reference, kv_single_multi, kv_pair, kv_inline_list, kv_base_inline, kv_base_list, kv_plain_list;
+    uint32_t km1_bits[RK_MAX_KS], km1_longest_hop[RK_MAX_KS], kf4_sectors[RK_MAX_KS], found[RK_MAX_KS];
+} rk_index_stats_t;
+int rk_index_stats(const rk_ctx* ctx, rk_index_stats_t* out);
+
 /* Read-depth filter (-M, src/rkmh.cpp:701-704): when set, classify masks hashes whose counter
  * value is below min_kmer_occ (mask_by_frequency, :916) before sketching.  NULL disables.
  * The table is read as it is AT THIS CALL (the fused kernel uses a one-bit-per-slot snapshot of the comparison): set the

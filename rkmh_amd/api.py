@@ -69,6 +69,16 @@ def library_path():
     return os.path.join(_HERE, "lib", "librkmh_amd.so")
 
 
+class IndexStats(C.Structure):
+    """rk_index_stats_t: which form each key of the index took (rkmh_amd.h)"""
+    _fields_ = ([(n, C.c_uint32) for n in (
+        "struct_size", "keys", "buckets", "buckets_overflowed", "longest_chain", "chain_wrapped",
+        "single_once", "single_multi", "pair", "list", "list_longest", "post_words",
+        "kmer_form", "bases_kept", "bases_dropped_by_share_rule",
+        "kv_reference", "kv_single_multi", "kv_pair", "kv_inline_list", "kv_base_inline", "kv_base_list", "kv_plain_list")]
+        + [(n, C.c_uint32 * 8) for n in ("km1_bits", "km1_longest_hop", "kf4_sectors", "found")])
+
+
 _u8p, _u64p, _i32p, _ip = C.POINTER(C.c_uint8), C.POINTER(C.c_uint64), C.POINTER(C.c_int32), C.POINTER(C.c_int)
 
 _SIGS = {
@@ -113,6 +123,7 @@ _SIGS = {
     "rk_classify_groups_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
     "rk_kmer_form": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
     "rk_set_kmer_form": (C.c_int, [C.c_void_p, C.c_int]),
+    "rk_index_stats": (C.c_int, [C.c_void_p, C.POINTER(IndexStats)]),
     "rk_device_props": (C.c_int, [C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "rk_counter_save": (C.c_int, [C.c_void_p, C.c_char_p]),
     "rk_counter_load": (C.c_int, [C.c_void_p, C.c_char_p]),
@@ -1256,6 +1267,15 @@ class Context:
         r = self._lib.rk_kmer_form(self._h, C.byref(n))
         _chk(min(r, 0))
         return bool(r), n.value
+
+    def index_stats(self) -> dict:
+        """What the index of the references now set was built as (rk_index_stats): counters per value form; the per-k arrays as
+        lists over the k-mer sizes of the run."""
+        st = IndexStats()
+        st.struct_size = C.sizeof(IndexStats)
+        _chk(self._lib.rk_index_stats(self._h, C.byref(st)))
+        nk = len(self.ks)
+        return {n: (list(getattr(st, n))[:nk] if t is not C.c_uint32 else int(getattr(st, n))) for n, t in IndexStats._fields_ if n != "struct_size"}
 
     def classify_groups(self, bases, offsets, argmax_refs):
         """hpv16's per-read loop: (out4 [n,4] over the first argmax_refs references, counts [n, nref - argmax_refs] of the rest)."""

@@ -135,6 +135,7 @@ struct rk_ctx {
     int kmer_cache_state = 0; // of the last index build: 0 no file given, 1 loaded, 2 enumerated and written, 3 enumerated (the file could not be written)
     RefIndex ix{};
     bool have_refs = false;
+    rk_index_stats_t istats{}; // rk_index_stats: which form each key of the index took, counted by build_index / build_kpost as they go
     double density = 1.0; // fraction of a reference's k-mers that its sketch keeps (largest over references)
     std::mutex general_mu; // the general path (rerouted rows) works in the context's own buffers: FASTQ slots take turns
     // -M

@@ -18,7 +18,7 @@
 constexpr int KBASE_MAX = 8;
 struct KList { uint32_t enc = 0, plain = 0, ix = 0, iy = 0, iw = 0; };
 static void build_kpost(const std::vector<uint32_t>& post, int R, std::vector<uint32_t>& kpost, std::vector<uint32_t>& kbase,
-                        std::unordered_map<uint32_t, KList>& remap) {
+                        std::unordered_map<uint32_t, KList>& remap, rk_index_stats_t& st) {
     struct Dist { std::vector<std::pair<uint32_t, uint32_t>> e; uint32_t weight = 0, plain = 0, enc = 0, ix = 0, iy = 0, iw = 0; bool simple = true; };
     std::map<std::vector<std::pair<uint32_t, uint32_t>>, uint32_t> ids; // list content (sorted by reference) -> distinct id
     std::vector<Dist> dl;
@@ -76,8 +76,9 @@ static void build_kpost(const std::vector<uint32_t>& post, int R, std::vector<ui
             for (auto& b : bases) bd = std::min(bd, sym_diff(d.e, b));
             if (2 * (1 + bd) <= d.e.size()) saved += (uint64_t)d.weight * (d.e.size() - bd - 1);
         }
-        if (saved * 20 < total) bases.clear();
+        if (saved * 20 < total) { bases.clear(); st.bases_dropped_by_share_rule = 1; }
     }
+    st.bases_kept = (uint32_t)bases.size();
     kbase.assign(2 * KBASE_MAX, 0u);
     for (size_t b = 0; b < bases.size(); ++b) {
         kbase[2 * b] = (uint32_t)kbase.size(); kbase[2 * b + 1] = (uint32_t)bases[b].size();
@@ -185,6 +186,7 @@ int build_index(rk_ctx* c) {
     IndexClock clk;
     struct Pair { uint64_t h; uint32_t ref; };
     const int R = c->nref, S = c->S;
+    rk_index_stats_t st{}; // rk_index_stats: filled where each form is chosen, published with have_refs
     if (R > 0xFFFFF) return fail(RK_ERR_LIMIT, "more than 2^20-1 references");
     std::vector<Pair> pairs;
     for (int r = 0; r < R; ++r)
@@ -230,12 +232,16 @@ int build_index(rk_ctx* c) {
             j = k;
         }
         uint32_t v;
-        if (grp.size() == 1 && grp[0].second <= 0x1FFu) v = grp[0].first | (grp[0].second << 20);
-        else if (grp.size() == 2 && grp[0].second == 1 && grp[1].second == 1 && grp[0].first < 2048 && grp[1].first < 2048)
+        if (grp.size() == 1 && grp[0].second <= 0x1FFu) {
+            v = grp[0].first | (grp[0].second << 20);
+            ++(grp[0].second == 1 ? st.single_once : st.single_multi);
+        } else if (grp.size() == 2 && grp[0].second == 1 && grp[1].second == 1 && grp[0].first < 2048 && grp[1].first < 2048) {
             v = (1u << 29) | grp[0].first | (grp[1].first << 11);
-        else {
+            ++st.pair;
+        } else {
             if (post.size() + 1 + 2 * grp.size() >= 0x3fffffffull) return fail(RK_ERR_LIMIT, "postings overflow"); // (offsets stay below 2^30: the k-mer-space value table uses the two top bits)
             v = 0x80000000u | (uint32_t)post.size();
+            ++st.list; st.list_longest = std::max(st.list_longest, (uint32_t)grp.size());
             post.push_back((uint32_t)grp.size());
             // Order inside a list is free.  The fused kernels walk a list 16 postings per step and add to packed per-reference
             // counters, four (or two) references per LDS word: in ascending order the 16 lanes of a step meet four by four in one word
@@ -245,15 +251,19 @@ int build_index(rk_ctx* c) {
             for (auto& g : grp) { post.push_back(g.first); post.push_back(g.second); }
         }
         uint32_t b = index_bucket(pairs[i].h, bmask);
-        for (;;) {
+        const uint32_t home = b;
+        for (uint32_t chain = 1;; ++chain) {
             uint32_t q = 0;
             while (q < (uint32_t)IDX_SLOTS && fpb[(size_t)IDX_SLOTS * b + q] != 0) ++q;
             if (q < (uint32_t)IDX_SLOTS) {
                 const size_t sl = (size_t)IDX_SLOTS * b + q;
                 fpb[sl] |= (uint16_t)index_fp(pairs[i].h);
                 kv[4 * sl] = (uint32_t)pairs[i].h; kv[4 * sl + 1] = (uint32_t)(pairs[i].h >> 32); kv[4 * sl + 2] = v;
+                st.longest_chain = std::max(st.longest_chain, chain);
+                if (b < home) st.chain_wrapped = 1;
                 break;
             }
+            if (!(fpb[(size_t)IDX_SLOTS * b] & IDX_OVF)) ++st.buckets_overflowed;
             fpb[(size_t)IDX_SLOTS * b] |= (uint16_t)IDX_OVF; // the key goes further down the chain: lookups must follow
             b = (b + 1) & bmask;
         }
@@ -270,6 +280,7 @@ int build_index(rk_ctx* c) {
     }
     const size_t nkeys = base[nb];
     c->nkeys = (uint32_t)nkeys;
+    st.keys = (uint32_t)nkeys; st.buckets = nb; st.post_words = (uint32_t)post.size();
     ++c->index_gen;
     c->ix.keepkey = nullptr; memset(&c->ksets_m, 0, sizeof c->ksets_m); // a depth filter set earlier refers to the old key ids
     std::vector<uint32_t> dense((nkeys + 1) * 4, 0);
@@ -330,7 +341,7 @@ int build_index(rk_ctx* c) {
     std::unordered_map<uint32_t, KList> kremap;
     c->ix.kpost = nullptr; c->ix.kbase = nullptr; c->ix.kbase_n = 0; c->ix.kkeys = nullptr; c->ix.kslots = nullptr;
     if (all_k_ok) {
-        build_kpost(post, R, kpost, kbase, kremap);
+        build_kpost(post, R, kpost, kbase, kremap, st);
         if (kpost.size() >= 0x3fffffffull) all_k_ok = false;
         else {
             RKCHK(c->d_kpost.reserve(kpost.size() * 4));
@@ -411,7 +422,7 @@ int build_index(rk_ctx* c) {
         std::unordered_map<uint32_t, uint32_t> val_id;
         auto value_id_of = [&](uint32_t slot) -> uint32_t {
             const uint32_t val = dense[(size_t)slot * 4 + 2];
-            if (!(val >> 31) && ((val >> 29) & 3u) == 0u && ((val >> 20) & 0x1FFu) == 1u) return val & 0xFFFFFu; // one posting, once: the reference
+            if (!(val >> 31) && ((val >> 29) & 3u) == 0u && ((val >> 20) & 0x1FFu) == 1u) { ++st.kv_reference; return val & 0xFFFFFu; } // one posting, once: the reference
             // lists: identical ones share one compound value (and one copy in kpost, see build_kpost)
             uint32_t vkey = val;
             KList kl;
@@ -443,6 +454,12 @@ int build_index(rk_ctx* c) {
                 }
                 vals.push_back(x); vals.push_back(y); vals.push_back(z); vals.push_back(w);
             }
+            // (rk_index_stats: the form this key's compound value took, read off the value the kernels will decode)
+            const uint32_t* cv = &vals[4 * (size_t)(it->second - (uint32_t)R)];
+            if (!(cv[0] >> 31)) ++(((cv[0] >> 29) & 3u) == 1u ? st.kv_pair : st.kv_single_multi);
+            else if ((cv[0] >> 29) == 7u) ++st.kv_base_inline;
+            else if ((cv[0] >> 30) == 3u) ++st.kv_inline_list;
+            else ++((cv[0] & 0x3fffffffu) != cv[2] ? st.kv_base_list : st.kv_plain_list);
             return it->second;
         };
         if (ok && k > 16) {
@@ -475,10 +492,11 @@ int build_index(rk_ctx* c) {
             while (b < 26 && (double)found > km2_load * 4.0 * (double)((size_t)1 << b)) ++b;
             std::vector<uint32_t> c1;
             bool placed_all = false;
+            uint32_t longest_hop = 0;
             for (; b <= 26 && !placed_all; ++b) {
                 const uint32_t nbk = 1u << b;
                 c1.assign((size_t)nbk * 4, KW_EMPTY); // empty: key number all ones, hop / tag / flag clear
-                placed_all = true;
+                placed_all = true; longest_hop = 0;
                 for (uint32_t i = 0; i < found && placed_all; ++i) {
                     const uint64_t y = kw_y(km[i], k);
                     uint32_t bk = (uint32_t)(y >> (kbits - b));
@@ -489,6 +507,7 @@ int build_index(rk_ctx* c) {
                         for (int q = 0; q < 4 && !placed; ++q)
                             if ((e[q] & KW_EMPTY) == KW_EMPTY) {
                                 e[q] = (e[q] & (1u << KW_IDBITS)) | (((hop << KW_TAG) | tag) << (KW_IDBITS + 1)) | i; // (the flag of a last cell stays)
+                                longest_hop = std::max(longest_hop, hop);
                                 placed = true;
                             }
                         if (!placed) { e[3] |= 1u << KW_IDBITS; bk = (bk + 1) & (nbk - 1); }
@@ -513,6 +532,7 @@ int build_index(rk_ctx* c) {
                 c->ksets.kf4[kidx] = c->d_kf4[(size_t)kidx].as<uint4>(); c->ksets.kf4_n[kidx] = nsect; c->ksets.k[kidx] = k;
                 c->ix.kkeys = c->d_kkeys.as<uint2>(); c->ix.kslots = c->d_kslots.as<uint32_t>();
                 c->km1_ncells[kidx] = 0;
+                st.km1_bits[kidx] = b; st.km1_longest_hop[kidx] = longest_hop; st.kf4_sectors[kidx] = nsect; st.found[kidx] = found;
                 ++built;
             }
             clk.tick("wide filter + map");
@@ -574,12 +594,14 @@ int build_index(rk_ctx* c) {
                 std::vector<uint32_t> c1;
                 std::vector<uint32_t> cell_of(found); // where each found k-mer was placed (rk_set_depth_filter masks cells by key)
                 bool built = false;
+                uint32_t longest_hop = 0;
                 for (; b <= kbits && b <= 28 && !built; ++b) {
                     const uint32_t r = kbits - b, vb = km1_vbits(k, b), vmask = (1u << vb) - 1u;
                     if ((uint64_t)R + vals.size() / 4 + 2 > (uint64_t)vmask) continue; // ids need more bits: a longer bucket index frees them
                     const uint32_t nbk = 1u << b, rmask = r ? (1u << r) - 1u : 0u;
                     c1.assign((size_t)nbk * 4, ~(1u << vb)); // empty: tag and id all ones, flag clear
                     bool placed_all = true;
+                    longest_hop = 0;
                     for (uint32_t i = 0; i < found && placed_all; ++i) {
                         const uint32_t y = km1_y(list[2 * (size_t)i], k);
                         uint32_t bk = r ? y >> r : y;
@@ -591,6 +613,7 @@ int build_index(rk_ctx* c) {
                                 if ((e[q] & vmask) == vmask) { // empty (no key carries the all-ones id)
                                     e[q] = ((rem | (hop << r)) << (vb + 1)) | id;
                                     cell_of[i] = bk * 4u + (uint32_t)q;
+                                    longest_hop = std::max(longest_hop, hop);
                                     placed = true;
                                 }
                             if (!placed) { e[3] |= 1u << vb; bk = (bk + 1) & (nbk - 1); } // full: later lookups that miss here try the next bucket
@@ -612,6 +635,7 @@ int build_index(rk_ctx* c) {
                     RKCHK(c->d_km1cells[(size_t)kidx].reserve(cells.size() * 4 + 16));
                     if (found) HIPCHK(hipMemcpy(c->d_km1cells[(size_t)kidx].p, cells.data(), cells.size() * 4, hipMemcpyHostToDevice));
                     c->km1_ncells[kidx] = found; c->km1_vmask[kidx] = (1u << km1_vbits(k, b)) - 1u;
+                    st.km1_bits[kidx] = b; st.km1_longest_hop[kidx] = longest_hop; st.kf4_sectors[kidx] = nsect; st.found[kidx] = found;
                 }
             }
             DevBuf& d_kf4 = c->d_kf4[(size_t)kidx];
@@ -628,7 +652,13 @@ int build_index(rk_ctx* c) {
         c->ksets.n = built;
         c->ix.kf4 = c->ksets.kf4[0]; c->ix.kf4_n = c->ksets.kf4_n[0]; c->ix.km1 = c->ksets.km1[0]; c->ix.km1_b = c->ksets.km1_b[0];
         c->ix.km1_vals = c->ksets.km1_vals[0]; c->ix.kpk = (uint32_t)c->ksets.k[0];
-    } else memset(&c->ksets, 0, sizeof c->ksets);
+        st.kmer_form = 1;
+    } else {
+        memset(&c->ksets, 0, sizeof c->ksets);
+        memset(&st.kmer_form, 0, sizeof st - offsetof(rk_index_stats_t, kmer_form)); // not built: every k-mer-space counter reads 0
+    }
+    st.struct_size = (uint32_t)sizeof st;
+    c->istats = st;
     // a full bottom-S sketch of uniform hashes keeps the fraction (largest kept hash / 2^64) of the k-mers
     c->density = 0.0;
     for (int r = 0; r < R; ++r) {
@@ -715,6 +745,15 @@ extern "C" int rk_set_kmer_cache(rk_ctx* c, const char* path) {
     return RK_OK;
 }
 extern "C" int rk_kmer_cache_state(const rk_ctx* c) { return c ? c->kmer_cache_state : 0; }
+extern "C" int rk_index_stats(const rk_ctx* c, rk_index_stats_t* out) {
+    if (!c || !out) return fail(RK_ERR_ARG, "bad arguments");
+    if (!c->have_refs) return fail(RK_ERR_STATE, "no references set");
+    if (out->struct_size < sizeof(uint32_t)) return fail(RK_ERR_ARG, "struct_size is not set");
+    const uint32_t n = std::min<uint32_t>(out->struct_size, (uint32_t)sizeof c->istats);
+    memcpy(out, &c->istats, n);
+    out->struct_size = n;
+    return RK_OK;
+}
 extern "C" int rk_kmer_form(const rk_ctx* c, uint32_t* kmers_found) {
     if (!c) return fail(RK_ERR_ARG, "ctx is NULL");
     if (!c->have_refs) return fail(RK_ERR_STATE, "no references set");
