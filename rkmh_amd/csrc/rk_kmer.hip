@@ -33,8 +33,15 @@ constexpr int KW = 64;
 constexpr int KM_MAX_T = 8;          // reads per tile (phase 2 takes eight reads in one pass; the group -> read search is unrolled for it)
 constexpr int KM_MQ = 32;            // deferred multi-posting hits (a full list is worked off at once: 16 lanes per hit)
 // (the timing experiments this kernel was shaped by -- parts switched off, loads faked -- live in tools/ubench/rk_kmer_ablation.hip, not here)
-constexpr int KM_CH = 2;             // steps (64 groups = 256 windows each) whose filter sectors are requested together
-constexpr int KM_QCAP = 64 + 4 * KW; // candidate queue entries (4 bytes each): a step adds at most 256 to a remainder of < 64
+constexpr int KM_CH = 4;             // steps (64 groups = 256 windows each) whose filter sectors are requested together (k_classify_kmer: CH)
+// candidate queue: 16-bit entries in 1280 bytes.  A step adds at most 4 KW = 256 entries and is only started when that many are free
+// (no per-push bounds check), so a tile whose candidates stay below 640 - 256 before its last step -- every tile of reads at a
+// panel's usual key density -- is drained ONCE, after its last step; a tile dense with hits drains whole waves of 64 whenever the next
+// step might not fit and carries the remainder (< 64) forward.
+constexpr int KM_QDW = 64 + 4 * KW;  // dwords of the queue
+constexpr int KM_QCAP = 2 * KM_QDW;  // entries
+static_assert(KM_QCAP * sizeof(uint16_t) == 1280, "the queue keeps its 1280 bytes: the LDS layout behind it, T and 8 waves per SIMD depend on it");
+static_assert(KW - 1 + 4 * KW <= KM_QCAP, "after a mid-tile drain (remainder < 64) the next step always fits: the window loop makes progress");
 constexpr int KM_LDS_SMALL = 5120;   // static LDS of the common instantiation: 32 single-wave workgroups per CU (8 per SIMD)
 constexpr int KM_LDS_BIG = 20480;    // ... of the one for large hit multisets / counter rows (8 per CU)
 constexpr int KM_WAVES = 8;
@@ -62,8 +69,9 @@ template <int NQ>
 struct KmLds {
     static constexpr int PK = 0;                              // packed 2-bit image of the staged quads + two zero dwords (position P = byte P of the quads)
     static constexpr int INV = PK + NQ * 64 + 2;              // bit P set <=> base P is not ACGT (built only for tiles that hold one)
-    static constexpr int Q = INV + NQ * 32 + 2;               // candidate queue: P | read << 12 (read 8: a lane without a group; rinfo[8] has no windows)
-    static constexpr int MQ = Q + KM_QCAP;                    // [KM_MQ][2] deferred hits with a posting list: read | rank << 8, list offset
+    static constexpr int Q = INV + NQ * 32 + 2;               // candidate queue, 16-bit entries: P | read << 12 (read 8: a lane without a group; rinfo[8] has no windows)
+    static constexpr int MQ = Q + KM_QDW;                     // [KM_MQ][2] deferred hits with a posting list: read | rank << 8, list offset
+    static_assert(((NQ * 1024 + 3) | (KM_MAX_T << 12)) <= 0xFFFF && NQ * 1024 + 3 < (1 << 12), "a queue entry fits 16 bits: P <= the padding's position + 3, read <= 8");
     static constexpr int RI = MQ + 2 * KM_MQ;                 // [9] uint4 {start position, windows, first group, -} of read t
     static constexpr int NZ = RI + 4 * (KM_MAX_T + 1);        // [8] zero hashes of read t
     static constexpr int BEST = NZ + KM_MAX_T;                // [8] sparse counters: max over increments of (count << 16 | 0xFFFF - ref)
@@ -144,13 +152,17 @@ __global__ __launch_bounds__(KW, BIG ? 2 : KM_WAVES) void k_classify_kmer(const 
     // KT = 32: ONE k-mer size from 17 to KW_MAX_K, known at run time (ix.kpk): wide k-mers, 64-bit arithmetic, the km2 map (rk_device.hpp)
     static_assert(KT == 0 || KT == 32 || (KT >= 4 && KT <= 16), "a k-mer packs into 32 bits; the core is the (k-3)-mer");
     constexpr bool WIDE = KT == 32;
+    // steps whose filter sectors are requested together: all four of a tile of up to 1009 bases (the queue holds two and a half
+    // steps' worth, so a tile at a panel's usual key density tests them all before its one drain); two where four steps' sectors and
+    // windows do not fit the 64 VGPRs of 8 waves per SIMD (several k-mer sizes, wide k-mers: they would spill to scratch)
+    constexpr int CH = (KT == 0 || WIDE) ? 2 : KM_CH;
     using L = KmLds<NQ>;
     __shared__ __attribute__((aligned(16))) uint32_t smem[(BIG ? KM_LDS_BIG : KM_LDS_SMALL) / 4];
     constexpr uint32_t PAD_P = NQ * 1024;       // position of the image's zero padding: where lanes without a group look
     constexpr uint32_t clg = CMODE == CM_DENSE8 ? 2 : 1, cbits = 32u >> clg, cmask = (1u << cbits) - 1u;
     uint32_t* const pk = smem + L::PK;
     uint32_t* const inv = smem + L::INV;
-    uint32_t* const q = smem + L::Q;
+    uint16_t* const q = reinterpret_cast<uint16_t*>(smem + L::Q);
     uint32_t* const mq = smem + L::MQ;
     uint4* const rinfo = reinterpret_cast<uint4*>(smem + L::RI);
     uint32_t* const nzero = smem + L::NZ;
@@ -444,7 +456,7 @@ __global__ __launch_bounds__(KW, BIG ? 2 : KM_WAVES) void k_classify_kmer(const 
         auto lookup = [&](uint32_t e, uint32_t qn) -> Cand {
             Cand c;
             uint32_t ent = PAD_P | (8u << 12); // past the queue's end: the all-A k-mer of the padding, of read 8 which has no windows
-            if (e < qn) ent = q[e];
+            if (e < qn) ent = q[e]; // ds_read_u16
             const uint32_t P = ent & 4095u, t = ent >> 12;
             const km_pair1 w = *reinterpret_cast<const km_pair1*>(reinterpret_cast<const uint8_t*>(pk) + (P >> 2));
             const uint2 ri = *reinterpret_cast<const uint2*>(&rinfo[t]);
@@ -626,7 +638,7 @@ __global__ __launch_bounds__(KW, BIG ? 2 : KM_WAVES) void k_classify_kmer(const 
             if (mqn) process_mq();
         };
 
-        // ---- window phase: 64 groups (256 windows) per step, KM_CH steps' filter sectors requested together ---------------------
+        // ---- window phase: 64 groups (256 windows) per step, CH steps' filter sectors requested together ---------------------
         const uint32_t nsteps = (NG + KW - 1) / KW;
         // a last step of 1 .. 16 groups runs a QUARTER wide: four lanes per group, one window (and one dword of the sector) each --
         // a fourth of the window tests for the step that would otherwise run 64 lanes for a dozen groups (six 150-base reads: 204 groups)
@@ -637,11 +649,11 @@ __global__ __launch_bounds__(KW, BIG ? 2 : KM_WAVES) void k_classify_kmer(const 
         for (;;) {
             // issue: every lane computes; a lane without a group looks at the image's zero padding (the all-A k-mer) and tags its
             // candidates, should the filter pass that k-mer, with read 8, which has no windows -- the drain drops them
-            uint32_t wl[KM_CH], wh[KM_CH], e0v[KM_CH], fq[KM_CH];
-            u32x4 fw[KM_CH];
-            bool isqv[KM_CH];
+            uint32_t wl[CH], wh[CH], e0v[CH], fq[CH];
+            u32x4 fw[CH];
+            bool isqv[CH];
 #pragma unroll
-            for (int s = 0; s < KM_CH; ++s) {
+            for (int s = 0; s < CH; ++s) {
                 const bool isq = qlast && step + (uint32_t)s + 1u == nsteps; // wave-uniform
                 isqv[s] = isq;
                 const uint32_t jq = isq ? (uint32_t)lane & 3u : 0u;
@@ -677,8 +689,6 @@ __global__ __launch_bounds__(KW, BIG ? 2 : KM_WAVES) void k_classify_kmer(const 
                 } else fw[s] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const uint8_t*>(kf4p) + sect_b);
             }
             // test + push.  has_invalid (a tile with a non-ACGT base, rare) runs its own copy of the code.
-            bool stop = false;
-            uint32_t done = 0;
             auto test_step = [&](int s, auto inv_tag, auto nw_tag) {
                 constexpr bool INV = decltype(inv_tag)::value;
                 constexpr int NW = decltype(nw_tag)::value; // windows this lane tests: 4, or 1 in a quarter-wide step (wl / fq / e0v are then that window's)
@@ -712,35 +722,36 @@ __global__ __launch_bounds__(KW, BIG ? 2 : KM_WAVES) void k_classify_kmer(const 
                     // inverse_ballot turns the mask back into the branch predicate (no second compare for the exec mask)
                     if (__builtin_amdgcn_inverse_ballot_w64(m)) {
                         const uint32_t mb = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-                        *reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(q) + ((mb << 2) + (qcount << 2))) = e0v[s] + (uint32_t)j;
+                        *reinterpret_cast<uint16_t*>(reinterpret_cast<uint8_t*>(q) + ((mb << 1) + (qcount << 1))) = (uint16_t)(e0v[s] + (uint32_t)j); // ds_write_b16
                     }
                     qcount += (uint32_t)__builtin_popcountll(m);
                 }
                 if constexpr (INV) { if (nz) atomicAdd(&nzero[t_], nz); }
             };
 #pragma unroll
-            for (int s = 0; s < KM_CH; ++s) {
-                if (step + (uint32_t)s < nsteps && !stop) { // wave-uniform
-                    if (qcount + 4u * KW > (uint32_t)KM_QCAP) stop = true;
-                    else {
-                        ++done;
-                        if (isqv[s]) { // wave-uniform
-                            if (has_invalid) test_step(s, std::true_type{}, std::integral_constant<int, 1>{});
-                            else test_step(s, std::false_type{}, std::integral_constant<int, 1>{});
-                        } else if (has_invalid) test_step(s, std::true_type{}, std::integral_constant<int, 4>{});
-                        else test_step(s, std::false_type{}, std::integral_constant<int, 4>{});
-                    }
-                }
+            for (int s = 0; s < CH; ++s) {
+                // wave-uniform; the steps of an issue run in order, so a step that does not run (the tile is over, or the queue
+                // may not hold its 256 entries) ends the issue: `step` then names it, and it is issued again after the drain
+                if (step < nsteps && qcount + 4u * KW <= (uint32_t)KM_QCAP) {
+                    if (isqv[s]) { // wave-uniform
+                        if (has_invalid) test_step(s, std::true_type{}, std::integral_constant<int, 1>{});
+                        else test_step(s, std::false_type{}, std::integral_constant<int, 1>{});
+                    } else if (has_invalid) test_step(s, std::true_type{}, std::integral_constant<int, 4>{});
+                    else test_step(s, std::false_type{}, std::integral_constant<int, 4>{});
+                    ++step;
+                } else break;
             }
-            step += done;
             const bool last = step >= nsteps;
+            // room for another step: go on with the windows.  The queue is drained when a step might not fit (whole waves of 64, the
+            // remainder carried) and once after the tile's last step.
+            if (!last && qcount + 4u * KW <= (uint32_t)KM_QCAP) continue;
             wave_sync();
             const uint32_t qn = last ? qcount : (qcount & ~(uint32_t)(KW - 1)); // mid-tile: whole waves of candidates only
             drain(qn);
             wave_sync();
             if (last) break;
             const uint32_t rem = qcount - qn; // < 64 candidates move to the front of the queue
-            uint32_t ce = 0;
+            uint16_t ce = 0;
             if ((uint32_t)lane < rem) ce = q[qn + lane];
             wave_sync();
             if ((uint32_t)lane < rem) q[lane] = ce;
