@@ -45,7 +45,8 @@
 
 namespace rk {
 
-// (the ablation switches this kernel was attributed with -- RK_ABLATE builds, RKMH_DBG -- live in tools/ubench/rk_classify_ablation.hip, not here)
+// (the wave helpers, tile ownership, a tile's reads and offsets, and the host rules for counters, hit multiset and grid are shared
+// with k_classify_kmer: rk_device.hpp.  What the ablation builds of this kernel measured is under profiles/.)
 
 constexpr int WAVE = 64;
 // Occupancy target: the kernel is sensitive to it (5 -> 6 waves/SIMD = +11 % measured), so registers and LDS are
@@ -54,35 +55,6 @@ constexpr int WAVE = 64;
 #define RK_WAVES_PER_SIMD 6
 #endif
 constexpr int PF_MAX = 6; // prefetched base dwords per lane: tile bytes <= PF*64*4 - 8 (template parameter PF = 2, 3 or 6)
-
-template <int CTRL>
-__device__ __forceinline__ int dpp_i32(int v) { return __builtin_amdgcn_update_dpp(v, v, CTRL, 0xf, 0xf, false); }
-// max over a 16-lane DPP row; every lane of the row ends with the result
-__device__ __forceinline__ int row_max_i32(int v) {
-    int t;
-    t = dpp_i32<0xB1>(v); v = t > v ? t : v;   // quad_perm [1,0,3,2]
-    t = dpp_i32<0x4E>(v); v = t > v ? t : v;   // quad_perm [2,3,0,1]
-    t = dpp_i32<0x141>(v); v = t > v ? t : v;  // row_half_mirror
-    t = dpp_i32<0x140>(v); v = t > v ? t : v;  // row_mirror
-    return v;
-}
-
-// max over an aligned group of 8 lanes (half a DPP row)
-__device__ __forceinline__ int half_row_max_i32(int v) {
-    int t;
-    t = dpp_i32<0xB1>(v); v = t > v ? t : v;   // quad_perm [1,0,3,2]
-    t = dpp_i32<0x4E>(v); v = t > v ? t : v;   // quad_perm [2,3,0,1]
-    t = dpp_i32<0x141>(v); v = t > v ? t : v;  // row_half_mirror
-    return v;
-}
-
-// Orders this wave's LDS traffic for cross-lane hand-offs.  A workgroup is one wave: LDS instructions of a
-// wave execute in order, so no hardware wait is needed -- only the compiler must not move accesses across.
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 struct TileGeom {
     int32_t T;          // reads per tile (<= 16)
@@ -152,18 +124,14 @@ __device__ __forceinline__ bool index_lookup(const RefIndex& ix, uint64_t h, uin
 
 // The lookup of a window is issued one step ahead: the bucket (or filter word) of window i is requested at the end of step i and
 // examined after window i + 1 has been hashed.  Plain loads: hipcc places the wait in front of the first use, i.e. behind the next
-// window's hashing (rounds 1-4 issued these loads through inline asm with hand-placed s_waitcnt and policed the ISA with a lint;
-// k_classify_kmer showed that the compiler keeps the same overlap on its own).
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void bucket_load_async(const uint4* base, uint32_t byte_off, u32x4& f) {
-    f = *reinterpret_cast<const u32x4*>(reinterpret_cast<const uint8_t*>(base) + byte_off);
+// window's hashing.  (Functions with an out-parameter, not the loads written out at their three sites: those compile to other code.)
+__device__ __forceinline__ void load_bucket(const uint4* base, uint32_t byte_off, rk_u32x4& f) {
+    f = *reinterpret_cast<const rk_u32x4*>(reinterpret_cast<const uint8_t*>(base) + byte_off);
 }
-__device__ __forceinline__ void bucket_wait(u32x4&) {}
 // the same for one word of the first-level filter (RefIndex::pre)
-__device__ __forceinline__ void word_load_async(const uint32_t* base, uint32_t byte_off, uint32_t& f) {
+__device__ __forceinline__ void load_word(const uint32_t* base, uint32_t byte_off, uint32_t& f) {
     f = *reinterpret_cast<const uint32_t*>(reinterpret_cast<const uint8_t*>(base) + byte_off);
 }
-__device__ __forceinline__ void word_wait(uint32_t&) {}
 
 // MODE 0: classify; MODE 1: count pass of -M (rkmh.cpp:904-910); MODE 2: classify with the -M mask (rkmh.cpp:916)
 // MODE_ 3 / 4: MODE 0 / 2 with the first-level filter of large panels (RefIndex::pre) in front of the bucket table
@@ -242,17 +210,6 @@ __global__ __launch_bounds__(WAVE, RK_WAVES_PER_SIMD) void k_classify_tile(const
             }
         }
     };
-    auto tile_reads = [&](uint32_t tl) -> int {
-        const uint32_t r = tl * (uint32_t)T;
-        return (int)((nreads - r) < (uint32_t)T ? (nreads - r) : (uint32_t)T);
-    };
-    auto load_offsets = [&](uint32_t tl, uint32_t& a_, uint32_t& b_, uint32_t& o_) {
-        const uint32_t r = tl * (uint32_t)T;
-        const int n = tile_reads(tl);
-        a_ = offs[r];
-        b_ = offs[r + (uint32_t)n];
-        o_ = offs[r + (uint32_t)(lane <= n ? lane : n)];
-    };
     // Addresses are clamped into the tile (out-of-range lanes are zeroed when the image is built).
     auto load_bases = [&](uint32_t a_, uint32_t b_) {
         const uint32_t* g32 = reinterpret_cast<const uint32_t*>(bases) + (a_ >> 2);
@@ -267,15 +224,9 @@ __global__ __launch_bounds__(WAVE, RK_WAVES_PER_SIMD) void k_classify_tile(const
             }
         }
     };
-    auto wait_bases = [&]() {}; // (plain loads: the compiler waits where the registers are first read)
-    // XCD-aware tile ownership: the dispatcher deals workgroups round-robin over the 8 XCDs, each with its own L2.
-    // Workgroup b is given the tiles of "virtual" workgroup (b % 8) * ceil(grid / 8) + b / 8, so the workgroups of one
-    // XCD walk one contiguous eighth of the batch and the cache lines that straddle two tiles are fetched into one L2.
-    uint32_t vb = blockIdx.x;
-    if (geo.xcd) { const uint32_t per = (gridDim.x + 7u) >> 3; vb = (blockIdx.x & 7u) * per + (blockIdx.x >> 3); }
-    const uint32_t tile0 = vb * (uint32_t)geo.tpb;
+    const uint32_t tile0 = xcd_virtual_block(geo.xcd) * (uint32_t)geo.tpb;
     const uint32_t tile_end = (tile0 + (uint32_t)geo.tpb) < ntiles ? (tile0 + (uint32_t)geo.tpb) : ntiles;
-    if (tile0 < ntiles) { load_offsets(tile0, cur_a, cur_b, cur_o); load_bases(cur_a, cur_b); }
+    if (tile0 < ntiles) { load_offsets(offs, nreads, T, lane, tile0, cur_a, cur_b, cur_o); load_bases(cur_a, cur_b); }
 
     for (uint32_t tile = tile0; tile < tile_end; ++tile) {
         const uint32_t r0 = tile * (uint32_t)T;
@@ -285,13 +236,13 @@ __global__ __launch_bounds__(WAVE, RK_WAVES_PER_SIMD) void k_classify_tile(const
         const uint32_t B_all = (uint32_t)__builtin_amdgcn_readfirstlane((int)(cur_b - cur_a));
         const uint32_t ntile = tile + 1u < tile_end ? tile + 1u : ntiles; // this workgroup's next tile (none: ntiles)
         uint32_t nxt_a = 0, nxt_b = 0, nxt_o = 0;
-        if (ntile < ntiles) load_offsets(ntile, nxt_a, nxt_b, nxt_o); // lands during phase 0
+        if (ntile < ntiles) load_offsets(offs, nreads, T, lane, ntile, nxt_a, nxt_b, nxt_o); // lands during phase 0
         wave_sync(); // previous tile fully consumed
         // A tile holding a read longer than the caller's hint is rerouted by the host (rows of -2; the count pass skips it).
         // Here it becomes an EMPTY tile (no reads, no bytes) that runs through the body like any other.
         const bool oversized = B_all > (uint32_t)geo.cap_bytes;
-        if (MODE != 1 && oversized && lane < tile_reads(tile)) reinterpret_cast<int4*>(out4)[r0 + lane] = make_int4(-2, 0, 0, 0);
-        const int Tn = oversized ? 0 : tile_reads(tile);
+        if (MODE != 1 && oversized && lane < tile_reads(nreads, T, tile)) reinterpret_cast<int4*>(out4)[r0 + lane] = make_int4(-2, 0, 0, 0);
+        const int Tn = oversized ? 0 : tile_reads(nreads, T, tile);
         const uint32_t B = oversized ? 0u : B_all;
         // ---- phase 0, interval 1: everything that needs only registers ------------------------------
         Staged s;
@@ -329,7 +280,6 @@ __global__ __launch_bounds__(WAVE, RK_WAVES_PER_SIMD) void k_classify_tile(const
         const uint32_t endb = ((tstart & 3u) + B) & 3u;
         const uint32_t m_last = endb ? (~0u >> (8u * (4u - endb))) : ~0u;
         uint32_t anyinv = 0;
-        wait_bases();
 #pragma unroll
         for (int q = 0; q < PF; ++q) { // upper-cased forward image; does any base of the tile fail the ACGT test?
             if ((uint32_t)q * WAVE <= ndw) { // wave-uniform
@@ -413,6 +363,7 @@ __global__ __launch_bounds__(WAVE, RK_WAVES_PER_SIMD) void k_classify_tile(const
             // exceeds the number of windows, so no field can carry into its neighbour)
             uint32_t cnt;
             if (geo.csparse) { // wave-uniform: large reference panels keep (ref, count) pairs of the references a read really hits
+                // (the same loop is count_posting of k_classify_kmer; why it is not one function: rk_device.hpp)
                 uint32_t* row = c16 + t * geo.cwords;
                 const uint32_t M1 = (uint32_t)geo.cwords - 1u, key = ref + 1u;
                 uint32_t idx = ((ref * 0x9E3779B1u) >> 16) & M1, probe = 0;
@@ -554,7 +505,7 @@ __global__ __launch_bounds__(WAVE, RK_WAVES_PER_SIMD) void k_classify_tile(const
             uint32_t magic = 0;
             if (compact) magic = nw_u == (uint32_t)geo.magic_nw ? (uint32_t)geo.magic
                                                                 : (uint32_t)__builtin_amdgcn_readfirstlane((int)(0xFFFFFFFFu / nw_u + 1u));
-            u32x4 fb = {0u, 0u, 0u, 0u}; // bucket fetched for the previous position (lookup in flight)
+            rk_u32x4 fb = {0u, 0u, 0u, 0u}; // bucket fetched for the previous position (lookup in flight)
             uint32_t fw = 0;             // ... or its word of the first-level filter (large panels)
             uint64_t hp = 0;
             uint32_t tp = 0; // read of the previous position
@@ -652,14 +603,13 @@ __global__ __launch_bounds__(WAVE, RK_WAVES_PER_SIMD) void k_classify_tile(const
                     if (MODE == 1) {
                         if (geo.cs.tab) { // wave-uniform: the compact depth map
                             uint32_t* cq = reinterpret_cast<uint32_t*>(qe);
-                            word_wait(cword);
                             const uint32_t pbit = (cprev * 0x9E3779B1u) >> geo.cs.pre_shift;
                             const bool pass = cprev != CS_EMPTY && ((cword >> (pbit & 31u)) & 1u) != 0u;
                             const uint64_t m = __ballot(pass);
-                            if (pass) cq[ccount + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u))] = cprev;
+                            if (pass) cq[ccount + lanes_below(m)] = cprev;
                             ccount = (uint32_t)__builtin_amdgcn_readfirstlane((int)(ccount + (uint32_t)__popcll(m)));
                             const uint32_t nbit = (cslot * 0x9E3779B1u) >> geo.cs.pre_shift; // (CS_EMPTY looks some word up too: never tested)
-                            word_load_async(geo.cs.pre, (nbit >> 5) << 2, cword);
+                            load_word(geo.cs.pre, (nbit >> 5) << 2, cword);
                             cprev = cslot;
                             cslot = CS_EMPTY;
                             if (ccount >= 2u * WAVE) { // (the queue holds 3 * 64 entries)
@@ -673,21 +623,16 @@ __global__ __launch_bounds__(WAVE, RK_WAVES_PER_SIMD) void k_classify_tile(const
                     }
                     // examine the lookup issued one step ago: fingerprint matches / full buckets are queued
                     if constexpr (PRE) { // large panel: the filter word decides what the drain will look up in the table
-                        word_wait(fw);
                         const uint32_t bm = index_pre_bits(hp);
                         const bool cand = (fw & bm) == bm;
                         const uint64_t m = __ballot(cand);
-                        if (cand) {
-                            const uint32_t q = qcount + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-                            qe[q] = make_uint4((uint32_t)hp, (uint32_t)(hp >> 32), tp, 0u);
-                        }
+                        if (cand) qe[qcount + lanes_below(m)] = make_uint4((uint32_t)hp, (uint32_t)(hp >> 32), tp, 0u);
                         qcount = (uint32_t)__builtin_amdgcn_readfirstlane((int)(qcount + (uint32_t)__popcll(m)));
-                        word_load_async(ix.pre, index_pre_word(h, ix.pmask) << 2, fw);
+                        load_word(ix.pre, index_pre_word(h, ix.pmask) << 2, fw);
                         hp = h;
                         tp = t;
                         continue;
                     }
-                    bucket_wait(fb);
                     {
                         const uint32_t fp = index_fp(hp);
                         // eight halfword compares (SDWA word selects, one VALU each).  A bucket whose overflow flag (bit 15 of slot
@@ -703,13 +648,10 @@ __global__ __launch_bounds__(WAVE, RK_WAVES_PER_SIMD) void k_classify_tile(const
                                            __builtin_amdgcn_ballot_w64((fb.w & 0xffffu) == fp) | __builtin_amdgcn_ballot_w64((fb.w >> 16) == fp) |
                                            __builtin_amdgcn_ballot_w64((fb.x & IDX_OVF) != 0u);
                         const bool cand = __builtin_amdgcn_inverse_ballot_w64(m);
-                        if (cand) {
-                            const uint32_t q = qcount + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-                            qe[q] = make_uint4((uint32_t)hp, (uint32_t)(hp >> 32), tp, 0u);
-                        }
+                        if (cand) qe[qcount + lanes_below(m)] = make_uint4((uint32_t)hp, (uint32_t)(hp >> 32), tp, 0u);
                         qcount = (uint32_t)__builtin_amdgcn_readfirstlane((int)(qcount + (uint32_t)__popcll(m)));
                     }
-                    bucket_load_async(ix.fpb, index_bucket(h, ix.bmask) << 4, fb); // lands while the next position is hashed
+                    load_bucket(ix.fpb, index_bucket(h, ix.bmask) << 4, fb); // lands while the next position is hashed
                     hp = h;
                     tp = t;
                 }
@@ -730,7 +672,7 @@ __global__ __launch_bounds__(WAVE, RK_WAVES_PER_SIMD) void k_classify_tile(const
                 wave_sync();
             }
         }
-        if (MODE == 1) { wait_bases(); continue; } // see the end of the loop body
+        if (MODE == 1) continue; // the count pass has no rows to write
 
         // ---- phase 2: 16 lanes per read, or 8 when the tile holds more than four (one pass for up to eight reads: with 16, the fifth
         //      read of a five-read tile was a pass of its own with 48 lanes idle) -----------------------
@@ -745,7 +687,7 @@ __global__ __launch_bounds__(WAVE, RK_WAVES_PER_SIMD) void k_classify_tile(const
                 const uint32_t bk = best[t];
                 if (reroute) {
                     for (int w = sl; w < geo.cwords; w += LPR) ct[w] = 0;
-                    if (sl == 0) reinterpret_cast<int4*>(out4)[r0 + t] = reroute ? make_int4(-2, 0, 0, 0) : make_int4(0, (int)(bk >> 16), 0, nmins);
+                    if (sl == 0) reinterpret_cast<int4*>(out4)[r0 + t] = make_int4(-2, 0, 0, 0);
                     continue;
                 }
                 // first max wins (rkmh.cpp:878); diff = max - best EARLIER score (untouched refs score 0; none => -1)
@@ -773,15 +715,13 @@ __global__ __launch_bounds__(WAVE, RK_WAVES_PER_SIMD) void k_classify_tile(const
                 if (sl == 0) reinterpret_cast<int4*>(out4)[r0 + t] = make_int4(max_id, max_shared, max_shared - prev, nmins < geo.nmin_cap ? nmins : geo.nmin_cap);
             }
         }
-        wait_bases();
     }
     if (MODE == 1 && geo.cs.tab) { // the compact count's last step and what is left in its queue
         uint32_t* cq = reinterpret_cast<uint32_t*>(qe);
-        word_wait(cword);
         const uint32_t pbit = (cprev * 0x9E3779B1u) >> geo.cs.pre_shift;
         const bool pass = cprev != CS_EMPTY && ((cword >> (pbit & 31u)) & 1u) != 0u;
         const uint64_t m = __ballot(pass);
-        if (pass) cq[ccount + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u))] = cprev;
+        if (pass) cq[ccount + lanes_below(m)] = cprev;
         ccount += (uint32_t)__popcll(m);
         wave_sync();
         for (uint32_t f = 0; f < ccount; f += WAVE) compact_drain(f, ccount - f < (uint32_t)WAVE ? ccount - f : (uint32_t)WAVE);
@@ -792,32 +732,17 @@ __global__ __launch_bounds__(WAVE, RK_WAVES_PER_SIMD) void k_classify_tile(const
 // saturates VALU issue at 6 waves/SIMD and loses ~11 % at 5 (measured), so tiles never grow past this.
 constexpr size_t LDS_BUDGET_6_WAVES = 6656;
 
-// RKMH_PRE_MASKED (tests: the -M classify kernel without / with the first-level filter) is read ONCE per process: a launch costs no getenv.
 // (The geometry sweeps that chose the values below ran with RKMH_TILE_* overrides; those are gone, the measurements are in profiles/.)
-struct TileKnobs {
-    int qcap = 0, c16 = 0, sparse = 0, dset = 0, tile_t = 0, tpb = 0, xcd = -1, pre_masked = -1;
-    TileKnobs() { const char* e = getenv("RKMH_PRE_MASKED"); pre_masked = e ? atoi(e) : -1; }
-};
-static const TileKnobs& knobs() { static const TileKnobs k; return k; }
-
 static TileGeom make_geom(int maxlen, int nref, int expect_hits, int win_per_read, int win_total, int uset = 0) {
-    const TileKnobs& kn = knobs();
     TileGeom g;
     g.uset = uset;
     if (maxlen < 1) maxlen = 1;
-    g.qcap = kn.qcap > 0 ? kn.qcap : 128;
-    g.clg = win_total <= 255 ? 2 : 1;
-    if (kn.c16 > 0) g.clg = 1; // A/B knob: always 16-bit counters
-    g.cwords = (nref + (1 << g.clg) - 1) >> g.clg;
-    g.csparse = 0;
-    // Many references: a dense counter row per read would eat the LDS budget (and reference ids beyond 2048 would not
-    // fit at all), so the row becomes a 128-entry map of the references the read actually hits.
-    const int sparse_min = kn.sparse > 0 ? 1 : (kn.sparse < 0 ? (1 << 30) : 129); // dense rows up to 128 words (512 B) stay dense
-    if (nref > 0 && g.cwords >= sparse_min) { g.csparse = 1; g.cwords = 128; }
-    int ds = 64;
-    while (ds < 3 * expect_hits && ds < 1024) ds <<= 1;
-    if (kn.dset > 0) ds = kn.dset;
-    g.dset = ds;
+    g.qcap = 128;
+    const CounterLayout cl = counter_layout(nref, win_total);
+    g.clg = cl.clg;
+    g.cwords = cl.cwords;
+    g.csparse = cl.sparse;
+    g.dset = hit_multiset_slots(expect_hits);
     // Reads per tile: the hashing loop walks T * win_per_read windows 64 at a time, so T is chosen for the best fill of
     // its last step (150 bp, k=16: T=3 fills 89.7 %, T=4 93.1 %) among the sizes that keep the occupancy target and
     // the short prefetch (<= 3 dwords per lane).
@@ -855,7 +780,6 @@ static TileGeom make_geom(int maxlen, int nref, int expect_hits, int win_per_rea
         for (int T = best + 1; T <= tmax && T <= 8; ++T) if (cost(T) < cost(alt)) alt = T;
         if (cost(alt) < 0.95 * cost(best)) best = alt;
     }
-    if (kn.tile_t > 0) best = kn.tile_t;
     if (best > 16) best = 16;
     if (best < 1) best = 1;
     while (best > 1 && best * maxlen > PF_MAX * WAVE * 4 - 8) --best;
@@ -868,38 +792,39 @@ static TileGeom make_geom(int maxlen, int nref, int expect_hits, int win_per_rea
 // one tile (>= 1 read of maxlen bytes) must fit the prefetch registers
 bool classify_tile_supported(int nref, int maxlen) { return nref <= 16384 && maxlen <= PF_MAX * WAVE * 4 - 8; }
 
-hipError_t launch_classify_tile(const uint8_t* bases, const uint32_t* offs, uint32_t nreads, const KsArr& ks, int S,
-                                const RefIndex& ix, int32_t* counter, uint64_t slots, int min_occ, int mode,
-                                int32_t* out4, const DevPolicy& pol, int maxlen, int expect_hits, hipStream_t st,
-                                uint32_t slot_stride, int nmin_cap, const CompactSlots* compact, bool dedup) {
-    if (nreads == 0) return hipSuccess;
-    if (dedup && mode == 1) return hipErrorInvalidValue; // the count passes count windows under either sketch rule
-    const TileKnobs& kn = knobs();
+hipError_t launch_classify_tile(const TileLaunch& a) {
+    const ReadBatch& b = a.batch;
+    const KsArr& ks = *a.ks;
+    const RefIndex& ix = *a.ix;
+    const DevPolicy& pol = *a.pol;
+    const int maxlen = b.maxlen;
+    const bool count = a.pass == TILE_COUNT, masked = a.pass == TILE_CLASSIFY_MASKED;
+    if (b.nreads == 0) return hipSuccess;
+    if (a.pass != TILE_CLASSIFY && !a.counter) return hipErrorInvalidValue; // both -M passes read or write it
+    if (a.dedup && count) return hipErrorInvalidValue; // the count passes count windows under either sketch rule
     int win_total = 0; // most windows any read of the batch can have (all k): bounds every per-reference count
     for (int j = 0; j < ks.n; ++j) win_total += num_windows(maxlen, ks.k[j], pol.drop_last_window);
     int uset = 0;
-    if (dedup) { uset = 64; while (uset < 2 * win_total && uset < DEDUP_MAX_SLOTS) uset <<= 1; }
-    TileGeom geo = make_geom(maxlen, mode == 1 ? 0 : ix.nref, mode == 1 ? 0 : expect_hits,
+    if (a.dedup) { uset = 64; while (uset < 2 * win_total && uset < DEDUP_MAX_SLOTS) uset <<= 1; }
+    TileGeom geo = make_geom(maxlen, count ? 0 : ix.nref, count ? 0 : b.expect_hits,
                              num_windows(maxlen, ks.k[0], pol.drop_last_window), win_total, uset);
-    if (mode == 1) { geo.qcap = compact ? 48 : 0; geo.dset = 0; } // (compact count: 3 * 64 queued slots of 4 bytes)
+    if (count) { geo.qcap = a.compact ? 48 : 0; geo.dset = 0; } // (compact count: 3 * 64 queued slots of 4 bytes)
     while (tile_lds_bytes(geo) > 20 * 1024 && geo.T > 1) { geo.T -= 1; geo.cap_bytes = geo.T * maxlen; } // >= 8 waves per CU
     const size_t lds = tile_lds_bytes(geo);
-    const uint32_t ntiles = (nreads + (uint32_t)geo.T - 1) / (uint32_t)geo.T;
+    const uint32_t ntiles = (b.nreads + (uint32_t)geo.T - 1) / (uint32_t)geo.T;
     // Short-lived waves: each single-wave workgroup walks a couple of tiles (the first one cold, the next prefetched)
     // and retires, so the hardware dispatcher keeps balancing the CUs.  Measured on MI355X with the current kernel
     // (T=4): 1 or 2 tiles per workgroup are within noise of each other, 3 is -1 %, 6 is -4 %, chip-resident persistent
     // waves were -17 % (tail imbalance); 2 keeps the cross-tile prefetch useful when the batch streams from HBM.
-    const int tpb = kn.tpb > 0 ? kn.tpb : 2;
-    geo.tpb = tpb;
-    geo.xcd = kn.xcd >= 0 ? (kn.xcd != 0) : 1;
-    geo.slots_m = slots ? ~0ull / slots : 0;
-    geo.slot_stride = slot_stride;
-    geo.nmin_cap = nmin_cap;
-    if (compact) geo.cs = *compact; else memset(&geo.cs, 0, sizeof geo.cs);
+    geo.tpb = 2;
+    geo.xcd = 1;
+    geo.slots_m = a.slots ? ~0ull / a.slots : 0;
+    geo.slot_stride = a.slot_stride;
+    geo.nmin_cap = b.nmin_cap;
+    if (a.compact) geo.cs = *a.compact; else memset(&geo.cs, 0, sizeof geo.cs);
     geo.magic_nw = num_windows(maxlen, ks.k[0], pol.drop_last_window);
-    geo.magic = geo.magic_nw >= 2 ? 0xFFFFFFFFu / (uint32_t)geo.magic_nw + 1u : 0u;
+    geo.magic = div_magic((uint32_t)geo.magic_nw);
     const bool k16 = (ks.n == 1 && ks.k[0] == 16);
-    const int kmode = mode == 1 ? 1 : (counter ? 2 : 0);
     // The masked (-M) form waits for a random read of the keep bitmap in every step: it is bound by memory requests,
     // not by VALU issue, and the filter word is one more request per window (C2: 2.86 ms without, 3.10 ms with).  It pays
     // only once the bucket table itself has left L2.
@@ -907,7 +832,9 @@ hipError_t launch_classify_tile(const uint8_t* bases, const uint32_t* offs, uint
     // pipelining that lookup one step ahead, in the filter-word form, was measured SLOWER, 2.89 ms: the pass is bound by the
     // rate of random accesses that miss the L2, about 5 * 10^10 per second here, not by latency or instructions.)
     bool pre_masked = ((size_t)ix.bmask + 1) * 16 > ((size_t)3 << 20);
-    if (kn.pre_masked >= 0) pre_masked = kn.pre_masked != 0; // tests force either form
+    // RKMH_PRE_MASKED (tests force either form) is read ONCE per process: a launch costs no getenv
+    static const int pre_masked_env = [] { const char* e = getenv("RKMH_PRE_MASKED"); return e ? atoi(e) : -1; }();
+    if (pre_masked_env >= 0) pre_masked = pre_masked_env != 0;
 #define RK_LAUNCH_P(KT, MODE, FOLD, PF, ...)                                                                         \
     do {                                                                                                             \
         if (lds > 64 * 1024) {                                                                                       \
@@ -915,10 +842,9 @@ hipError_t launch_classify_tile(const uint8_t* bases, const uint32_t* offs, uint
                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);               \
             if (e != hipSuccess) return e;                                                                           \
         }                                                                                                            \
-        uint32_t grid = (ntiles + (uint32_t)tpb - 1) / (uint32_t)tpb;                                                \
-        grid = (grid + 7u) & ~7u; /* whole rounds of the 8 XCDs: the virtual ids then cover [0, grid) exactly */      \
-        hipLaunchKernelGGL((k_classify_tile<KT, MODE, FOLD, PF, ##__VA_ARGS__>), dim3(grid), dim3(WAVE), lds, st, bases, offs, nreads, \
-                           ks, S, ix, counter, slots, min_occ, out4, pol, geo);                                      \
+        const uint32_t grid = xcd_grid((ntiles + (uint32_t)geo.tpb - 1) / (uint32_t)geo.tpb);                        \
+        hipLaunchKernelGGL((k_classify_tile<KT, MODE, FOLD, PF, ##__VA_ARGS__>), dim3(grid), dim3(WAVE), lds, b.st, b.bases, b.offs,  \
+                           b.nreads, ks, a.S, ix, a.counter, a.slots, a.min_occ, a.out4, pol, geo);                  \
     } while (0)
 #define RK_LAUNCH(KT, MODE, FOLD, ...)                                                                               \
     do {                                                                                                             \
@@ -928,9 +854,9 @@ hipError_t launch_classify_tile(const uint8_t* bases, const uint32_t* offs, uint
     } while (0)
 #define RK_LAUNCH_M(KT, FOLD, ...)                                                                                   \
     do {                                                                                                             \
-        if (kmode == 1) RK_LAUNCH(KT, 1, FOLD, ##__VA_ARGS__);                                                       \
-        else if (kmode == 0 && !ix.pre) RK_LAUNCH(KT, 0, FOLD, ##__VA_ARGS__);                                       \
-        else if (kmode == 0) RK_LAUNCH(KT, 3, FOLD, ##__VA_ARGS__);                                                  \
+        if (count) RK_LAUNCH(KT, 1, FOLD, ##__VA_ARGS__);                                                            \
+        else if (!masked && !ix.pre) RK_LAUNCH(KT, 0, FOLD, ##__VA_ARGS__);                                          \
+        else if (!masked) RK_LAUNCH(KT, 3, FOLD, ##__VA_ARGS__);                                                     \
         else if (!ix.pre || !pre_masked) RK_LAUNCH(KT, 2, FOLD, ##__VA_ARGS__);                                      \
         else RK_LAUNCH(KT, 4, FOLD, ##__VA_ARGS__);                                                                  \
     } while (0)
@@ -939,11 +865,11 @@ hipError_t launch_classify_tile(const uint8_t* bases, const uint32_t* offs, uint
     RK_LAUNCH_M(RK_TILE_ONLY_K, -1);
     return hipGetLastError();
 #endif
-    if (dedup) { // dedup=distinct: the run-time-k form, any k, either strand rule (no count mode)
+    if (a.dedup) { // dedup=distinct: the run-time-k form, any k, either strand rule (no count mode)
 #define RK_LAUNCH_D(CANON)                                                                                           \
     do {                                                                                                             \
-        if (kmode == 0 && !ix.pre) RK_LAUNCH(0, 0, -1, CANON, true);                                                 \
-        else if (kmode == 0) RK_LAUNCH(0, 3, -1, CANON, true);                                                       \
+        if (!masked && !ix.pre) RK_LAUNCH(0, 0, -1, CANON, true);                                                    \
+        else if (!masked) RK_LAUNCH(0, 3, -1, CANON, true);                                                          \
         else if (!ix.pre || !pre_masked) RK_LAUNCH(0, 2, -1, CANON, true);                                           \
         else RK_LAUNCH(0, 4, -1, CANON, true);                                                                       \
     } while (0)

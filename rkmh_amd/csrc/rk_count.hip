@@ -20,8 +20,6 @@
 
 namespace rk {
 
-typedef uint32_t u32x4c __attribute__((ext_vector_type(4)));
-
 __device__ __forceinline__ uint32_t cb_bin(uint32_t slot, const CountPlan& pl) {
     const uint32_t sub = slot >> CB_SUB_LG;
     return pl.R == 1 ? sub : __umulhi(sub, pl.magicR); // sub * R < 2^32: the magic division is exact
@@ -55,7 +53,7 @@ __global__ __launch_bounds__(CB_THREADS) void k_slot_hist(const uint32_t* __rest
     const uint64_t lo = (uint64_t)blockIdx.x * pl.span;
     const uint64_t hi = lo + pl.span < pl.n ? lo + pl.span : pl.n; // n is a multiple of 4 and the array is sentinel-filled
     for (uint64_t i = lo + (uint64_t)threadIdx.x * 4; i < hi; i += (uint64_t)CB_THREADS * 4) {
-        const u32x4c v = __builtin_nontemporal_load(reinterpret_cast<const u32x4c*>(flat + i));
+        const rk_u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const rk_u32x4*>(flat + i));
         if (v.x != CB_NONE) atomicAdd(&lh[cb_bin(v.x, pl)], 1u);
         if (v.y != CB_NONE) atomicAdd(&lh[cb_bin(v.y, pl)], 1u);
         if (v.z != CB_NONE) atomicAdd(&lh[cb_bin(v.z, pl)], 1u);
@@ -113,8 +111,8 @@ __global__ __launch_bounds__(CB_THREADS) void k_slot_scatter(const uint32_t* __r
 #pragma unroll
         for (int j = 0; j < QPT; ++j) {
             const uint64_t i = c0 + ((uint64_t)j * CB_THREADS + tid) * 4;
-            u32x4c q = {CB_NONE, CB_NONE, CB_NONE, CB_NONE};
-            if (i < hi) q = __builtin_nontemporal_load(reinterpret_cast<const u32x4c*>(flat + i));
+            rk_u32x4 q = {CB_NONE, CB_NONE, CB_NONE, CB_NONE};
+            if (i < hi) q = __builtin_nontemporal_load(reinterpret_cast<const rk_u32x4*>(flat + i));
             v[4 * j] = q.x; v[4 * j + 1] = q.y; v[4 * j + 2] = q.z; v[4 * j + 3] = q.w;
         }
 #pragma unroll
@@ -153,7 +151,7 @@ __global__ __launch_bounds__(CB_THREADS) void k_count_bins(const uint32_t* __res
     __syncthreads();
     const uint32_t lo = bin_start[b], hi = bin_start[b + 1];
     for (uint32_t i = (lo & ~3u) + tid * 4; i < hi; i += CB_THREADS * 4) {
-        const u32x4c v = *reinterpret_cast<const u32x4c*>(bin_data + i); // entries before lo belong to another bin: no match
+        const rk_u32x4 v = *reinterpret_cast<const rk_u32x4*>(bin_data + i); // entries before lo belong to another bin: no match
         if ((v.x >> CB_SUB_LG) == sub) atomicAdd(&cnt[v.x & ((1u << CB_SUB_LG) - 1)], 1u);
         if ((v.y >> CB_SUB_LG) == sub && i + 1 < hi) atomicAdd(&cnt[v.y & ((1u << CB_SUB_LG) - 1)], 1u);
         if ((v.z >> CB_SUB_LG) == sub && i + 2 < hi) atomicAdd(&cnt[v.z & ((1u << CB_SUB_LG) - 1)], 1u);
@@ -193,7 +191,7 @@ bool count_plan(uint64_t slots, uint64_t n_entries, CountPlan* out) {
     pl.nsub = (uint32_t)((slots + (1u << CB_SUB_LG) - 1) >> CB_SUB_LG);
     pl.R = (pl.nsub + CB_MAX_BINS - 1) / CB_MAX_BINS;
     pl.nb = (pl.nsub + pl.R - 1) / pl.R;
-    pl.magicR = pl.R > 1 ? 0xFFFFFFFFu / pl.R + 1u : 0u;
+    pl.magicR = div_magic(pl.R);
     pl.n = (n_entries + 3) & ~3ull;
     uint64_t chunks = (pl.n + CB_CHUNK - 1) / CB_CHUNK;
     pl.G = (uint32_t)(chunks < 512 ? chunks : 512);

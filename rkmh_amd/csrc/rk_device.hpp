@@ -745,4 +745,98 @@ __device__ __forceinline__ int wave_min_i32(int v) {
     return v;
 }
 
+template <int CTRL>
+__device__ __forceinline__ int dpp_i32(int v) { return __builtin_amdgcn_update_dpp(v, v, CTRL, 0xf, 0xf, false); }
+// max over a 16-lane DPP row; every lane of the row ends with the result
+__device__ __forceinline__ int row_max_i32(int v) {
+    int t;
+    t = dpp_i32<0xB1>(v); v = t > v ? t : v;   // quad_perm [1,0,3,2]
+    t = dpp_i32<0x4E>(v); v = t > v ? t : v;   // quad_perm [2,3,0,1]
+    t = dpp_i32<0x141>(v); v = t > v ? t : v;  // row_half_mirror
+    t = dpp_i32<0x140>(v); v = t > v ? t : v;  // row_mirror
+    return v;
+}
+// max over an aligned group of 8 lanes (half a DPP row)
+__device__ __forceinline__ int half_row_max_i32(int v) {
+    int t;
+    t = dpp_i32<0xB1>(v); v = t > v ? t : v;   // quad_perm [1,0,3,2]
+    t = dpp_i32<0x4E>(v); v = t > v ? t : v;   // quad_perm [2,3,0,1]
+    t = dpp_i32<0x141>(v); v = t > v ? t : v;  // row_half_mirror
+    return v;
+}
+
+// set bits of a ballot below this lane: the lane's place among the lanes that voted
+__device__ __forceinline__ uint32_t lanes_below(uint64_t ballot) {
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(ballot >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ballot, 0u));
+}
+
+// ---- what the two fused per-read kernels, k_classify_tile (rk_classify.hip) and k_classify_kmer (rk_kmer.hip), have in common ----
+
+// Orders this wave's LDS traffic for cross-lane hand-offs.  A workgroup is one wave: LDS instructions of a
+// wave execute in order, so no hardware wait is needed -- only the compiler must not move accesses across.
+__device__ __forceinline__ void wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// XCD-aware tile ownership: the dispatcher deals workgroups round-robin over the 8 XCDs, each with its own L2.
+// Workgroup b is given the tiles of "virtual" workgroup (b % 8) * ceil(grid / 8) + b / 8, so the workgroups of one
+// XCD walk one contiguous eighth of the batch and the cache lines that straddle two tiles are fetched into one L2.
+// (The grid is a whole number of rounds, xcd_grid: the virtual ids then cover [0, grid) exactly.  k_classify_kmer writes the same
+// two lines out: through this function the scalar code of all its instantiations is scheduled differently.)
+__device__ __forceinline__ uint32_t xcd_virtual_block(int32_t xcd) {
+    uint32_t vb = blockIdx.x;
+    if (xcd) { const uint32_t per = (gridDim.x + 7u) >> 3; vb = (blockIdx.x & 7u) * per + (blockIdx.x >> 3); }
+    return vb;
+}
+inline uint32_t xcd_grid(uint32_t grid) { return (grid + 7u) & ~7u; }
+
+// reads of tile `tile` (T per tile, the batch's last tile may hold fewer)
+__device__ __forceinline__ int tile_reads(uint32_t nreads, int T, uint32_t tile) {
+    const uint32_t r = tile * (uint32_t)T;
+    return (int)((nreads - r) < (uint32_t)T ? (nreads - r) : (uint32_t)T);
+}
+// the tile's byte range [a, b) in the batch and, in lane t <= its reads, the offset of read t (later lanes: the tile's end)
+__device__ __forceinline__ void load_offsets(const uint32_t* offs, uint32_t nreads, int T, int lane, uint32_t tile,
+                                             uint32_t& a, uint32_t& b, uint32_t& o) {
+    const uint32_t r = tile * (uint32_t)T;
+    const int n = tile_reads(nreads, T, tile);
+    a = offs[r];
+    b = offs[r + (uint32_t)n];
+    o = offs[r + (uint32_t)(lane <= n ? lane : n)];
+}
+
+// (The sparse counter row -- the CAS loop of count_posting and its scan in phase 2 -- is still written out in both kernels.  Moved
+// into a function, the loop's exits are laid out differently and every instantiation that holds it comes out with other code;
+// tried: the overflow, the probe count or the count as out-parameter, the bounds by reference, with and without forced inlining.)
+
+// ---- and on the host: the rules by which their launchers size a read's counters and hit multiset ----
+
+// Per-reference counters of a read: packed fields, 8 bits wide when no read has more than 255 windows (a count never exceeds the
+// number of windows, so no field can carry into its neighbour), else 16.  Many references: a dense row would eat the LDS budget
+// (and reference ids beyond 2048 would not fit at all), so from 129 words up the row becomes a 128-entry sparse row; dense rows up
+// to 128 words (512 B) stay dense.
+struct CounterLayout {
+    int clg;     // log2(fields per 32-bit word): 2 = 8-bit fields, 1 = 16-bit
+    int cwords;  // words per row
+    int sparse;
+};
+inline CounterLayout counter_layout(int nref, int win_total) {
+    CounterLayout c;
+    c.clg = win_total <= 255 ? 2 : 1;
+    c.cwords = (nref + (1 << c.clg) - 1) >> c.clg;
+    c.sparse = nref > 0 && c.cwords >= 129;
+    if (c.sparse) c.cwords = 128;
+    return c;
+}
+// slots of the per-read hit multiset (power of two): three times the hits an error-free read is expected to score, 64 .. 1024
+inline int hit_multiset_slots(int expect_hits) {
+    int ds = 64;
+    while (ds < 3 * expect_hits && ds < 1024) ds <<= 1;
+    return ds;
+}
+// ceil(2^32 / n): w / n = __umulhi(w, magic) without a division, exact while w * n < 2^32 (n >= 2; otherwise 0, never used)
+inline uint32_t div_magic(uint32_t n) { return n >= 2u ? 0xFFFFFFFFu / n + 1u : 0u; }
+
 } // namespace rk

@@ -21,9 +21,6 @@ struct GatherState {
     int32_t pad[4];
 };
 
-__device__ __forceinline__ uint32_t lanes_below(uint64_t bal) { // set bits of bal below this lane
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
-}
 // row r of the references, clamped to [0, nvalues] and to 2^31 - 1 values (as k_scaled_pairs clamps its rows)
 __device__ __forceinline__ void clamped_row(const uint64_t* __restrict__ off, uint32_t r, uint64_t nvalues, uint64_t& r0, uint64_t& r1) {
     r0 = min(off[r], nvalues);

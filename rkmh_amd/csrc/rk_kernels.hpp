@@ -213,20 +213,44 @@ struct CompactSlots {
     uint32_t tab_shift;  // first probe = (slot * 0x85EBCA6B) >> tab_shift
     uint32_t tab_mask;
 };
-// mode 0: classify (out4 written); mode 1: count only (counter incremented)
-// wave-per-tile fused kernel (rk_classify.hip); expect_hits sizes the per-read hit multiset
+// a batch of reads as both fused per-read kernels are given it
+struct ReadBatch {
+    const uint8_t* bases = nullptr;
+    const uint32_t* offs = nullptr;  // [nreads + 1]
+    uint32_t nreads = 0;
+    int maxlen = 1;                  // length hint: a tile holding a longer read is handed back (rows of -2)
+    int expect_hits = 0;             // hits an error-free read is expected to score: sizes the per-read hit multiset
+    int nmin_cap = 0x7fffffff;       // row field 3 = min(non-zero hashes, nmin_cap) (-M with a bounded min_num)
+    hipStream_t st = nullptr;
+};
+// wave-per-tile fused kernel in hash space (rk_classify.hip)
+enum TilePass {
+    TILE_CLASSIFY,         // rows to out4
+    TILE_COUNT,            // pass 1 of -M: every window's slot of `counter` + 1, no rows
+    TILE_CLASSIFY_MASKED,  // pass 2 of -M, masked per window: `counter` is the keep bitmap, one bit per slot (rk_set_depth_filter)
+};
+struct TileLaunch {
+    ReadBatch batch;
+    TilePass pass = TILE_CLASSIFY;
+    const KsArr* ks = nullptr;
+    int S = 0;
+    const RefIndex* ix = nullptr;
+    const DevPolicy* pol = nullptr;
+    int32_t* counter = nullptr;            // the two -M passes (see TilePass)
+    uint64_t slots = 1;                    // ... and its number of slots
+    int min_occ = 0;
+    int32_t* out4 = nullptr;               // rows; TILE_COUNT: null, or the flat array that takes the slots instead of `counter` (rk_count.hip) ...
+    uint32_t slot_stride = 0;              // ... with this many entries per k-mer size
+    const CompactSlots* compact = nullptr; // TILE_COUNT into a compact depth map: `counter` holds one entry per tracked slot
+    bool dedup = false;                    // policy U6 (classify passes): row field 3 counts DISTINCT non-zero hashes
+};
 bool classify_tile_supported(int nref, int maxlen);
+hipError_t launch_classify_tile(const TileLaunch& a);
 constexpr int KPRE_MIN_K = 8; // the k-mer-space kernel (rk_kmer.hip) exists for a single k in [KPRE_MIN_K, 16]
-hipError_t launch_classify_tile(const uint8_t* bases, const uint32_t* offs, uint32_t nreads, const KsArr& ks, int S,
-                                const RefIndex& ix, int32_t* counter, uint64_t slots, int min_occ, int mode,
-                                int32_t* out4, const DevPolicy& pol, int maxlen, int expect_hits, hipStream_t st,
-                                uint32_t slot_stride = 0, int nmin_cap = 0x7fffffff, const CompactSlots* compact = nullptr,
-                                bool dedup = false); // dedup (policy U6, classify modes): row field 3 counts DISTINCT non-zero hashes
 // the k-mer-space kernel (rk_kmer.hip): plain classification with k-mer sizes from KPRE_MIN_K to 16 whose exact k-mer maps and group
 // filters were built (KmerSets: one per size; a single size runs the compile-time-k kernels, several the run-time-k one)
 bool classify_kmer_supported(int nref, int maxlen, int k);
-hipError_t launch_classify_kmer(const uint8_t* bases, const uint32_t* offs, uint32_t nreads, const KmerSets& ksets, int S, const RefIndex& ix,
-                                int32_t* out4, const DevPolicy& pol, int maxlen, int expect_hits, hipStream_t st, int nmin_cap = 0x7fffffff);
+hipError_t launch_classify_kmer(const ReadBatch& b, const KmerSets& ksets, int S, const RefIndex& ix, int32_t* out4, const DevPolicy& pol);
 hipError_t launch_max_len(const uint32_t* offs, uint32_t nreads, uint32_t* d_max, hipStream_t st);
 hipError_t launch_mask_by_frequency(uint64_t* h, uint64_t n, const int32_t* counter, uint64_t slots, int min_occ,
                                     const DevPolicy& pol, hipStream_t st);

@@ -32,7 +32,8 @@ namespace {
 constexpr int KW = 64;
 constexpr int KM_MAX_T = 8;          // reads per tile (phase 2 takes eight reads in one pass; the group -> read search is unrolled for it)
 constexpr int KM_MQ = 32;            // deferred multi-posting hits (a full list is worked off at once: 16 lanes per hit)
-// (the timing experiments this kernel was shaped by -- parts switched off, loads faked -- live in tools/ubench/rk_kmer_ablation.hip, not here)
+// (the wave helpers, a tile's reads and offsets, and the host rules for counters, hit multiset and grid are shared with
+// k_classify_tile: rk_device.hpp.  What the timing experiments this kernel was shaped by measured is under profiles/.)
 constexpr int KM_CH = 4;             // steps (64 groups = 256 windows each) whose filter sectors are requested together (k_classify_kmer: CH)
 // candidate queue: 16-bit entries in 1280 bytes.  A step adds at most 4 KW = 256 entries and is only started when that many are free
 // (no per-push bounds check), so a tile whose candidates stay below 640 - 256 before its last step -- every tile of reads at a
@@ -60,7 +61,6 @@ struct KmerGeom {
     uint32_t magic[KM_MAX_KS]; // ... and ceil(2^32 / gpr): the group -> read division of tiles made of such reads
 };
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 struct __attribute__((packed, aligned(1))) km_pair1 { uint32_t x, y; };
 struct __attribute__((packed, aligned(4))) km_pair4 { uint32_t x, y; }; // two dwords at any dword-aligned address (posting entries)
 
@@ -87,29 +87,6 @@ inline size_t km_lds_bytes(const KmerGeom& g, int nq) {
     return ((size_t)(nq == 1 ? KmLds<1>::CNT : KmLds<2>::CNT) + (size_t)g.T * (size_t)(g.cwords + g.dset)) * 4;
 }
 
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-template <int CTRL>
-__device__ __forceinline__ int dpp_i32(int v) { return __builtin_amdgcn_update_dpp(v, v, CTRL, 0xf, 0xf, false); }
-__device__ __forceinline__ int row_max_i32(int v) {
-    int t;
-    t = dpp_i32<0xB1>(v); v = t > v ? t : v;
-    t = dpp_i32<0x4E>(v); v = t > v ? t : v;
-    t = dpp_i32<0x141>(v); v = t > v ? t : v;
-    t = dpp_i32<0x140>(v); v = t > v ? t : v;
-    return v;
-}
-__device__ __forceinline__ int half_row_max_i32(int v) {
-    int t;
-    t = dpp_i32<0xB1>(v); v = t > v ? t : v;
-    t = dpp_i32<0x4E>(v); v = t > v ? t : v;
-    t = dpp_i32<0x141>(v); v = t > v ? t : v;
-    return v;
-}
-
 // four ASCII bases (any case) -> their 2-bit codes (A=0 C=1 T=2 G=3) gathered in bits 24..31; mism collects the bytes that are
 // not one of ACGTacgt (mkmh's to_upper only moves a..z onto A..Z among them, so the test on the case-folded byte is exact)
 __device__ __forceinline__ uint32_t km_pack4_hi(uint32_t x, uint32_t& mism) {
@@ -119,7 +96,7 @@ __device__ __forceinline__ uint32_t km_pack4_hi(uint32_t x, uint32_t& mism) {
     return c * 0x01041040u;
 }
 // 16 bases in four dwords -> one dword of 2-bit codes (base i in bits [2i, 2i+2))
-__device__ __forceinline__ uint32_t km_pack16(const u32x4& v, uint32_t& mism) {
+__device__ __forceinline__ uint32_t km_pack16(const rk_u32x4& v, uint32_t& mism) {
     const uint32_t m0 = km_pack4_hi(v.x, mism), m1 = km_pack4_hi(v.y, mism), m2 = km_pack4_hi(v.z, mism), m3 = km_pack4_hi(v.w, mism);
     // v_perm_b32: selector bytes 0-3 pick from the second operand, 4-7 from the first, 0x0c = zero
     const uint32_t lo = __builtin_amdgcn_perm(m1, m0, 0x0c0c0703u); // byte 0 = m0 byte 3, byte 1 = m1 byte 3
@@ -184,21 +161,10 @@ __global__ __launch_bounds__(KW, BIG ? 2 : KM_WAVES) void k_classify_kmer(const 
     // readable byte range of the batch: [bases, bases + offs[nreads] + 4) (the ABI asks for 4 bytes of slack), whole dwords
     const uintptr_t safe_hi = (gb + (uintptr_t)offs[nreads] + 4u) & ~(uintptr_t)3;
 
-    auto tile_reads = [&](uint32_t tl) -> int {
-        const uint32_t r = tl * (uint32_t)T;
-        return (int)((nreads - r) < (uint32_t)T ? (nreads - r) : (uint32_t)T);
-    };
-    auto load_offsets = [&](uint32_t tl, uint32_t& a_, uint32_t& b_, uint32_t& o_) {
-        const uint32_t r = tl * (uint32_t)T;
-        const int n = tile_reads(tl);
-        a_ = offs[r];
-        b_ = offs[r + (uint32_t)n];
-        o_ = offs[r + (uint32_t)(lane <= n ? lane : n)];
-    };
     // The tile's bases as 16-byte quads: quad i = bytes [16 i, 16 i + 16) from the 16-byte boundary at or below the tile's first
     // base; lane l holds quads l, 64 + l, ...  A quad that reaches outside the batch's readable range (only possible in the first
     // and the last tile) is fetched dword by dword with the unreadable dwords taken as 0.
-    u32x4 pf[NQ];
+    rk_u32x4 pf[NQ];
     auto fetch_tile = [&](uint32_t a_, uint32_t b_) {
         const uintptr_t first = gb + a_;
         const uintptr_t base16 = first & ~(uintptr_t)15;
@@ -209,11 +175,11 @@ __global__ __launch_bounds__(KW, BIG ? 2 : KM_WAVES) void k_classify_kmer(const 
 #pragma unroll
         for (int r = 0; r < NQ; ++r) {
             const uint32_t qi = (uint32_t)r * KW + (uint32_t)lane;
-            u32x4 v = {0u, 0u, 0u, 0u};
+            rk_u32x4 v = {0u, 0u, 0u, 0u};
             if (qi < nq) {
                 const uintptr_t qa = base16 + 16u * (uintptr_t)qi;
                 if (safe) { // through a global-address-space pointer: the integer round trip would otherwise make it a flat load
-                    typedef const u32x4 __attribute__((address_space(1))) * gq_t;
+                    typedef const rk_u32x4 __attribute__((address_space(1))) * gq_t;
                     v = __builtin_nontemporal_load((gq_t)qa); // the bases are read once: streaming loads keep them from evicting the filter and the map from L2
                 }
                 else {
@@ -232,13 +198,13 @@ __global__ __launch_bounds__(KW, BIG ? 2 : KM_WAVES) void k_classify_kmer(const 
 
     // One tile per workgroup (measured with batches streaming from HBM: 1 tile 0.381 ms, 2 tiles with the second one's bases
     // prefetched 0.383, 4 tiles 0.392, 8 tiles 0.402 -- short-lived waves let the dispatcher balance the CUs, and the other waves of
-    // the SIMD hide a fresh wave's two cold loads).  XCD-aware ownership: the dispatcher deals workgroups round-robin over the 8
-    // XCDs, so workgroup b takes tile (b % 8) * ceil(grid / 8) + b / 8 and each XCD's L2 sees one contiguous eighth of the batch.
+    // the SIMD hide a fresh wave's two cold loads).  XCD-aware ownership: each XCD's L2 sees one contiguous eighth of the batch
+    // (xcd_virtual_block, rk_device.hpp, written out: see there).
     uint32_t tile = blockIdx.x;
     if (geo.xcd) { const uint32_t per = (gridDim.x + 7u) >> 3; tile = (blockIdx.x & 7u) * per + (blockIdx.x >> 3); }
     if (tile >= ntiles) return;
     uint32_t cur_a = 0, cur_b = 0, cur_o = 0;
-    load_offsets(tile, cur_a, cur_b, cur_o);
+    load_offsets(offs, nreads, T, lane, tile, cur_a, cur_b, cur_o);
     fetch_tile(cur_a, cur_b);
     {
         const uint32_t r0 = tile * (uint32_t)T;
@@ -250,7 +216,7 @@ __global__ __launch_bounds__(KW, BIG ? 2 : KM_WAVES) void k_classify_kmer(const 
         const uint32_t len = o_next - cur_o;
         // A tile longer than the staged quads (only possible when the caller's length hint was too small): the reads that end
         // inside the quads -- a prefix of the tile -- are served, the others are handed back (rows of -2).
-        int Tn = tile_reads(tile);
+        int Tn = tile_reads(nreads, T, tile);
         uint32_t nq = (nbytes + 15u) >> 4;
         if (nbytes > (uint32_t)(NQ * 1024)) { // wave-uniform, rare
             const int Tn0 = Tn;
@@ -339,6 +305,7 @@ __global__ __launch_bounds__(KW, BIG ? 2 : KM_WAVES) void k_classify_kmer(const 
         // the read's running maximum, count << 16 | ~ref (0: the read left for the general path) -- the monotone counters make
         // (max_shared, first max_id) a running atomicMax.  add_posting = count + atomicMax.
         auto count_posting = [&](uint32_t t, uint32_t crow_b, uint32_t ref) -> uint32_t {
+            // (the same loop is count_posting of k_classify_tile; why it is not one function: rk_device.hpp)
             uint32_t* crow = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(cnt) + crow_b);
             const uint32_t M1 = CW - 1u, key = ref + 1u;
             uint32_t idx = ((ref * 0x9E3779B1u) >> 16) & M1, probe = 0, c = 0;
@@ -492,12 +459,12 @@ __global__ __launch_bounds__(KW, BIG ? 2 : KM_WAVES) void k_classify_kmer(const 
         // a later bucket of a search that goes on (again): hop_load issues its ONE 16-byte load, next_match tests it.  The drain
         // issues both rounds' loads before it pins them in registers (left to itself the compiler splits a bucket load and issues
         // the parts lazily, behind the short-circuit of match_cell: three loads per hop)
-        auto hop_load = [&](const Cand& c, uint32_t hop, bool again) -> u32x4 {
-            u32x4 v = {0u, 0u, 0u, 0u};
-            if (again) v = *reinterpret_cast<const u32x4*>(km1p + (((c.y >> km_r) + hop) & ((1u << km1_b) - 1u)));
+        auto hop_load = [&](const Cand& c, uint32_t hop, bool again) -> rk_u32x4 {
+            rk_u32x4 v = {0u, 0u, 0u, 0u};
+            if (again) v = *reinterpret_cast<const rk_u32x4*>(km1p + (((c.y >> km_r) + hop) & ((1u << km1_b) - 1u)));
             return v;
         };
-        auto next_match = [&](const Cand& c, uint32_t hop, const u32x4& nv, uint32_t& cell, bool& again) {
+        auto next_match = [&](const Cand& c, uint32_t hop, const rk_u32x4& nv, uint32_t& cell, bool& again) {
             if (again) {
                 const uint4 nb = make_uint4(nv.x, nv.y, nv.z, nv.w);
                 cell = match_cell(nb, ((c.y & km_rmask) << km_vb1) | (hop << (32u - KM1_HB)));
@@ -587,7 +554,7 @@ __global__ __launch_bounds__(KW, BIG ? 2 : KM_WAVES) void k_classify_kmer(const 
             const uint32_t listoff = (CMODE == CM_SPARSE ? valz : val) & 0x3fffffffu;
             uint64_t mm = __ballot(multi);
             while (mm) { // wave-uniform
-                const uint32_t pos = __builtin_amdgcn_mbcnt_hi((uint32_t)(mm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mm, 0u));
+                const uint32_t pos = lanes_below(mm);
                 const uint32_t space = (uint32_t)KM_MQ - mqn;
                 if (multi && pos < space) {
                     mq[2 * (mqn + pos)] = c.t | (rank << 8); mq[2 * (mqn + pos) + 1] = listoff;
@@ -627,7 +594,7 @@ __global__ __launch_bounds__(KW, BIG ? 2 : KM_WAVES) void k_classify_kmer(const 
                 // the searches that go on (about one lookup in ten, once) are continued for both rounds together: one more memory
                 // round trip per hop for the tile, not per round; the wave leaves when its last lane is done
                 for (uint32_t hop = 1; hop < (1u << KM1_HB) && __ballot(ga || gb); ++hop) {
-                    u32x4 na = hop_load(a, hop, ga), nb = hop_load(b, hop, gb);
+                    rk_u32x4 na = hop_load(a, hop, ga), nb = hop_load(b, hop, gb);
                     asm volatile("" : "+v"(na), "+v"(nb));
                     next_match(a, hop, na, ca, ga);
                     next_match(b, hop, nb, cb, gb);
@@ -650,7 +617,7 @@ __global__ __launch_bounds__(KW, BIG ? 2 : KM_WAVES) void k_classify_kmer(const 
             // issue: every lane computes; a lane without a group looks at the image's zero padding (the all-A k-mer) and tags its
             // candidates, should the filter pass that k-mer, with read 8, which has no windows -- the drain drops them
             uint32_t wl[CH], wh[CH], e0v[CH], fq[CH];
-            u32x4 fw[CH];
+            rk_u32x4 fw[CH];
             bool isqv[CH];
 #pragma unroll
             for (int s = 0; s < CH; ++s) {
@@ -681,12 +648,12 @@ __global__ __launch_bounds__(KW, BIG ? 2 : KM_WAVES) void k_classify_kmer(const 
                 const uint32_t sect_b = __umulhi(core * 0x85EBCA6Bu, kf4_n16) & ~15u;
                 e0v[s] = P0 | (t << 12);
                 fq[s] = 0u;
-                fw[s] = u32x4{0u, 0u, 0u, 0u}; // (defined on both paths: left undefined, the compiler reuses a register still in flight and waits)
+                fw[s] = rk_u32x4{0u, 0u, 0u, 0u}; // (defined on both paths: left undefined, the compiler reuses a register still in flight and waits)
                 if (isq) { // this lane's window of the group: its k-mer moves to the front, its entry names position + jq
                     wl[s] = __builtin_amdgcn_alignbit(wh[s], wl[s], 2u * jq);
                     if (act) e0v[s] += jq;
                     fq[s] = *reinterpret_cast<const uint32_t*>(reinterpret_cast<const uint8_t*>(kf4p) + (sect_b + 4u * jq));
-                } else fw[s] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const uint8_t*>(kf4p) + sect_b);
+                } else fw[s] = *reinterpret_cast<const rk_u32x4*>(reinterpret_cast<const uint8_t*>(kf4p) + sect_b);
             }
             // test + push.  has_invalid (a tile with a non-ACGT base, rare) runs its own copy of the code.
             auto test_step = [&](int s, auto inv_tag, auto nw_tag) {
@@ -721,7 +688,7 @@ __global__ __launch_bounds__(KW, BIG ? 2 : KM_WAVES) void k_classify_kmer(const 
                     const uint64_t m = __builtin_amdgcn_ballot_w64(cand);
                     // inverse_ballot turns the mask back into the branch predicate (no second compare for the exec mask)
                     if (__builtin_amdgcn_inverse_ballot_w64(m)) {
-                        const uint32_t mb = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+                        const uint32_t mb = lanes_below(m);
                         *reinterpret_cast<uint16_t*>(reinterpret_cast<uint8_t*>(q) + ((mb << 1) + (qcount << 1))) = (uint16_t)(e0v[s] + (uint32_t)j); // ds_write_b16
                     }
                     qcount += (uint32_t)__builtin_popcountll(m);
@@ -845,16 +812,10 @@ __global__ __launch_bounds__(KW, BIG ? 2 : KM_WAVES) void k_classify_kmer(const 
 // win_total: windows of a read of the hinted length, all k-mer sizes together (bounds every per-reference count)
 bool make_kmer_geom(KmerGeom& g, int maxlen, int nref, int expect_hits, int win_total, const int* nw_k, int nk, int nq, int& cmode, bool& big) {
     if (maxlen < 1) maxlen = 1;
-    cmode = win_total <= 255 ? CM_DENSE8 : CM_DENSE16;
-    const int clg = cmode == CM_DENSE8 ? 2 : 1;
-    g.cwords = (nref + (1 << clg) - 1) >> clg;
-    // Many references: a dense counter row per read would eat the LDS budget (and reference ids beyond 2048 would not fit at all),
-    // so the row becomes a 128-entry map of the references the read actually hits.
-    if (nref > 0 && g.cwords >= 129) { cmode = CM_SPARSE; g.cwords = 128; }
-    g.cwords = (g.cwords + 3) & ~3; // rows stay 16-byte aligned
-    int ds = 64;
-    while (ds < 3 * expect_hits && ds < 1024) ds <<= 1;
-    g.dset = ds;
+    const CounterLayout cl = counter_layout(nref, win_total);
+    cmode = cl.sparse ? CM_SPARSE : (cl.clg == 2 ? CM_DENSE8 : CM_DENSE16);
+    g.cwords = (cl.cwords + 3) & ~3; // rows stay 16-byte aligned
+    g.dset = hit_multiset_slots(expect_hits);
     int T = (nq * 1024 - 15) / maxlen;
     if (T > KM_MAX_T) T = KM_MAX_T;
     if (T < 1) T = 1;
@@ -872,15 +833,15 @@ bool make_kmer_geom(KmerGeom& g, int maxlen, int nref, int expect_hits, int win_
     g.L = maxlen;
     for (int j = 0; j < KM_MAX_KS; ++j) {
         g.gpr[j] = j < nk ? (nw_k[j] + 3) >> 2 : 0;
-        g.magic[j] = g.gpr[j] >= 2 ? 0xFFFFFFFFu / (uint32_t)g.gpr[j] + 1u : 0u;
+        g.magic[j] = div_magic((uint32_t)g.gpr[j]);
     }
     return true;
 }
 
 template <int KT>
-hipError_t launch_k(int nq, int cmode, bool big, bool fam, dim3 grid, hipStream_t st, const uint8_t* bases, const uint32_t* offs, uint32_t nreads,
-                    int S, const RefIndex& ix, const KmerSets& ksets, int32_t* out4, const DevPolicy& pol, const KmerGeom& geo) {
-#define RK_KM_GO(NQ, CM, BIG, FAM) hipLaunchKernelGGL((k_classify_kmer<KT, NQ, CM, BIG, FAM>), grid, dim3(KW), 0, st, bases, offs, nreads, S, ix, ksets, out4, pol, geo)
+hipError_t launch_k(int nq, int cmode, bool big, bool fam, dim3 grid, const ReadBatch& b, int S, const RefIndex& ix, const KmerSets& ksets,
+                    int32_t* out4, const DevPolicy& pol, const KmerGeom& geo) {
+#define RK_KM_GO(NQ, CM, BIG, FAM) hipLaunchKernelGGL((k_classify_kmer<KT, NQ, CM, BIG, FAM>), grid, dim3(KW), 0, b.st, b.bases, b.offs, b.nreads, S, ix, ksets, out4, pol, geo)
     // (the sparse counters cannot subtract: they walk the plain form of every list and never see a (base, exceptions) value)
 #define RK_KM_CM(NQ, BIG)                                                                                    \
     do {                                                                                                     \
@@ -905,28 +866,26 @@ bool classify_kmer_supported(int nref, int maxlen, int k) {
 }
 
 // ksets: the structures of every k-mer size of the run (n = 1: the compile-time-k kernels, whose structures are ix.kf4 / km1 too)
-hipError_t launch_classify_kmer(const uint8_t* bases, const uint32_t* offs, uint32_t nreads, const KmerSets& ksets, int S, const RefIndex& ix,
-                                int32_t* out4, const DevPolicy& pol, int maxlen, int expect_hits, hipStream_t st, int nmin_cap) {
-    if (nreads == 0) return hipSuccess;
+hipError_t launch_classify_kmer(const ReadBatch& b, const KmerSets& ksets, int S, const RefIndex& ix, int32_t* out4, const DevPolicy& pol) {
+    if (b.nreads == 0) return hipSuccess;
     if (ksets.n < 1 || ksets.n > KM_MAX_KS) return hipErrorInvalidValue;
-    const int nq = maxlen <= 1024 - 15 ? 1 : 2;
+    const int nq = b.maxlen <= 1024 - 15 ? 1 : 2;
     int nw_k[KM_MAX_KS] = {0}, win_total = 0;
-    for (int j = 0; j < ksets.n; ++j) { nw_k[j] = num_windows(maxlen, ksets.k[j], pol.drop_last_window); win_total += nw_k[j]; }
+    for (int j = 0; j < ksets.n; ++j) { nw_k[j] = num_windows(b.maxlen, ksets.k[j], pol.drop_last_window); win_total += nw_k[j]; }
     KmerGeom geo;
     int cmode = 0;
     bool big = false;
-    if (!make_kmer_geom(geo, maxlen, ix.nref, expect_hits, win_total, nw_k, ksets.n, nq, cmode, big)) return hipErrorInvalidConfiguration;
-    geo.nmin_cap = nmin_cap;
-    const uint32_t ntiles = (nreads + (uint32_t)geo.T - 1) / (uint32_t)geo.T;
+    if (!make_kmer_geom(geo, b.maxlen, ix.nref, b.expect_hits, win_total, nw_k, ksets.n, nq, cmode, big)) return hipErrorInvalidConfiguration;
+    geo.nmin_cap = b.nmin_cap;
+    const uint32_t ntiles = (b.nreads + (uint32_t)geo.T - 1) / (uint32_t)geo.T;
     const bool fam = ix.kbase_n != 0u; // lists stored as (base, exceptions) exist
-    uint32_t grid = ntiles;
-    grid = (grid + 7u) & ~7u; // whole rounds of the 8 XCDs: the virtual ids then cover [0, grid) exactly
-    if (ksets.n > 1) return launch_k<0>(nq, cmode, big, fam, dim3(grid), st, bases, offs, nreads, S, ix, ksets, out4, pol, geo);
-#define RK_KM_K(KT) case KT: return launch_k<KT>(nq, cmode, big, fam, dim3(grid), st, bases, offs, nreads, S, ix, ksets, out4, pol, geo)
+    const uint32_t grid = xcd_grid(ntiles); // one tile per workgroup
+    if (ksets.n > 1) return launch_k<0>(nq, cmode, big, fam, dim3(grid), b, S, ix, ksets, out4, pol, geo);
+#define RK_KM_K(KT) case KT: return launch_k<KT>(nq, cmode, big, fam, dim3(grid), b, S, ix, ksets, out4, pol, geo)
     switch (ksets.k[0]) {
         RK_KM_K(8); RK_KM_K(9); RK_KM_K(10); RK_KM_K(11); RK_KM_K(12); RK_KM_K(13); RK_KM_K(14); RK_KM_K(15); RK_KM_K(16);
         case 17: case 18: case 19: case 20: // wide k-mers: one run-time-k instantiation (KT = 32)
-            return ix.kkeys ? launch_k<32>(nq, cmode, big, fam, dim3(grid), st, bases, offs, nreads, S, ix, ksets, out4, pol, geo) : hipErrorInvalidValue;
+            return ix.kkeys ? launch_k<32>(nq, cmode, big, fam, dim3(grid), b, S, ix, ksets, out4, pol, geo) : hipErrorInvalidValue;
         default: return hipErrorInvalidValue;
     }
 #undef RK_KM_K

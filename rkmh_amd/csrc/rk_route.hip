@@ -9,14 +9,15 @@ static int count_bins_env() {
     const char* e = getenv("RKMH_COUNT_BINS"); // read per pass (a few launches each): tests switch it inside one process
     return e && *e ? atoi(e) : -1;
 }
-static int count_partitioned(rk_ctx* c, const void* d_bases, const void* d_offs, int64_t nreads, uint32_t ml, int expect,
-                             rk_counter* k, uint64_t total_bases, hipStream_t st, bool* done) {
+// tl: the count pass into k as the atomic form launches it
+static int count_partitioned(TileLaunch tl, rk_counter* k, uint64_t total_bases, bool* done) {
     *done = false;
+    const hipStream_t st = tl.batch.st;
     const int env = count_bins_env();
-    if (env == 0 || total_bases == 0 || !classify_tile_supported(0, (int)ml)) return RK_OK;
+    if (env == 0 || total_bases == 0 || !classify_tile_supported(0, tl.batch.maxlen)) return RK_OK;
     const uint64_t stride = (total_bases + 3) & ~3ull;
     CountPlan pl;
-    if (stride >= (1ull << 31) || !count_plan(k->slots, stride * (uint64_t)c->ks.n, &pl)) return RK_OK;
+    if (stride >= (1ull << 31) || !count_plan(k->slots, stride * (uint64_t)tl.ks->n, &pl)) return RK_OK;
     if (env < 0 && (pl.n < ((uint64_t)4 << 20) || pl.nsub < 256)) return RK_OK;
     std::lock_guard<std::mutex> lock(k->mu);
     if (!k->last) HIPCHK(hipEventCreateWithFlags(&k->last, hipEventDisableTiming));
@@ -26,8 +27,9 @@ static int count_partitioned(rk_ctx* c, const void* d_bases, const void* d_offs,
     if (need > k->ws.cap) { HIPCHK(hipDeviceSynchronize()); RKCHK(k->ws.reserve(need)); } // nothing may still be reading the old arrays
     const CountScratch sc = count_plan_carve(pl, k->ws.p);
     HIPCHK(launch_count_prepare(pl, sc, st));
-    HIPCHK(launch_classify_tile((const uint8_t*)d_bases, (const uint32_t*)d_offs, (uint32_t)nreads, c->ks, c->S, c->ix, k->d, k->slots, 0, 1,
-                                (int32_t*)sc.flat, c->pol, (int)ml, expect, st, (uint32_t)stride));
+    tl.out4 = (int32_t*)sc.flat; // the kernel writes every window's slot here instead of counting it
+    tl.slot_stride = (uint32_t)stride;
+    HIPCHK(launch_classify_tile(tl));
     HIPCHK(launch_count_bins(pl, sc, k->d, st));
     HIPCHK(hipEventRecord(k->last, st));
     k->last_set = true;
@@ -49,6 +51,23 @@ int fused_device(rk_ctx* c, const void* d_bases, const void* d_offs, int64_t nre
     uint32_t ml = max_read_len < 1 ? 1 : (max_read_len > (uint32_t)FUSED_MAXLEN ? (uint32_t)FUSED_MAXLEN : max_read_len);
     int expect = 0; // hits an error-free read is expected to score: sizes the kernel's per-read hit multiset
     for (int j = 0; j < c->ks.n; ++j) expect += (int)(c->density * (double)num_windows((int)ml, c->ks.k[j], c->pol.drop_last_window)) + 1;
+    TileLaunch tl; // what every pass through k_classify_tile has in common
+    ReadBatch& rb = tl.batch;
+    rb.bases = (const uint8_t*)d_bases;
+    rb.offs = (const uint32_t*)d_offs;
+    rb.nreads = (uint32_t)nreads;
+    rb.maxlen = (int)ml;
+    rb.expect_hits = expect;
+    rb.st = st;
+    RefIndex ix0 = c->ix; ix0.keepkey = nullptr;
+    tl.pass = mode == 1 ? TILE_COUNT : (counter ? TILE_CLASSIFY_MASKED : TILE_CLASSIFY);
+    tl.ks = &c->ks;
+    tl.S = c->S;
+    tl.ix = &ix0;
+    tl.pol = &c->pol;
+    tl.counter = counter;
+    tl.slots = slots;
+    tl.min_occ = min_occ;
     if (mode == 1 && count_into->compact) {
         // pass 1 into a compact depth map: hash every window, count the few whose slot is tracked (k_classify_tile, MODE 1, cs.tab)
         if (count_into->index_gen != c->index_gen || count_into->ctx != c)
@@ -57,9 +76,8 @@ int fused_device(rk_ctx* c, const void* d_bases, const void* d_offs, int64_t nre
         if (nh > (uint64_t)c->S || max_read_len > (uint32_t)FUSED_MAXLEN || !classify_tile_supported(0, (int)ml))
             return fail(RK_ERR_NEED_FULL, "reads of up to %u bases have more hashes (%llu) than the sketch keeps (%d): bottom-s selection needs the "
                         "depth of every hash, which a compact depth map does not hold", max_read_len, (unsigned long long)nh, c->S);
-        RefIndex ix0 = c->ix; ix0.keepkey = nullptr;
-        HIPCHK(launch_classify_tile((const uint8_t*)d_bases, (const uint32_t*)d_offs, (uint32_t)nreads, c->ks, c->S, ix0,
-                                    counter, slots, 0, 1, nullptr, c->pol, (int)ml, expect, st, 0, 0x7fffffff, &count_into->cs));
+        tl.compact = &count_into->cs;
+        HIPCHK(launch_classify_tile(tl));
         std::lock_guard<std::mutex> lock(count_into->mu);
         if (!count_into->last_atomic) HIPCHK(hipEventCreateWithFlags(&count_into->last_atomic, hipEventDisableTiming));
         HIPCHK(hipEventRecord(count_into->last_atomic, st)); // readers of the map wait for the latest pass (they all add with atomics: no order among them)
@@ -68,7 +86,7 @@ int fused_device(rk_ctx* c, const void* d_bases, const void* d_offs, int64_t nre
     }
     if (mode == 1) {
         bool done = false;
-        RKCHK(count_partitioned(c, d_bases, d_offs, nreads, ml, expect, count_into, total_bases, st, &done));
+        RKCHK(count_partitioned(tl, count_into, total_bases, &done));
         if (done) return RK_OK;
         // atomic form: other passes into this table may still be adding with plain stores
         std::lock_guard<std::mutex> lock(count_into->mu);
@@ -78,9 +96,7 @@ int fused_device(rk_ctx* c, const void* d_bases, const void* d_offs, int64_t nre
         // two atomic passes on different streams would wait for the second one only and its plain adds could lose the first one's counts
         if (count_into->last_atomic_set) HIPCHK(hipStreamWaitEvent(st, count_into->last_atomic, 0));
         if (!classify_tile_supported(0, (int)ml)) return fail(RK_ERR_LIMIT, "count pass: batch not supported by the fused kernel");
-        RefIndex ix0 = c->ix; ix0.keepkey = nullptr;
-        HIPCHK(launch_classify_tile((const uint8_t*)d_bases, (const uint32_t*)d_offs, (uint32_t)nreads, c->ks, c->S, ix0,
-                                    counter, slots, min_occ, 1, nullptr, c->pol, (int)ml, expect, st)); // (given an array there, it would write slots to it)
+        HIPCHK(launch_classify_tile(tl)); // (out4 stays null: given an array there, the pass would write slots to it)
         // a later pass of either form must not overlap this one
         if (!count_into->last_atomic) HIPCHK(hipEventCreateWithFlags(&count_into->last_atomic, hipEventDisableTiming));
         HIPCHK(hipEventRecord(count_into->last_atomic, st));
@@ -93,17 +109,18 @@ int fused_device(rk_ctx* c, const void* d_bases, const void* d_offs, int64_t nre
         if (c->ksets_m.n >= 1) ix.km1 = c->ksets_m.km1[0]; // (the compile-time-k kernels read the first size's structures from ix)
         ix.kv = c->d_kvm.as<uint4>();                       // (hash-space kernels: the key array with the mask's verdict in it)
     }
-    const int nmin_cap = (mode != 1 && c->depth && c->min_num_bound >= 0) ? c->min_num_bound : 0x7fffffff;
+    if (c->depth && c->min_num_bound >= 0) rb.nmin_cap = c->min_num_bound;
     // classification with k-mer sizes the exact k-mer maps were enumerated for: the k-mer-space kernel (rk_kmer.hip); under a
     // bounded depth filter it reads the masked copies of the maps (a dropped key is a zero-hash k-mer there)
     if (!counter && c->ksets.n == c->ks.n && c->ksets.n >= 1 && (!bounded || c->ksets_m.n == c->ksets.n) &&
         classify_kmer_supported(c->ix.nref, (int)ml, c->ks.k[0]))
-        HIPCHK(launch_classify_kmer((const uint8_t*)d_bases, (const uint32_t*)d_offs, (uint32_t)nreads, bounded ? c->ksets_m : c->ksets, c->S, ix,
-                                    (int32_t*)d_out4, c->pol, (int)ml, expect, st, nmin_cap));
-    else if (classify_tile_supported(c->ix.nref, (int)ml))
-        HIPCHK(launch_classify_tile((const uint8_t*)d_bases, (const uint32_t*)d_offs, (uint32_t)nreads, c->ks, c->S, ix,
-                                    counter, slots, min_occ, 0, (int32_t*)d_out4, c->pol, (int)ml, expect, st, 0, nmin_cap, nullptr, c->dedup));
-    else
+        HIPCHK(launch_classify_kmer(rb, bounded ? c->ksets_m : c->ksets, c->S, ix, (int32_t*)d_out4, c->pol));
+    else if (classify_tile_supported(c->ix.nref, (int)ml)) {
+        tl.ix = &ix;
+        tl.out4 = (int32_t*)d_out4;
+        tl.dedup = c->dedup;
+        HIPCHK(launch_classify_tile(tl));
+    } else
         HIPCHK(launch_fill_reroute((int32_t*)d_out4, (uint32_t)nreads, st)); // e.g. more than 16384 references: general path
     // bound > 0: the first `bound` surviving windows of every answered read are counted by hashing them (k_min_num_probe)
     if (bounded && c->min_num_bound > 0)

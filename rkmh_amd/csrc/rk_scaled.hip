@@ -31,9 +31,6 @@ __device__ __forceinline__ bool keeps(const uint64_t* __restrict__ v, uint64_t t
     if (t == 0 || v[t - 1] != x) return true;
     return segment_starts_at(off, nseg, t); // equal to the element before it: stays only as the first of the next segment
 }
-__device__ __forceinline__ uint32_t lanes_below(uint64_t bal) { // set bits of bal below this lane
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
-}
 
 template <int MODE>
 __global__ __launch_bounds__(KEEP_T) void k_keep_count(const uint64_t* __restrict__ v, uint64_t n, uint64_t max_hash, const uint64_t* __restrict__ off,

@@ -74,10 +74,10 @@ class _Panel:
     def close(self):
         self.c.close()
 
-    def dense(self, L, keep=None):
-        """an error-free read of L bases: the first `keep` (default: all) from a reference, the rest random text"""
+    def dense(self, L, keep=None, ref=None):
+        """an error-free read of L bases: the first `keep` (default: all) from a reference (default: any), the rest random text"""
         keep = L if keep is None else keep
-        g = self.refs[int(self.rng.integers(0, len(self.refs)))]
+        g = self.refs[int(self.rng.integers(0, len(self.refs))) if ref is None else ref]
         p = int(self.rng.integers(0, len(g) - keep + 1))
         return g[p: p + keep] + _rand(self.rng, L - keep)
 
@@ -159,14 +159,6 @@ def family(orc):
     p.close()
 
 
-@pytest.fixture(scope="module")
-def many(orc):
-    """more than 512 references: the per-read counters are the sparse map (CM_SPARSE)"""
-    p = _Panel(orc, _random_refs(16, 520, glen=200), [16], 105)
-    yield p
-    p.close()
-
-
 # ---- 1. dense tiles at every tile geometry: 0 .. T dense reads per tile, first / last / alternating, random text between them ---------
 @pytest.mark.parametrize("L,T", [(100, 8), (150, 6), (250, 4), (500, 2)])
 def test_dense_tiles(k16, L, T):
@@ -230,6 +222,20 @@ def test_family_panel(family):
     assert raw[:, 1].max() == 134
 
 
-def test_sparse_counters(many):
-    raw = many.check(_dense_and_mixed(many, 6, 150), "520 references")
-    assert raw[:, 1].max() == 134
+@pytest.mark.parametrize("nref,L,glen", [(512, 150, 200), (513, 150, 200), (256, 300, 400), (257, 300, 400)])
+def test_sparse_counters(orc, nref, L, glen):
+    """Both sides of both switches of the per-read counter form (the launcher's rule: 8-bit fields while no read has more than 255
+    windows, else 16-bit; a 128-entry sparse map from 129 words per row up):
+        512 references, 150 bases: 134 windows, 8-bit fields, 128 words -- the largest dense row;  513: 129 words, sparse
+        256 references, 300 bases: 284 windows, 16-bit fields, 128 words -- dense;                  257: sparse
+    The references are `glen` bases long, so a dense read lies inside one of them.  One read is drawn from the last reference and one
+    from the first: at the dense boundary the arg-max of the former reads the last field of the row's last word."""
+    p = _Panel(orc, _random_refs(16, nref, glen=glen), [16], 105)
+    try:
+        T = min((1024 - 15) // L, 8)
+        reads = _dense_and_mixed(p, T, L) + [p.dense(L, ref=nref - 1), p.dense(L, ref=0)]
+        raw = p.check(reads, "%d references, %d bases" % (nref, L))
+    finally:
+        p.close()
+    assert raw[:, 1].max() == L - 16
+    assert raw[-2, :2].tolist() == [nref - 1, L - 16] and raw[-1, :2].tolist() == [0, L - 16]
