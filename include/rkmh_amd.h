@@ -690,8 +690,8 @@ int rk_scaled_distance(int64_t shared, int64_t la, int64_t lb, int k, double* ja
  *     out4[t] = (ref, unique = count[ref], total[ref], remaining = |alive| after the removal), four int32,
  *   is written and alive -= R_ref; stop after max_rounds rows.  *nrounds = the number of rows written.
  *   It follows that unique never increases from row to row, that no reference is picked twice, that nq - sum(unique) = remaining of
- *   the last row, and that a reference whose total is below min_shared is never picked.  Abundance, base-pair estimates and
- *   weighting are not part of it.
+ *   the last row, and that a reference whose total is below min_shared is never picked.  Base-pair estimates are not part of
+ *   it; abundance and the weighted share of a pick: "ABUNDANCE" below.
  * All three entries refuse (RK_ERR_ARG, a size beyond the limit RK_ERR_LIMIT) before anything is launched: NULL, nref < 1,
  * min_shared < 1, max_rounds < 1, nq > 2^31 - 1.
  * rk_gather_scaled: host arrays; additionally refuses a query that is not strictly ascending or holds 0, offsets that decrease and a
@@ -714,6 +714,42 @@ int rk_gather_scaled_device(rk_ctx* ctx, const void* d_q_values, uint64_t nq, co
                             uint64_t r_nvalues, int min_shared, int max_rounds, void* d_out4, int* nrounds, void* hip_stream);
 int rk_gather_scaled_host(const uint64_t* q_values, uint64_t nq, const uint64_t* r_values, const uint64_t* r_offsets, int nref,
                           int min_shared, int max_rounds, int threads, int32_t* out4, int* nrounds);
+
+/* ------------------------------------------------------------------------------------------------
+ * ABUNDANCE (`rkmh sketch --scaled <n> --abund`, `rkmh gather --abund`; what sourmash calls track_abundance).  These are this
+ * library's own definitions, chosen to coincide with sourmash's where that can be known.
+ *   The abundance sketch of a sequence at max_hash: its scaled sketch values[] (unchanged: ascending, distinct, 0 < h <= max_hash)
+ *   plus a parallel uint32 abund[]: abund[j] = the number of windows of that sequence whose hash equals values[j], pooled over the
+ *   k-mer sizes as the values are.  Windows that hash to 0 are not counted.  Every abundance is >= 1 and sum(abund) = the number of
+ *   kept windows (a count beyond 2^32 - 1 is stored as 2^32 - 1).  A batch is the CSR of scaled sketches plus one uint32 per value.
+ *   Union (the -g reduction; one query per -f file): the ascending distinct union of the values; abundances are summed per value,
+ *   saturating at 2^32 - 1.  Cutting to a larger `scaled` keeps the prefix of both arrays.
+ *   Weighted gather: rows and pick rule are exactly rk_gather_scaled's -- the pick is by the UNWEIGHTED count, lowest reference index
+ *   among equals.  Row t also gets uint64 wunique[t] = the sum of q_abund[i] over the query values i that the pick of row t removes
+ *   (the ones still alive at its turn).  wtotal = sum(q_abund) is the caller's to compute.  Reference abundances play no part.  It
+ *   follows that with all abundances 1 wunique = unique, and that sum_t wunique[t] + the abundances of the values alive at the end
+ *   = wtotal.
+ * rk_sketch_scaled_abund_batch: rk_sketch_scaled_batch plus *abunds (both malloc'd, rk_free); the values are bit-identical to
+ * rk_sketch_scaled_batch's.  On the device the abundance of a value is the length of its run among the sorted kept values of its
+ * sequence, taken where the repeats are dropped (rk_scaled.hip: k_keep_first_src, k_run_lengths); it leaves with the values.
+ * rk_merge_scaled_abund: host only; rk_merge_scaled plus the summed abundances; RK_ERR_ARG also for a NULL abunds and an abundance of 0.
+ * rk_gather_scaled_abund / _device / _host: rk_gather_scaled / _device / _host plus q_abund (uint32[nq]) and wunique; the checks of
+ * their plain forms, and RK_ERR_ARG for a NULL q_abund when nq > 0 and for a NULL wunique.  wunique takes min(max_rounds, nref)
+ * uint64 (d_wunique: max_rounds may be given) and is zeroed that far at the start of every call, then rows [0, *nrounds) are written.
+ * The two entries that take host arrays also refuse an abundance of 0; the device entry cannot check that cheaply: there a 0 adds
+ * nothing.  On the device k_gather_remove_w takes k_gather_remove's place, so a round stays three launches. */
+int rk_sketch_scaled_abund_batch(rk_ctx* ctx, const uint8_t* bases, const uint64_t* offsets, int64_t nseq, const int* ks, int nks,
+                                 uint64_t max_hash, uint64_t** values, uint32_t** abunds, uint64_t* sk_offsets);
+int rk_merge_scaled_abund(const uint64_t* values, const uint32_t* abunds, const uint64_t* offsets, int n, uint64_t max_hash,
+                          uint64_t** out_values, uint32_t** out_abunds, uint64_t* out_len);
+int rk_gather_scaled_abund(rk_ctx* ctx, const uint64_t* q_values, const uint32_t* q_abund, uint64_t nq, const uint64_t* r_values,
+                           const uint64_t* r_offsets, int nref, int min_shared, int max_rounds, int32_t* out4, uint64_t* wunique, int* nrounds);
+int rk_gather_scaled_abund_device(rk_ctx* ctx, const void* d_q_values, const void* d_q_abund, uint64_t nq, const void* d_r_values,
+                                  const void* d_r_offsets, int nref, uint64_t r_nvalues, int min_shared, int max_rounds, void* d_out4,
+                                  void* d_wunique, int* nrounds, void* hip_stream);
+int rk_gather_scaled_abund_host(const uint64_t* q_values, const uint32_t* q_abund, uint64_t nq, const uint64_t* r_values,
+                                const uint64_t* r_offsets, int nref, int min_shared, int max_rounds, int threads, int32_t* out4,
+                                uint64_t* wunique, int* nrounds);
 
 #ifdef __cplusplus
 }

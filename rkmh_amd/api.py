@@ -80,6 +80,7 @@ class IndexStats(C.Structure):
 
 
 _u8p, _u64p, _i32p, _ip = C.POINTER(C.c_uint8), C.POINTER(C.c_uint64), C.POINTER(C.c_int32), C.POINTER(C.c_int)
+_u32p = C.POINTER(C.c_uint32)
 
 _SIGS = {
     "rk_default_policy": (None, [C.POINTER(Policy)]),
@@ -251,6 +252,13 @@ _SIGS = {
     "rk_gather_scaled_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_int, C.c_int,
                                           C.c_void_p, _ip, C.c_void_p]),
     "rk_gather_scaled_host": (C.c_int, [_u64p, C.c_uint64, _u64p, _u64p, C.c_int, C.c_int, C.c_int, C.c_int, _i32p, _ip]),
+    "rk_sketch_scaled_abund_batch": (C.c_int, [C.c_void_p, _u8p, _u64p, C.c_int64, C.POINTER(C.c_int), C.c_int, C.c_uint64, C.POINTER(_u64p),
+                                               C.POINTER(_u32p), _u64p]),
+    "rk_merge_scaled_abund": (C.c_int, [_u64p, _u32p, _u64p, C.c_int, C.c_uint64, C.POINTER(_u64p), C.POINTER(_u32p), C.POINTER(C.c_uint64)]),
+    "rk_gather_scaled_abund": (C.c_int, [C.c_void_p, _u64p, _u32p, C.c_uint64, _u64p, _u64p, C.c_int, C.c_int, C.c_int, _i32p, _u64p, _ip]),
+    "rk_gather_scaled_abund_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_int,
+                                                C.c_int, C.c_void_p, C.c_void_p, _ip, C.c_void_p]),
+    "rk_gather_scaled_abund_host": (C.c_int, [_u64p, _u32p, C.c_uint64, _u64p, _u64p, C.c_int, C.c_int, C.c_int, C.c_int, _i32p, _u64p, _ip]),
 }
 
 
@@ -985,6 +993,43 @@ def gather_scaled_host(q, r_values, r_offsets, min_shared=1, max_rounds=None, th
     return out[: n.value].copy()
 
 
+def _abund(abund, values):
+    """the abundances that lie parallel to `values`: uint32, one per value"""
+    abund = np.ascontiguousarray(abund, dtype=np.uint32)
+    if abund.ndim != 1 or len(abund) != len(values):
+        raise ValueError("%d abundances for %d values" % (abund.size, len(values)))
+    return abund
+
+
+def merge_scaled_abund(values, abunds, offsets, max_hash=(1 << 64) - 1):
+    """rk_merge_scaled_abund (host code, no GPU): merge_scaled's values plus, per value, the sum of its abundances over the sketches,
+    saturating at 2^32 - 1 -> (values uint64, abunds uint32)."""
+    values, offsets = _csr(values, offsets)
+    abunds = _abund(abunds, values)
+    out, oa, n = _u64p(), _u32p(), C.c_uint64()
+    lib = load_library()
+    _chk(lib.rk_merge_scaled_abund(_p(values, C.c_uint64), _p(abunds, C.c_uint32), _p(offsets, C.c_uint64), len(offsets) - 1, C.c_uint64(int(max_hash)),
+                                   C.byref(out), C.byref(oa), C.byref(n)))
+    m = int(n.value)
+    r = np.ctypeslib.as_array(out, shape=(max(m, 1),))[:m].copy()
+    a = np.ctypeslib.as_array(oa, shape=(max(m, 1),))[:m].copy()
+    lib.rk_free(out)
+    lib.rk_free(oa)
+    return r, a
+
+
+def gather_scaled_abund_host(q, q_abund, r_values, r_offsets, min_shared=1, max_rounds=None, threads=1):
+    """rk_gather_scaled_abund_host (host code, no GPU): the rows of gather_scaled_host and, per row, wunique = the summed abundances
+    of the query values that pick removes -> (int32 [n, 4], uint64 [n])."""
+    q, r_values, r_offsets, nref, max_rounds, out = _gather_args(q, r_values, r_offsets, max_rounds)
+    q_abund = _abund(q_abund, q)
+    wu = np.zeros(len(out), dtype=np.uint64)
+    n = C.c_int(0)
+    _chk(load_library().rk_gather_scaled_abund_host(_p(q, C.c_uint64), _p(q_abund, C.c_uint32), len(q), _p(r_values, C.c_uint64), _p(r_offsets, C.c_uint64),
+                                                    nref, int(min_shared), max_rounds, int(threads), _p(out, C.c_int32), _p(wu, C.c_uint64), C.byref(n)))
+    return out[: n.value].copy(), wu[: n.value].copy()
+
+
 class Context:
     """One GPU. Methods are named after the reference's functions they replace."""
 
@@ -1123,6 +1168,23 @@ class Context:
         self._lib.rk_free(out)
         return r, so
 
+    def sketch_scaled_abund_batch(self, bases, offsets, ks, max_hash):
+        """rk_sketch_scaled_abund_batch: sketch_scaled_batch's (values, offsets) and abunds uint32, parallel to the values: the number
+        of windows of the sequence that hash to each -> (values, abunds, offsets)."""
+        ks = _ks(ks)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = len(offsets) - 1
+        so = np.zeros(n + 1, dtype=np.uint64)
+        out, oa = _u64p(), _u32p()
+        _chk(self._lib.rk_sketch_scaled_abund_batch(self._h, _p(bases, C.c_uint8), _p(offsets, C.c_uint64), n, _p(ks, C.c_int), len(ks),
+                                                    C.c_uint64(int(max_hash)), C.byref(out), C.byref(oa), _p(so, C.c_uint64)))
+        tot = int(so[-1])
+        r = np.ctypeslib.as_array(out, shape=(max(tot, 1),))[:tot].copy()
+        a = np.ctypeslib.as_array(oa, shape=(max(tot, 1),))[:tot].copy()
+        self._lib.rk_free(out)
+        self._lib.rk_free(oa)
+        return r, a, so
+
     def compare_scaled(self, a_values, a_offsets, b_values=None, b_offsets=None, lanes=0):
         """rk_compare_scaled: every CSR sketch of `a` against every one of `b` (None: of `a` itself) -> int32 [na, nb], the number
         of shared values.  lanes: 0 (chosen from the lengths), 1, 8 or 64 lanes of the kernel per pair; the answer is the same."""
@@ -1169,6 +1231,30 @@ class Context:
         _chk(self._lib.rk_gather_scaled_device(self._h, C.c_void_p(d_q_ptr), C.c_uint64(int(nq)), C.c_void_p(d_r_values_ptr), C.c_void_p(d_r_offsets_ptr),
                                                int(nref), C.c_uint64(int(r_nvalues)), int(min_shared), int(nref if max_rounds is None else max_rounds),
                                                C.c_void_p(d_out4_ptr), C.byref(n), C.c_void_p(stream)))
+        return n.value
+
+    def gather_scaled_abund(self, q, q_abund, r_values, r_offsets, min_shared=1, max_rounds=None):
+        """rk_gather_scaled_abund: gather_scaled's rows and, per row, wunique = the summed abundances (q_abund: uint32, one per value of
+        q, none 0) of the query values that pick removes -> (int32 [n, 4], uint64 [n])."""
+        q, r_values, r_offsets, nref, max_rounds, out = _gather_args(q, r_values, r_offsets, max_rounds)
+        q_abund = _abund(q_abund, q)
+        wu = np.zeros(len(out), dtype=np.uint64)
+        n = C.c_int(0)
+        _chk(self._lib.rk_gather_scaled_abund(self._h, _p(q, C.c_uint64), _p(q_abund, C.c_uint32), len(q), _p(r_values, C.c_uint64), _p(r_offsets, C.c_uint64),
+                                              nref, int(min_shared), max_rounds, _p(out, C.c_int32), _p(wu, C.c_uint64), C.byref(n)))
+        return out[: n.value].copy(), wu[: n.value].copy()
+
+    def gather_scaled_abund_device(self, d_q_ptr, d_q_abund_ptr, nq, d_r_values_ptr, d_r_offsets_ptr, nref, r_nvalues, d_out4_ptr, d_wunique_ptr,
+                                   min_shared=1, max_rounds=None, stream=None):
+        """gather_scaled_device with the query's abundances (d_q_abund: nq uint32) and d_wunique (max_rounds uint64, None: nref) -> the
+        number of rows written.  An abundance of 0 adds nothing."""
+        if stream is None:
+            stream = self.stream
+        n = C.c_int(0)
+        _chk(self._lib.rk_gather_scaled_abund_device(self._h, C.c_void_p(d_q_ptr), C.c_void_p(d_q_abund_ptr), C.c_uint64(int(nq)), C.c_void_p(d_r_values_ptr),
+                                                     C.c_void_p(d_r_offsets_ptr), int(nref), C.c_uint64(int(r_nvalues)), int(min_shared),
+                                                     int(nref if max_rounds is None else max_rounds), C.c_void_p(d_out4_ptr), C.c_void_p(d_wunique_ptr),
+                                                     C.byref(n), C.c_void_p(stream)))
         return n.value
 
     # ---- outer boundary (batches) ------------------------------------------------------------

@@ -84,8 +84,8 @@ extern "C" void rk_ctx_destroy(rk_ctx* c) {
     e = hipDeviceSynchronize(); (void)e;
     for (DevBuf* b : {&c->d_fpb, &c->d_base, &c->d_kv, &c->d_post, &c->d_pre, &c->d_keepbits, &c->d_kpost, &c->d_kbase, &c->d_kkeys, &c->d_kslots, &c->w_bases, &c->w_tiles, &c->w_hashes, &c->w_segoff,
                       &c->w_ids, &c->w_sk, &c->w_lens, &c->w_out, &c->w_misc, &c->w_sel, &c->w_selstate, &c->w_table, &c->w_gcount, &c->w_tail, &c->w_dedup,
-                      &c->w_sc_cnt, &c->w_sc_pre, &c->w_sc_off, &c->w_sc_a, &c->w_sc_b,
-                      &c->w_g_hit, &c->w_g_total, &c->w_g_alive, &c->w_g_state, &c->w_g_cand, &c->w_g_coff, &c->w_g_count, &c->w_g_list}) b->release();
+                      &c->w_sc_cnt, &c->w_sc_pre, &c->w_sc_off, &c->w_sc_a, &c->w_sc_b, &c->w_sc_src, &c->w_sc_ab,
+                      &c->w_g_hit, &c->w_g_total, &c->w_g_alive, &c->w_g_state, &c->w_g_cand, &c->w_g_coff, &c->w_g_count, &c->w_g_list, &c->w_g_ab}) b->release();
     for (int j = 0; j < KM_MAX_KS; ++j) { c->d_kf4[j].release(); c->d_km1[j].release(); c->d_km1v[j].release(); c->d_km1m[j].release(); c->d_km1cells[j].release(); }
     c->d_keepkey.release(); c->d_kvm.release();
     for (auto& s : c->slot) {

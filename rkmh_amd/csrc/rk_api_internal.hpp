@@ -154,7 +154,8 @@ struct rk_ctx {
     // workspaces for the general path
     DevBuf w_bases, w_tiles, w_hashes, w_segoff, w_ids, w_sk, w_lens, w_out, w_misc, w_sel, w_selstate, w_table, w_gcount, w_tail, w_dedup;
     DevBuf w_sc_cnt, w_sc_pre, w_sc_off, w_sc_a, w_sc_b; // scaled sketches (rk_scaled.hip): block counts, their scan, CSR offsets, kept / distinct values
-    DevBuf w_g_hit, w_g_total, w_g_alive, w_g_state, w_g_cand, w_g_coff, w_g_count, w_g_list; // gather (rk_gather.hip): probe scratch, hit counts, alive bytes, round state, candidates, their offsets, counts and hit lists
+    DevBuf w_sc_src, w_sc_ab;                            // abundances: where every distinct value stood among the kept ones, the run lengths
+    DevBuf w_g_hit, w_g_total, w_g_alive, w_g_state, w_g_cand, w_g_coff, w_g_count, w_g_list, w_g_ab; // gather (rk_gather.hip): probe scratch, hit counts, alive bytes, round state, candidates, their offsets, counts and hit lists
     int ref_count_mode = 0; // -I counter fill: 0 per k-mer occurrence (stream), 1 once per distinct hash per reference (filter)
     Slot slot[2];
 };
@@ -163,7 +164,8 @@ inline int set_dev(rk_ctx* c) { HIPCHK(hipSetDevice(c->device)); return RK_OK; }
 
 // ---- the general path (rk_general.hip): hash tiles -> (optional) in-LDS sort / sketch / intersect, for sequences of any length
 // scaled sketches of a batch, grown chunk by chunk (rk_scaled.hip): values is malloc'd, offsets[n + 1] the caller's
-struct ScaledSink { uint64_t max_hash = 0; uint64_t* values = nullptr; size_t len = 0, cap = 0; uint64_t* offsets = nullptr; };
+// with_abund: abund (malloc'd, parallel to values) takes the number of windows behind every value
+struct ScaledSink { uint64_t max_hash = 0; uint64_t* values = nullptr; size_t len = 0, cap = 0; uint64_t* offsets = nullptr; bool with_abund = false; uint32_t* abund = nullptr; };
 struct GeneralOut {
     uint64_t* hashes = nullptr;      // host, [total hashes of the batch] (caller sized via hash_offsets)
     uint64_t* sketches = nullptr;    // host [n*S]

@@ -2,7 +2,7 @@
 // Round after round the reference that shares most with what is left of Q is written out and its values leave Q.  The state stays on
 // the device across rounds: one byte per query value (alive), and per candidate reference the list of the query indices it holds.
 // The host-only form of the same loop is rk_gather_scaled_host (rk_scaled_host.cpp); semantics, bounds and measurements: DESIGN.md
-// section 12.
+// section 12.  With the query's abundances every row also gets the weight it explains (k_gather_remove_w; section 13).
 #include "rk_api_internal.hpp"
 
 namespace {
@@ -155,16 +155,43 @@ __global__ __launch_bounds__(GATHER_T) void k_gather_remove(const GatherState* _
     }
 }
 
+// k_gather_remove when the call carries abundances (include/rkmh_amd.h, "ABUNDANCE"): the same grid over the same list; a lane also
+// reads the abundance of every value it takes out of the query, the wave adds its lanes' sums with shuffles, and its first lane adds
+// the result to wunique[t - 1], the row k_gather_pick has just written.  Integer sums: the order of the additions cannot change them.
+// Indices within one hit list are distinct (the rows ascend), so no two lanes see the same byte alive.
+__global__ __launch_bounds__(GATHER_T) void k_gather_remove_w(const GatherState* __restrict__ state, int32_t max_rounds, uint8_t* __restrict__ alive,
+                                                              const uint32_t* __restrict__ q_abund, uint32_t nq, const uint64_t* __restrict__ coff,
+                                                              uint32_t ncand, uint64_t nlist, const uint32_t* __restrict__ list,
+                                                              unsigned long long* __restrict__ wunique) {
+    const int32_t c = state->pick; // (uniform over the grid: whole workgroups leave)
+    if (c < 0 || (uint32_t)c >= ncand) return;
+    const int32_t row = state->t - 1;
+    const uint64_t end = min(coff[c + 1], nlist), begin = min(coff[c], end);
+    const uint64_t step = (uint64_t)gridDim.x * GATHER_T;
+    unsigned long long sum = 0;
+    for (uint64_t i = begin + (uint64_t)blockIdx.x * GATHER_T + threadIdx.x; i < end; i += step) {
+        const uint32_t h = list[i];
+        if (h < nq) {
+            if (alive[h]) sum += q_abund[h];
+            alive[h] = 0;
+        }
+    }
+    for (int d = 32; d > 0; d >>= 1) sum += __shfl_xor(sum, d, 64);
+    if ((threadIdx.x & 63) == 0 && sum != 0 && row >= 0 && row < max_rounds) atomicAdd(wunique + row, sum);
+}
+
 uint32_t wave_grid(uint64_t nwaves_wanted) { // workgroups of GATHER_WAVES waves for that many waves; the kernels stride beyond 2^16 of them
     return (uint32_t)std::min<uint64_t>(std::max<uint64_t>((nwaves_wanted + GATHER_WAVES - 1) / GATHER_WAVES, 1), 1u << 16);
 }
 
 // The loop on resident arrays, on stream st, with the context's work buffers (the caller holds general_mu).  d_out4 takes at most
-// max_rounds rows.  Synchronises st.
-int gather_run(rk_ctx* c, const uint64_t* d_q, uint64_t nq, const uint64_t* d_rv, const uint64_t* d_ro, int nref, uint64_t r_nvalues,
-               int min_shared, int max_rounds, int32_t* d_out4, int* nrounds, hipStream_t st) {
+// max_rounds rows.  d_wunique != nullptr: a weighted call (d_q_abund: one uint32 per query value), d_wunique takes one uint64 per row and is zeroed as far as rows can be
+// written.  Synchronises st.
+int gather_run(rk_ctx* c, const uint64_t* d_q, const uint32_t* d_q_abund, uint64_t nq, const uint64_t* d_rv, const uint64_t* d_ro, int nref,
+               uint64_t r_nvalues, int min_shared, int max_rounds, int32_t* d_out4, uint64_t* d_wunique, int* nrounds, hipStream_t st) {
     *nrounds = 0;
     const uint32_t nq32 = (uint32_t)nq;
+    if (d_wunique) HIPCHK(hipMemsetAsync(d_wunique, 0, (size_t)std::min(max_rounds, nref) * 8, st));
     // 1. probe: hit[] parallel to the reference values, total[r]
     RKCHK(c->w_g_hit.reserve((size_t)r_nvalues * 4 + 4));
     RKCHK(c->w_g_total.reserve((size_t)nref * 4));
@@ -222,7 +249,11 @@ int gather_run(rk_ctx* c, const uint64_t* d_q, uint64_t nq, const uint64_t* d_rv
         for (int i = 0; i < group; ++i) {
             hipLaunchKernelGGL(k_gather_count, count_grid, dim3(GATHER_T), 0, st, d_state, rounds, d_alive, nq32, d_coff, ncand, nlist, d_list, d_count);
             hipLaunchKernelGGL(k_gather_pick, dim3(1), dim3(PICK_T), 0, st, d_state, rounds, min_shared, d_count, d_cand, ncand, d_total, (uint32_t)nref, d_out4);
-            hipLaunchKernelGGL(k_gather_remove, remove_grid, dim3(GATHER_T), 0, st, d_state, d_alive, nq32, d_coff, ncand, nlist, d_list);
+            if (d_wunique)
+                hipLaunchKernelGGL(k_gather_remove_w, remove_grid, dim3(GATHER_T), 0, st, d_state, rounds, d_alive, d_q_abund, nq32, d_coff, ncand, nlist, d_list,
+                                   (unsigned long long*)d_wunique);
+            else
+                hipLaunchKernelGGL(k_gather_remove, remove_grid, dim3(GATHER_T), 0, st, d_state, d_alive, nq32, d_coff, ncand, nlist, d_list);
         }
         HIPCHK(hipGetLastError());
         launched += group;
@@ -243,24 +274,27 @@ int check_gather_shape(uint64_t nq, int nref, int min_shared, int max_rounds) {
     return RK_OK;
 }
 
-} // namespace
-
-extern "C" int rk_gather_scaled_device(rk_ctx* c, const void* d_q_values, uint64_t nq, const void* d_r_values, const void* d_r_offsets, int nref,
-                                       uint64_t r_nvalues, int min_shared, int max_rounds, void* d_out4, int* nrounds, void* hip_stream) {
+// the entry on resident arrays; d_wunique: nullptr for the plain call
+int gather_resident(rk_ctx* c, const void* d_q_values, const void* d_q_abund, uint64_t nq, const void* d_r_values, const void* d_r_offsets, int nref,
+                    uint64_t r_nvalues, int min_shared, int max_rounds, void* d_out4, void* d_wunique, int* nrounds, void* hip_stream) {
     if (!c || !d_r_offsets || !d_out4 || !nrounds || (!d_q_values && nq) || (!d_r_values && r_nvalues)) return fail(RK_ERR_ARG, "bad arguments");
     RKCHK(check_gather_shape(nq, nref, min_shared, max_rounds));
     RKCHK(set_dev(c));
     std::lock_guard<std::mutex> lk(c->general_mu);
-    return gather_run(c, (const uint64_t*)d_q_values, nq, (const uint64_t*)d_r_values, (const uint64_t*)d_r_offsets, nref, r_nvalues, min_shared, max_rounds,
-                      (int32_t*)d_out4, nrounds, (hipStream_t)hip_stream);
+    return gather_run(c, (const uint64_t*)d_q_values, (const uint32_t*)d_q_abund, nq, (const uint64_t*)d_r_values, (const uint64_t*)d_r_offsets, nref, r_nvalues,
+                      min_shared, max_rounds, (int32_t*)d_out4, (uint64_t*)d_wunique, nrounds, (hipStream_t)hip_stream);
 }
 
-extern "C" int rk_gather_scaled(rk_ctx* c, const uint64_t* q_values, uint64_t nq, const uint64_t* r_values, const uint64_t* r_offsets, int nref,
-                                int min_shared, int max_rounds, int32_t* out4, int* nrounds) {
+// the entry on host arrays; wunique: nullptr for the plain call
+int gather_uploaded(rk_ctx* c, const uint64_t* q_values, const uint32_t* q_abund, uint64_t nq, const uint64_t* r_values, const uint64_t* r_offsets, int nref,
+                    int min_shared, int max_rounds, int32_t* out4, uint64_t* wunique, int* nrounds) {
     if (!c || !r_offsets || !out4 || !nrounds || (!q_values && nq)) return fail(RK_ERR_ARG, "bad arguments");
     RKCHK(check_gather_shape(nq, nref, min_shared, max_rounds));
     for (uint64_t i = 0; i < nq; ++i)
         if (q_values[i] == 0 || (i && q_values[i] <= q_values[i - 1])) return fail(RK_ERR_ARG, "gather: the query is not ascending, distinct and non-zero at value %llu", (unsigned long long)i);
+    if (wunique)
+        for (uint64_t i = 0; i < nq; ++i)
+            if (q_abund[i] == 0) return fail(RK_ERR_ARG, "gather: abundance 0 at query value %llu", (unsigned long long)i);
     for (int i = 0; i < nref; ++i) {
         if (r_offsets[i + 1] < r_offsets[i]) return fail(RK_ERR_ARG, "gather: offsets of the references decrease at sketch %d", i);
         if (r_offsets[i + 1] - r_offsets[i] > 0x7fffffffull) return fail(RK_ERR_LIMIT, "gather: reference sketch %d holds 2^31 values or more", i);
@@ -276,13 +310,46 @@ extern "C" int rk_gather_scaled(rk_ctx* c, const uint64_t* q_values, uint64_t nq
     uint64_t* d_q = c->w_sk.as<uint64_t>();
     uint64_t* d_rv = d_q + nq;
     uint64_t* d_ro = c->w_sc_off.as<uint64_t>();
+    uint64_t* d_wu = nullptr;  // the weighted call: wunique[rows], then the query's abundances
+    uint32_t* d_qa = nullptr;
+    if (wunique) {
+        RKCHK(c->w_g_ab.reserve((size_t)rows * 8 + (size_t)nq * 4 + 4));
+        d_wu = c->w_g_ab.as<uint64_t>();
+        d_qa = (uint32_t*)(d_wu + rows);
+        if (nq) HIPCHK(hipMemcpyAsync(d_qa, q_abund, (size_t)nq * 4, hipMemcpyHostToDevice, c->st));
+    }
     std::vector<uint64_t> off((size_t)nref + 1);
     for (int i = 0; i <= nref; ++i) off[(size_t)i] = r_offsets[i] - r0;
     if (nq) HIPCHK(hipMemcpyAsync(d_q, q_values, (size_t)nq * 8, hipMemcpyHostToDevice, c->st));
     if (rn) HIPCHK(hipMemcpyAsync(d_rv, r_values + r0, (size_t)rn * 8, hipMemcpyHostToDevice, c->st));
     HIPCHK(hipMemcpyAsync(d_ro, off.data(), ((size_t)nref + 1) * 8, hipMemcpyHostToDevice, c->st));
-    RKCHK(gather_run(c, d_q, nq, d_rv, d_ro, nref, rn, min_shared, rows, c->w_out.as<int32_t>(), nrounds, c->st)); // (synchronises: off lives until there)
+    RKCHK(gather_run(c, d_q, d_qa, nq, d_rv, d_ro, nref, rn, min_shared, rows, c->w_out.as<int32_t>(), d_wu, nrounds, c->st)); // (synchronises: off lives until there)
     if (*nrounds) HIPCHK(hipMemcpyAsync(out4, c->w_out.p, (size_t)*nrounds * 16, hipMemcpyDeviceToHost, c->st));
+    if (wunique) HIPCHK(hipMemcpyAsync(wunique, d_wu, (size_t)rows * 8, hipMemcpyDeviceToHost, c->st));
     HIPCHK(hipStreamSynchronize(c->st));
     return RK_OK;
+}
+
+} // namespace
+
+extern "C" int rk_gather_scaled_device(rk_ctx* c, const void* d_q_values, uint64_t nq, const void* d_r_values, const void* d_r_offsets, int nref,
+                                       uint64_t r_nvalues, int min_shared, int max_rounds, void* d_out4, int* nrounds, void* hip_stream) {
+    return gather_resident(c, d_q_values, nullptr, nq, d_r_values, d_r_offsets, nref, r_nvalues, min_shared, max_rounds, d_out4, nullptr, nrounds, hip_stream);
+}
+extern "C" int rk_gather_scaled_abund_device(rk_ctx* c, const void* d_q_values, const void* d_q_abund, uint64_t nq, const void* d_r_values,
+                                             const void* d_r_offsets, int nref, uint64_t r_nvalues, int min_shared, int max_rounds, void* d_out4,
+                                             void* d_wunique, int* nrounds, void* hip_stream) {
+    if (!d_wunique || (!d_q_abund && nq)) return fail(RK_ERR_ARG, "bad arguments");
+    return gather_resident(c, d_q_values, d_q_abund, nq, d_r_values, d_r_offsets, nref, r_nvalues, min_shared, max_rounds, d_out4, d_wunique,
+                           nrounds, hip_stream);
+}
+
+extern "C" int rk_gather_scaled(rk_ctx* c, const uint64_t* q_values, uint64_t nq, const uint64_t* r_values, const uint64_t* r_offsets, int nref,
+                                int min_shared, int max_rounds, int32_t* out4, int* nrounds) {
+    return gather_uploaded(c, q_values, nullptr, nq, r_values, r_offsets, nref, min_shared, max_rounds, out4, nullptr, nrounds);
+}
+extern "C" int rk_gather_scaled_abund(rk_ctx* c, const uint64_t* q_values, const uint32_t* q_abund, uint64_t nq, const uint64_t* r_values,
+                                      const uint64_t* r_offsets, int nref, int min_shared, int max_rounds, int32_t* out4, uint64_t* wunique, int* nrounds) {
+    if (!wunique || (!q_abund && nq)) return fail(RK_ERR_ARG, "bad arguments");
+    return gather_uploaded(c, q_values, q_abund, nq, r_values, r_offsets, nref, min_shared, max_rounds, out4, wunique, nrounds);
 }

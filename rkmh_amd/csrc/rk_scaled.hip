@@ -1,7 +1,7 @@
 // rk_scaled.hip -- scaled (FracMinHash) sketches (include/rkmh_amd.h, "SCALED SKETCHES"): the step of the general path that turns a
 // chunk's window hashes into one variable-length set per sequence (keep / sort / drop repeats), and k_scaled_pairs, which intersects
 // every pair of such sets.  The host-only half (threshold, union, distance) is rk_scaled_host.cpp; semantics, routes, the lane rule
-// and measurements: DESIGN.md section 11.
+// and measurements: DESIGN.md section 11; the abundances (the run lengths of the drop-repeats step): section 13.
 #include "rk_api_internal.hpp"
 
 namespace {
@@ -82,9 +82,11 @@ __global__ __launch_bounds__(KEEP_T) void k_keep_bounds(const uint64_t* __restri
     if ((threadIdx.x & 63) == 0) out_off[s] = pre[blk] + cnt;
 }
 
-template <int MODE>
-__global__ __launch_bounds__(KEEP_T) void k_keep_scatter(const uint64_t* __restrict__ v, uint64_t n, uint64_t max_hash, const uint64_t* __restrict__ off,
-                                                         uint32_t nseg, const uint64_t* __restrict__ pre, uint64_t* __restrict__ out, uint64_t out_cap) {
+// the scatter of one workgroup; SRC: the index t of every kept element also goes to src[], parallel to out[]
+template <int MODE, bool SRC>
+__device__ __forceinline__ void keep_scatter_block(const uint64_t* __restrict__ v, uint64_t n, uint64_t max_hash, const uint64_t* __restrict__ off,
+                                                   uint32_t nseg, const uint64_t* __restrict__ pre, uint64_t* __restrict__ out, uint64_t* __restrict__ src,
+                                                   uint64_t out_cap) {
     __shared__ uint32_t wcnt[KEEP_ROUNDS * (KEEP_T / 64)]; // kept by (round, wave), in element order
     const uint64_t base = (uint64_t)blockIdx.x * KEEP_BLK;
     const uint32_t wave = threadIdx.x >> 6;
@@ -106,10 +108,37 @@ __global__ __launch_bounds__(KEEP_T) void k_keep_scatter(const uint64_t* __restr
         for (uint32_t w = 0; w < KEEP_T / 64; ++w) {
             if (w == wave && keep[r]) {
                 const uint64_t at = first + before + rank[r];
-                if (at < out_cap) out[at] = x[r]; // (always: out holds pre[nblocks] values)
+                if (at < out_cap) { // (always: out holds pre[nblocks] values)
+                    out[at] = x[r];
+                    if (SRC) src[at] = base + (uint64_t)(r * KEEP_T) + threadIdx.x;
+                }
             }
             before += wcnt[r * (KEEP_T / 64) + w];
         }
+}
+template <int MODE>
+__global__ __launch_bounds__(KEEP_T) void k_keep_scatter(const uint64_t* __restrict__ v, uint64_t n, uint64_t max_hash, const uint64_t* __restrict__ off,
+                                                         uint32_t nseg, const uint64_t* __restrict__ pre, uint64_t* __restrict__ out, uint64_t out_cap) {
+    keep_scatter_block<MODE, false>(v, n, max_hash, off, nseg, pre, out, nullptr, out_cap);
+}
+
+// ---- abundances (include/rkmh_amd.h, "ABUNDANCE"): the length of every run that KEEP_FIRST collapses.  Every element of the sorted
+// array is the first of its value in its segment or a repeat of the element before it, so run j ends where run j + 1 begins, and the
+// last one at n.  k_keep_first_src is KEEP_FIRST's scatter that also notes where each first stood; k_run_lengths subtracts neighbours.
+__global__ __launch_bounds__(KEEP_T) void k_keep_first_src(const uint64_t* __restrict__ v, uint64_t n, const uint64_t* __restrict__ off, uint32_t nseg,
+                                                           const uint64_t* __restrict__ pre, uint64_t* __restrict__ out, uint64_t* __restrict__ src,
+                                                           uint64_t out_cap) {
+    keep_scatter_block<KEEP_FIRST, true>(v, n, 0, off, nseg, pre, out, src, out_cap);
+}
+// abund[j] = (j + 1 < m ? src[j + 1] : n) - src[j] for j < m, m = *kept (the scan's total: the number of firsts) clamped to cap, the
+// length of src[] and abund[]; a run longer than 2^32 - 1 is stored as 2^32 - 1.  One thread per run.
+__global__ __launch_bounds__(KEEP_T) void k_run_lengths(const uint64_t* __restrict__ src, const uint64_t* __restrict__ kept, uint64_t n, uint64_t cap,
+                                                        uint32_t* __restrict__ abund) {
+    const uint64_t m = min(*kept, cap);
+    const uint64_t j = (uint64_t)blockIdx.x * KEEP_T + threadIdx.x;
+    if (j >= m) return;
+    const uint64_t begin = src[j], end = j + 1 < m ? src[j + 1] : n;
+    abund[j] = (uint32_t)min(end > begin ? end - begin : (uint64_t)0, (uint64_t)0xffffffffu);
 }
 
 template <int MODE>
@@ -134,12 +163,30 @@ int keep_scatter(rk_ctx* c, const uint64_t* v, uint64_t n, uint64_t max_hash, co
     return RK_OK;
 }
 
+// KEEP_FIRST's scatter with the abundances: d_src and d_abund hold n entries each, as out does; the number of firsts is read on the device
+int keep_first_abund(rk_ctx* c, const uint64_t* v, uint64_t n, const uint64_t* d_off, uint32_t nseg, uint64_t* out, uint64_t* d_src, uint32_t* d_abund) {
+    const uint64_t nblocks = (n + KEEP_BLK - 1) / KEEP_BLK;
+    if (!nblocks) return RK_OK;
+    if ((n + KEEP_T - 1) / KEEP_T > 0x7fffffffull) return fail(RK_ERR_LIMIT, "%llu kept values are more than one run-length launch takes", (unsigned long long)n);
+    const uint64_t* d_pre = c->w_sc_pre.as<uint64_t>();
+    hipLaunchKernelGGL(k_keep_first_src, dim3((uint32_t)nblocks), dim3(KEEP_T), 0, c->st, v, n, d_off, nseg, d_pre, out, d_src, n);
+    hipLaunchKernelGGL(k_run_lengths, dim3((uint32_t)((n + KEEP_T - 1) / KEEP_T)), dim3(KEEP_T), 0, c->st, d_src, d_pre + nblocks, n, n, d_abund);
+    HIPCHK(hipGetLastError());
+    return RK_OK;
+}
+
 int grow_sink(ScaledSink& sink, size_t more) {
     if (sink.len + more <= sink.cap) return RK_OK;
     size_t cap = std::max(sink.len + more, sink.cap + sink.cap / 2) + 16;
     uint64_t* p = (uint64_t*)realloc(sink.values, cap * 8);
     if (!p) return fail(RK_ERR_NOMEM, "realloc of %zu scaled values", cap);
-    sink.values = p; sink.cap = cap;
+    sink.values = p;
+    if (sink.with_abund) {
+        uint32_t* a = (uint32_t*)realloc(sink.abund, cap * 4);
+        if (!a) return fail(RK_ERR_NOMEM, "realloc of %zu abundances", cap);
+        sink.abund = a;
+    }
+    sink.cap = cap;
     return RK_OK;
 }
 
@@ -209,7 +256,14 @@ int scaled_keep_chunk(rk_ctx* c, const std::vector<uint64_t>& seg, uint64_t nhas
     }
     // 3. drop repeats: the first of every value in its segment stays
     RKCHK(keep_counts<KEEP_FIRST>(c, d_a, total1, 0, d_koff1, nseg, d_koff2));
-    RKCHK(keep_scatter<KEEP_FIRST>(c, d_a, total1, 0, d_koff1, nseg, d_b, total1));
+    uint32_t* d_abund = nullptr;
+    if (sink.with_abund) { // the run lengths leave with the values
+        RKCHK(c->w_sc_src.reserve((size_t)total1 * 8));
+        RKCHK(c->w_sc_ab.reserve((size_t)total1 * 4));
+        d_abund = c->w_sc_ab.as<uint32_t>();
+        RKCHK(keep_first_abund(c, d_a, total1, d_koff1, nseg, d_b, c->w_sc_src.as<uint64_t>(), d_abund));
+    } else
+        RKCHK(keep_scatter<KEEP_FIRST>(c, d_a, total1, 0, d_koff1, nseg, d_b, total1));
     std::vector<uint64_t> koff2(cn + 1);
     HIPCHK(hipMemcpyAsync(koff2.data(), d_koff2, (cn + 1) * 8, hipMemcpyDeviceToHost, c->st));
     HIPCHK(hipStreamSynchronize(c->st)); // (the id vectors of step 2 live until here)
@@ -217,27 +271,39 @@ int scaled_keep_chunk(rk_ctx* c, const std::vector<uint64_t>& seg, uint64_t nhas
     if (total2 > total1) return fail(RK_ERR_HIP, "scaled keep: %llu distinct values of %llu", (unsigned long long)total2, (unsigned long long)total1);
     RKCHK(grow_sink(sink, (size_t)total2));
     if (total2) HIPCHK(hipMemcpyAsync(sink.values + sink.len, d_b, (size_t)total2 * 8, hipMemcpyDeviceToHost, c->st));
+    if (total2 && d_abund) HIPCHK(hipMemcpyAsync(sink.abund + sink.len, d_abund, (size_t)total2 * 4, hipMemcpyDeviceToHost, c->st));
     HIPCHK(hipStreamSynchronize(c->st));
     for (size_t q = 0; q < cn; ++q) sink.offsets[i0 + q + 1] = sink.len + koff2[q + 1];
     sink.len += (size_t)total2;
     return RK_OK;
 }
 
-extern "C" int rk_sketch_scaled_batch(rk_ctx* c, const uint8_t* bases, const uint64_t* offsets, int64_t nseq, const int* ks, int nks,
-                                      uint64_t max_hash, uint64_t** values, uint64_t* sk_offsets) {
+static int sketch_scaled(rk_ctx* c, const uint8_t* bases, const uint64_t* offsets, int64_t nseq, const int* ks, int nks, uint64_t max_hash,
+                         uint64_t** values, uint32_t** abunds, uint64_t* sk_offsets) {
     if (!c || !offsets || nseq < 0 || !values || !sk_offsets) return fail(RK_ERR_ARG, "bad arguments");
     GeneralCfg cfg;
     RKCHK(check_ks(ks, nks, &cfg.ks));
     ScaledSink sink;
-    sink.max_hash = max_hash; sink.offsets = sk_offsets;
+    sink.max_hash = max_hash; sink.offsets = sk_offsets; sink.with_abund = abunds != nullptr;
     sink.values = (uint64_t*)malloc(8 * 16); sink.cap = 16;
-    if (!sink.values) return fail(RK_ERR_NOMEM, "malloc");
+    if (sink.with_abund) sink.abund = (uint32_t*)malloc(4 * 16);
+    if (!sink.values || (sink.with_abund && !sink.abund)) { free(sink.values); free(sink.abund); return fail(RK_ERR_NOMEM, "malloc"); }
     sk_offsets[0] = 0;
     GeneralOut go; go.scaled = &sink;
     const int r = general_run(c, bases, nullptr, offsets, nseq, cfg, go);
-    if (r != RK_OK) { free(sink.values); return r; }
+    if (r != RK_OK) { free(sink.values); free(sink.abund); return r; }
     *values = sink.values;
+    if (abunds) *abunds = sink.abund;
     return RK_OK;
+}
+extern "C" int rk_sketch_scaled_batch(rk_ctx* c, const uint8_t* bases, const uint64_t* offsets, int64_t nseq, const int* ks, int nks,
+                                      uint64_t max_hash, uint64_t** values, uint64_t* sk_offsets) {
+    return sketch_scaled(c, bases, offsets, nseq, ks, nks, max_hash, values, nullptr, sk_offsets);
+}
+extern "C" int rk_sketch_scaled_abund_batch(rk_ctx* c, const uint8_t* bases, const uint64_t* offsets, int64_t nseq, const int* ks, int nks,
+                                            uint64_t max_hash, uint64_t** values, uint32_t** abunds, uint64_t* sk_offsets) {
+    if (!abunds) return fail(RK_ERR_ARG, "bad arguments");
+    return sketch_scaled(c, bases, offsets, nseq, ks, nks, max_hash, values, abunds, sk_offsets);
 }
 
 // ---- pairs ---------------------------------------------------------------------------------------------------------------

@@ -9,6 +9,7 @@
 #include <cstring>
 #include <string>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #include "../../include/rkmh_amd.h"
@@ -49,6 +50,37 @@ extern "C" int rk_merge_scaled(const uint64_t* values, const uint64_t* offsets, 
     return RK_OK;
 }
 
+// rk_merge_scaled with abundances (include/rkmh_amd.h, "ABUNDANCE"): the values as rk_merge_scaled gives them, and per value the sum of
+// its abundances over the parts, saturating at 2^32 - 1.  A cut to a smaller max_hash keeps the prefix of both arrays.
+extern "C" int rk_merge_scaled_abund(const uint64_t* values, const uint32_t* abunds, const uint64_t* offsets, int n, uint64_t max_hash,
+                                     uint64_t** out_values, uint32_t** out_abunds, uint64_t* out_len) {
+    if (!out_values || !out_abunds || !out_len || n < 0 || (n > 0 && !offsets)) return bad("rk_merge_scaled_abund: bad arguments");
+    for (int i = 0; i < n; ++i)
+        if (offsets[i + 1] < offsets[i]) return bad("rk_merge_scaled_abund: offsets decrease at sketch " + std::to_string(i));
+    const uint64_t lo = n ? offsets[0] : 0, hi = n ? offsets[n] : 0;
+    if (hi > lo && (!values || !abunds)) return bad("rk_merge_scaled_abund: values or abunds is NULL");
+    std::vector<std::pair<uint64_t, uint32_t>> v;
+    v.reserve((size_t)(hi - lo));
+    for (uint64_t t = lo; t < hi; ++t) {
+        if (abunds[t] == 0) return bad("rk_merge_scaled_abund: abundance 0 at value " + std::to_string(t));
+        if (values[t] != 0 && values[t] <= max_hash) v.emplace_back(values[t], abunds[t]);
+    }
+    std::sort(v.begin(), v.end(), [](const std::pair<uint64_t, uint32_t>& a, const std::pair<uint64_t, uint32_t>& b) { return a.first < b.first; });
+    size_t m = 0; // distinct values so far; sums saturate (an integer sum: the order of the parts cannot change it)
+    for (size_t t = 0; t < v.size(); ++t) {
+        if (m && v[m - 1].first == v[t].first) v[m - 1].second = (uint32_t)std::min<uint64_t>((uint64_t)v[m - 1].second + v[t].second, 0xffffffffull);
+        else v[m++] = v[t];
+    }
+    uint64_t* rv = (uint64_t*)malloc(sizeof(uint64_t) * (m ? m : 1));
+    uint32_t* ra = (uint32_t*)malloc(sizeof(uint32_t) * (m ? m : 1));
+    if (!rv || !ra) { free(rv); free(ra); rk__set_error("rk_merge_scaled_abund: malloc"); return RK_ERR_NOMEM; }
+    for (size_t t = 0; t < m; ++t) { rv[t] = v[t].first; ra[t] = v[t].second; }
+    *out_values = rv;
+    *out_abunds = ra;
+    *out_len = (uint64_t)m;
+    return RK_OK;
+}
+
 // ---- gather on the host (include/rkmh_amd.h, "GATHER"): the loop of rk_gather.hip on host threads -- each reference value looked up in
 // Q once, the hits of every candidate kept as a list of query indices, then per round a recount of every list against one byte per
 // query value, the pick, and the removal.
@@ -70,20 +102,23 @@ void on_threads(size_t n, int nt, size_t min_piece, F f) {
 }
 } // namespace
 
-extern "C" int rk_gather_scaled_host(const uint64_t* q, uint64_t nq, const uint64_t* rv, const uint64_t* roff, int nref, int min_shared,
-                                     int max_rounds, int threads, int32_t* out4, int* nrounds) {
-    if (!roff || !out4 || !nrounds || (!q && nq)) return bad("rk_gather_scaled_host: bad arguments");
-    if (nref < 1) return bad("rk_gather_scaled_host: need at least one reference sketch");
-    if (min_shared < 1 || max_rounds < 1) return bad("rk_gather_scaled_host: min_shared and max_rounds must be at least 1");
-    if (nq > 0x7fffffffull) { rk__set_error("rk_gather_scaled_host: a query of more than 2^31-1 values"); return RK_ERR_LIMIT; }
+// The loop of both host entries.  wunique != nullptr (rk_gather_scaled_abund_host): wunique[t] = the abundances of the query values
+// that row t removes, summed; the rows themselves never depend on it.
+static int gather_host(const std::string& who, const uint64_t* q, const uint32_t* q_abund, uint64_t nq, const uint64_t* rv, const uint64_t* roff, int nref,
+                       int min_shared, int max_rounds, int threads, int32_t* out4, uint64_t* wunique, int* nrounds) {
+    if (!roff || !out4 || !nrounds || (!q && nq)) return bad(who + ": bad arguments");
+    if (nref < 1) return bad(who + ": need at least one reference sketch");
+    if (min_shared < 1 || max_rounds < 1) return bad(who + ": min_shared and max_rounds must be at least 1");
+    if (nq > 0x7fffffffull) { rk__set_error((who + ": a query of more than 2^31-1 values").c_str()); return RK_ERR_LIMIT; }
     for (uint64_t i = 0; i < nq; ++i)
-        if (q[i] == 0 || (i && q[i] <= q[i - 1])) return bad("rk_gather_scaled_host: the query is not ascending, distinct and non-zero at value " + std::to_string(i));
+        if (q[i] == 0 || (i && q[i] <= q[i - 1])) return bad(who + ": the query is not ascending, distinct and non-zero at value " + std::to_string(i));
     for (int i = 0; i < nref; ++i) {
-        if (roff[i + 1] < roff[i]) return bad("rk_gather_scaled_host: offsets of the references decrease at sketch " + std::to_string(i));
-        if (roff[i + 1] - roff[i] > 0x7fffffffull) { rk__set_error("rk_gather_scaled_host: a reference sketch of 2^31 values or more"); return RK_ERR_LIMIT; }
+        if (roff[i + 1] < roff[i]) return bad(who + ": offsets of the references decrease at sketch " + std::to_string(i));
+        if (roff[i + 1] - roff[i] > 0x7fffffffull) { rk__set_error((who + ": a reference sketch of 2^31 values or more").c_str()); return RK_ERR_LIMIT; }
     }
-    if (roff[nref] > roff[0] && !rv) return bad("rk_gather_scaled_host: r_values is NULL");
+    if (roff[nref] > roff[0] && !rv) return bad(who + ": r_values is NULL");
     *nrounds = 0;
+    if (wunique) std::fill(wunique, wunique + std::min(max_rounds, nref), (uint64_t)0); // every row there can be
     // the hits of every reference: a row ascends, so each lookup starts where the one before it ended
     std::vector<std::vector<uint32_t>> hits((size_t)nref);
     on_threads((size_t)nref, threads, 1, [&](size_t lo, size_t hi) {
@@ -115,6 +150,11 @@ extern "C" int rk_gather_scaled_host(const uint64_t* q, uint64_t nq, const uint6
             if (count[c] > count[best]) best = c;
         if (count[best] < min_shared) break;
         const std::vector<uint32_t>& mine = hits[(size_t)cand[best]];
+        if (wunique) {
+            uint64_t w = 0; // at most 2^31 - 1 values of at most 2^32 - 1 each: below 2^63
+            for (uint32_t h : mine) w += alive[h] ? (uint64_t)q_abund[h] : 0;
+            wunique[t] = w;
+        }
         for (uint32_t h : mine) alive[h] = 0;
         remaining -= count[best];
         int32_t* row = out4 + (size_t)t * 4;
@@ -122,6 +162,22 @@ extern "C" int rk_gather_scaled_host(const uint64_t* q, uint64_t nq, const uint6
         *nrounds = t + 1;
     }
     return RK_OK;
+}
+
+extern "C" int rk_gather_scaled_host(const uint64_t* q, uint64_t nq, const uint64_t* rv, const uint64_t* roff, int nref, int min_shared,
+                                     int max_rounds, int threads, int32_t* out4, int* nrounds) {
+    return gather_host("rk_gather_scaled_host", q, nullptr, nq, rv, roff, nref, min_shared, max_rounds, threads, out4, nullptr, nrounds);
+}
+
+// q_abund and wunique are checked here; everything else as rk_gather_scaled_host checks it
+extern "C" int rk_gather_scaled_abund_host(const uint64_t* q, const uint32_t* q_abund, uint64_t nq, const uint64_t* rv, const uint64_t* roff, int nref,
+                                           int min_shared, int max_rounds, int threads, int32_t* out4, uint64_t* wunique, int* nrounds) {
+    const std::string who = "rk_gather_scaled_abund_host";
+    if (!wunique || (!q_abund && nq)) return bad(who + ": bad arguments");
+    if (q && nq <= 0x7fffffffull)
+        for (uint64_t i = 0; i < nq; ++i)
+            if (q_abund[i] == 0) return bad(who + ": abundance 0 at query value " + std::to_string(i));
+    return gather_host(who, q, q_abund, nq, rv, roff, nref, min_shared, max_rounds, threads, out4, wunique, nrounds);
 }
 
 // rk_mash_distance's formula and clamps on j = shared / (la + lb - shared): j = 0 and the distance 1 when the union is empty; the

@@ -71,6 +71,9 @@ struct LoadedSketches {
     // sketch i is sk[off[i], off[i + 1]).  Only `dist` compares such sketches: every other reader refuses them (refuse_scaled).
     uint64_t scaled = 0;
     std::vector<uint64_t> off;
+    // "abundances" (`rkmh sketch --scaled <n> --abund`): every sketch of the file carries them or none does; parallel to sk, each 1 .. 2^32 - 1
+    bool has_abund = false;
+    std::vector<uint32_t> abund;
     std::string err; // why load_sketch_json returned false, where it knows more than "cannot load"
 };
 bool load_sketch_json(const char* path, LoadedSketches& L, int max_S = 0); // max_S > 0: a larger "length" is refused before anything of that size is allocated
@@ -90,10 +93,14 @@ struct OutBuf { // lines on their way to a file: written whenever a row ends wit
 // record -- or, whole_files (-g), one per FILE: its records are sketched one by one (no window spans two contigs) and united
 // (rk_merge_sketches: the bottom S under the policy's dedup rule; rk_merge_scaled), named by the path as given, seqLen their sum.
 struct SketchSet { std::vector<std::string> names; std::vector<uint64_t> seq_len; std::vector<uint64_t> sk; std::vector<int32_t> lens; };
-struct ScaledSet { std::vector<std::string> names; std::vector<uint64_t> seq_len; std::vector<uint64_t> values; std::vector<uint64_t> off = std::vector<uint64_t>(1, 0); };
+// with_abund: abund lies parallel to values (the windows behind every value; -g and the one query of a -f file sum them: rk_merge_scaled_abund)
+struct ScaledSet {
+    std::vector<std::string> names; std::vector<uint64_t> seq_len; std::vector<uint64_t> values; std::vector<uint64_t> off = std::vector<uint64_t>(1, 0);
+    bool with_abund = false; std::vector<uint32_t> abund;
+};
 void sketch_files(rk_ctx* ctx, const std::vector<const char*>& files, const std::vector<int>& ks, int S, bool whole_files, SketchSet& out);
 void sketch_files_scaled(rk_ctx* ctx, const std::vector<const char*>& files, const std::vector<int>& ks, uint64_t max_hash, bool whole_files, ScaledSet& out);
-struct SketchRow { const uint64_t* hashes; uint64_t n, length; }; // a sketch to write; "length": the S of a bottom-s sketch, a scaled one's own size
+struct SketchRow { const uint64_t* hashes; uint64_t n, length; const uint32_t* abund = nullptr; }; // a sketch to write; "length": the S of a bottom-s sketch, a scaled one's own size; abund: its "abundances", or none
 void write_sketch_json(FILE* fo, const std::vector<std::string>& names, const std::vector<uint64_t>& seq_len, const std::string& kstr,
                        const std::vector<SketchRow>& rows, uint64_t scaled, uint64_t max_hash); // scaled = 0: a bottom-s file
 bool parse_scaled(const char* text, uint64_t& scaled); // --scaled: a number of at least 1, nothing else
@@ -105,6 +112,7 @@ struct CompareInputs {
     std::vector<int> ks;
     int S = 0, device = 0; // S: 0 without -s, -1 for a -s below 1
     bool whole_files = false, scaled_given = false, scaled_ok = true;
+    bool abund = false; // gather --abund: the queries carry abundances
     uint64_t scaled = 0;
     bool self() const { return query_files.empty() && query_json.empty(); }
 };

@@ -5,11 +5,13 @@
 
 static void help_sketch() {
     fprintf(stderr,
-            "rkmh sketch -f <seqs.fa|fq> [-k <k>]... [-s <sketch> | --scaled <n>] [-g] [-o <out.json>] [--kmer-cache <file>]\n"
+            "rkmh sketch -f <seqs.fa|fq> [-k <k>]... [-s <sketch> | --scaled <n> [--abund]] [-g] [-o <out.json>] [--kmer-cache <file>]\n"
             "  writes a JSON array with one MinHash sketch per sequence (schema of the reference's dump_hash_json);\n"
             "  -g: one sketch per input FILE (named by its path; no k-mer spans two of its records), as Mash sketches an assembly;\n"
             "  --scaled <n>: scaled (FracMinHash) sketches instead of bottom-s ones: every distinct hash up to (2^64 - 1) / n, so the size\n"
             "  grows with the sequence; objects gain \"scaled\" and \"maxHash\"; such files serve `rkmh dist` only\n"
+            "  --abund (with --scaled): \"sketches\" gains \"abundances\", parallel to \"hashes\": how many windows of the sequence hash to each\n"
+            "  value (with -g: summed over the file's records); `rkmh gather --abund -Q` needs them, every other reader ignores them\n"
             "  `rkmh stream -R <out.json>` loads it instead of sketching references again;\n"
             "  --kmer-cache <file>: also enumerates the k-mers behind these sketches (k 8 .. 18) into <file>, which\n"
             "  `rkmh stream -R <out.json> --kmer-cache <file>` then loads instead of enumerating them at every start\n"
@@ -21,7 +23,7 @@ int main_sketch(int argc, char** argv) {
     int S = 1000, device = 0;
     const char* outp = nullptr;
     const char* kmer_cache = nullptr;
-    bool whole_files = false, s_given = false, scaled_given = false, scaled_ok = true;
+    bool whole_files = false, s_given = false, scaled_given = false, scaled_ok = true, abund = false;
     uint64_t scaled = 0;
     if (argc <= 2) { help_sketch(); exit(1); }
     optind = 2;
@@ -29,9 +31,10 @@ int main_sketch(int argc, char** argv) {
     static struct option long_options[] = {{"help", no_argument, 0, 'h'}, {"kmer", required_argument, 0, 'k'},
         {"fasta", required_argument, 0, 'f'}, {"reference", required_argument, 0, 'r'}, {"sketch-size", required_argument, 0, 's'},
         {"output", required_argument, 0, 'o'}, {"device", required_argument, 0, 1000}, {"kmer-cache", required_argument, 0, 1003},
-        {"whole-files", no_argument, 0, 'g'}, {"scaled", required_argument, 0, 1005}, HASH_POLICY_OPTION, {0, 0, 0, 0}};
+        {"whole-files", no_argument, 0, 'g'}, {"scaled", required_argument, 0, 1005}, {"abund", no_argument, 0, 1008}, HASH_POLICY_OPTION, {0, 0, 0, 0}};
     while ((c = getopt_long(argc, argv, "hgk:f:r:s:o:t:", long_options, nullptr)) != -1) {
         switch (c) {
+            case 1008: abund = true; break;
             case 1004: policy_apply(optarg, "--hash-policy"); break;
             case 1005: scaled_given = true; scaled_ok = parse_scaled(optarg, scaled); break;
             case 1003: kmer_cache = optarg; break;
@@ -52,6 +55,7 @@ int main_sketch(int argc, char** argv) {
         if (s_given) { fprintf(stderr, "rkmh sketch: --scaled and -s are two kinds of sketch; give one of them\n"); exit(1); }
         if (kmer_cache) { fprintf(stderr, "rkmh sketch: --kmer-cache serves `stream -R`; scaled sketches serve `rkmh dist` only\n"); exit(1); }
     }
+    if (abund && !scaled_given) { fprintf(stderr, "rkmh sketch: --abund goes with --scaled <n>; bottom-s sketches keep no abundances\n"); exit(1); }
     if (!scaled_given && whole_files && (S < 1 || S > RK_MAX_SKETCH)) { fprintf(stderr, "rkmh sketch: -g needs a sketch size of 1 .. %d\n", RK_MAX_SKETCH); exit(1); }
     rk_ctx* ctx = nullptr;
     CK(rk_ctx_create(device, &g_policy, &ctx));
@@ -61,8 +65,12 @@ int main_sketch(int argc, char** argv) {
     uint64_t max_hash = 0;
     if (scaled_given) {
         CK(rk_scaled_max_hash(scaled, &max_hash));
+        sc.with_abund = abund;
         sketch_files_scaled(ctx, files, ks, max_hash, whole_files, sc);
-        for (size_t i = 0; i < sc.names.size(); ++i) rows.push_back({sc.values.data() + sc.off[i], sc.off[i + 1] - sc.off[i], sc.off[i + 1] - sc.off[i]});
+        static const uint32_t no_values = 0; // (an empty sketch still says "abundances":[])
+        const uint32_t* ab = !abund ? nullptr : sc.abund.empty() ? &no_values : sc.abund.data();
+        for (size_t i = 0; i < sc.names.size(); ++i)
+            rows.push_back({sc.values.data() + sc.off[i], sc.off[i + 1] - sc.off[i], sc.off[i + 1] - sc.off[i], ab ? ab + sc.off[i] : nullptr});
     } else {
         sketch_files(ctx, files, ks, S, whole_files, set);
         if (kmer_cache && *kmer_cache) {
@@ -199,7 +207,7 @@ int main_dist(int argc, char** argv) {
 static void help_gather() {
     fprintf(stderr,
             "rkmh gather (-r <refs.fa> ... | -R <refs.json> ...) (-f <sample.fa|fq[.gz]> ... | -Q <queries.json> ...) [-k <k>] [--scaled <n>] [-g]\n"
-            "            [--min-shared <n>] [--max-rounds <n>] [--device <id>]\n"
+            "            [--min-shared <n>] [--max-rounds <n>] [--abund] [--device <id>]\n"
             "  decomposes every query into references, greedily: the reference that holds most of what is left of the query is printed and\n"
             "  its hashes leave the query, until the best reference holds fewer than --min-shared (default 1) of them or --max-rounds lines\n"
             "  are printed; one line per pick, query by query: query, rank (from 1), reference, unique/|query| (hashes only this pick\n"
@@ -208,7 +216,11 @@ static void help_gather() {
             "  -f: every file is ONE query, the union of its records (a sample is a file of reads);  -Q: every sketch of the file is a query\n"
             "  -r: one reference per record, with -g one per FILE;  -R / -Q: scaled sketches written by `rkmh sketch --scaled <m>`\n"
             "  --scaled <n>: -r / -f files are sketched at n, -R / -Q files (m <= n) are cut down to n; without it: the largest m among the\n"
-            "  files; not with -s (bottom-s sketches cannot be decomposed)\n" HASH_POLICY_HELP);
+            "  files; not with -s (bottom-s sketches cannot be decomposed)\n"
+            "  --abund: the query keeps how many of its windows hash to each value (-f files are sketched so, summed over a file's records;\n"
+            "  -Q files must come from `rkmh sketch --scaled <m> --abund`); the picks are the same, every line gains two columns:\n"
+            "  wunique/wtotal (the windows behind the hashes only this pick explains at its turn / all windows the query kept) and the mean\n"
+            "  abundance of those hashes, wunique / unique; abundances in -R files are ignored\n" HASH_POLICY_HELP);
 }
 static const CompareRules gather_rules = {"gather", "gather", "gather decomposes scaled ones (rkmh sketch --scaled)", true, nullptr};
 int main_gather(int argc, char** argv) {
@@ -216,7 +228,7 @@ int main_gather(int argc, char** argv) {
     int min_shared = 1, max_rounds = 0x7fffffff;
     bool min_ok = true, rounds_ok = true;
     if (argc <= 2) { help_gather(); exit(1); }
-    static struct option long_options[] = {COMPARE_OPTIONS, {"min-shared", required_argument, 0, 1006}, {"max-rounds", required_argument, 0, 1007}, {0, 0, 0, 0}};
+    static struct option long_options[] = {COMPARE_OPTIONS, {"min-shared", required_argument, 0, 1006}, {"max-rounds", required_argument, 0, 1007}, {"abund", no_argument, 0, 1008}, {0, 0, 0, 0}};
     optind = 2;
     int c;
     while ((c = getopt_long(argc, argv, "hgk:f:r:R:Q:s:", long_options, nullptr)) != -1) {
@@ -224,6 +236,7 @@ int main_gather(int argc, char** argv) {
         switch (c) {
             case 1006: min_ok = parse_at_least_1(optarg, min_shared); break;
             case 1007: rounds_ok = parse_at_least_1(optarg, max_rounds); break;
+            case 1008: in.abund = true; break;
             default: help_gather(); exit(1);
         }
     }
@@ -250,11 +263,16 @@ int main_gather(int argc, char** argv) {
     for (size_t i = 0; i < nq; ++i) longest = std::max(longest, sq.off[i + 1] - sq.off[i]);
     if (longest > 0x7fffffffull) refuse(gather_rules, "a query of more than 2^31-1 hashes");
     const int rows = (int)std::min<size_t>((size_t)max_rounds, nr);
-    void *d_rv = nullptr, *d_ro = nullptr, *d_q = nullptr, *d_out = nullptr;
+    void *d_rv = nullptr, *d_ro = nullptr, *d_q = nullptr, *d_out = nullptr, *d_qa = nullptr, *d_wu = nullptr;
     CK(rk_device_alloc(ctx, sr.values.size() * 8, &d_rv));
     CK(rk_device_alloc(ctx, sr.off.size() * 8, &d_ro));
     CK(rk_device_alloc(ctx, (size_t)longest * 8, &d_q));
     CK(rk_device_alloc(ctx, (size_t)rows * 16, &d_out));
+    if (in.abund) {
+        CK(rk_device_alloc(ctx, (size_t)longest * 4, &d_qa));
+        CK(rk_device_alloc(ctx, (size_t)rows * 8, &d_wu));
+    }
+    std::vector<uint64_t> wunique((size_t)(in.abund ? rows : 0));
     CK(rk_device_upload(ctx, d_rv, sr.values.data(), sr.values.size() * 8));
     CK(rk_device_upload(ctx, d_ro, sr.off.data(), sr.off.size() * 8));
     std::vector<int32_t> out4((size_t)rows * 4);
@@ -263,7 +281,15 @@ int main_gather(int argc, char** argv) {
         const uint64_t lq = sq.off[i + 1] - sq.off[i];
         int n = 0;
         CK(rk_device_upload(ctx, d_q, sq.values.data() + sq.off[i], (size_t)lq * 8));
-        CK(rk_gather_scaled_device(ctx, d_q, lq, d_rv, d_ro, (int)nr, sr.values.size(), min_shared, rows, d_out, &n, rk_ctx_stream(ctx)));
+        uint64_t wtotal = 0;
+        if (in.abund) {
+            const uint32_t* qa = sq.abund.data() + sq.off[i];
+            for (uint64_t j = 0; j < lq; ++j) wtotal += qa[j];
+            CK(rk_device_upload(ctx, d_qa, qa, (size_t)lq * 4));
+            CK(rk_gather_scaled_abund_device(ctx, d_q, d_qa, lq, d_rv, d_ro, (int)nr, sr.values.size(), min_shared, rows, d_out, d_wu, &n, rk_ctx_stream(ctx)));
+            CK(rk_device_download(ctx, wunique.data(), d_wu, (size_t)n * 8));
+        } else
+            CK(rk_gather_scaled_device(ctx, d_q, lq, d_rv, d_ro, (int)nr, sr.values.size(), min_shared, rows, d_out, &n, rk_ctx_stream(ctx)));
         CK(rk_device_download(ctx, out4.data(), d_out, (size_t)n * 16));
         for (int t = 0; t < n; ++t) {
             const int32_t* r = &out4[(size_t)t * 4];
@@ -272,13 +298,15 @@ int main_gather(int argc, char** argv) {
             o.append(sq.names[i]);
             o.appendf("\t%d\t", t + 1);
             o.append(sr.names[ref]);
-            o.appendf("\t%d/%llu\t%d/%llu\t%d/%llu\t%d\n", r[1], (unsigned long long)lq, r[2], (unsigned long long)lq, r[2], (unsigned long long)(sr.off[ref + 1] - sr.off[ref]), r[3]);
+            o.appendf("\t%d/%llu\t%d/%llu\t%d/%llu\t%d", r[1], (unsigned long long)lq, r[2], (unsigned long long)lq, r[2], (unsigned long long)(sr.off[ref + 1] - sr.off[ref]), r[3]);
+            if (in.abund) o.appendf("\t%llu/%llu\t%.6g", (unsigned long long)wunique[(size_t)t], (unsigned long long)wtotal, (double)wunique[(size_t)t] / (double)r[1]);
+            o.append("\n");
         }
         o.end_row();
     }
     o.flush();
     fflush(stdout);
-    for (void* p : {d_rv, d_ro, d_q, d_out}) rk_device_free(ctx, p);
+    for (void* p : {d_rv, d_ro, d_q, d_out, d_qa, d_wu}) if (p) rk_device_free(ctx, p);
     rk_ctx_destroy(ctx);
     return 0;
 }

@@ -36,6 +36,7 @@ bool load_sketch_json(const char* path, LoadedSketches& L, int max_S) {
     // objects are delimited by their "sketches":{...}} tail; walk by the "alphabet" key that opens each object
     size_t pos = 0;
     std::vector<std::vector<uint64_t>> all;
+    std::vector<std::vector<uint32_t>> all_abund;
     while ((pos = t.find("\"alphabet\"", pos)) != std::string::npos) {
         size_t next = t.find("\"alphabet\"", pos + 10);
         size_t end = next == std::string::npos ? t.size() : next;
@@ -89,6 +90,28 @@ bool load_sketch_json(const char* path, LoadedSketches& L, int max_S) {
                     L.err = "sketch " + std::to_string(all.size()) + ": the hashes of a scaled sketch are ascending, distinct and at most its maxHash";
                     return false;
                 }
+        // "abundances" (`sketch --scaled <n> --abund`): parallel to "hashes", every entry 1 .. 2^32 - 1; all objects of a file or none
+        std::vector<uint32_t> ab;
+        const bool has_abund = scaled && json_find(t, sp, end, "abundances", v);
+        if (has_abund) {
+            const std::string bad = "sketch " + std::to_string(all.size()) + ": \"abundances\" holds one number of 1 .. 2^32 - 1 for every hash";
+            q = t.c_str() + v;
+            if (*q != '[') { L.err = bad; return false; }
+            ++q;
+            for (;;) {
+                while (*q && (isspace((unsigned char)*q) || *q == ',')) ++q;
+                if (*q == ']' || !*q) break;
+                char* e;
+                const unsigned long long a = isdigit((unsigned char)*q) ? strtoull(q, &e, 10) : 0;
+                if (a < 1 || a > 0xffffffffull) { L.err = bad; return false; }
+                ab.push_back((uint32_t)a);
+                q = e;
+            }
+            if (ab.size() != h.size()) { L.err = bad; return false; }
+        }
+        if (!all.empty() && has_abund != L.has_abund) { L.err = "its sketches disagree in carrying abundances"; return false; }
+        L.has_abund = has_abund;
+        all_abund.push_back(ab);
         all.push_back(h);
         pos = end;
     }
@@ -100,6 +123,7 @@ bool load_sketch_json(const char* path, LoadedSketches& L, int max_S) {
             L.sk.insert(L.sk.end(), h.begin(), h.end());
             L.off.push_back(L.sk.size());
         }
+        for (const auto& a : all_abund) L.abund.insert(L.abund.end(), a.begin(), a.end());
         return true;
     }
     if (all.empty() || L.S <= 0) return false;

@@ -47,26 +47,34 @@ void sketch_files(rk_ctx* ctx, const std::vector<const char*>& files, const std:
 }
 void sketch_files_scaled(rk_ctx* ctx, const std::vector<const char*>& files, const std::vector<int>& ks, uint64_t max_hash, bool whole_files, ScaledSet& out) {
     std::vector<uint64_t> off;
-    auto batch = [&](const rk_seqset& s, uint64_t** v) {
+    auto batch = [&](const rk_seqset& s, uint64_t** v, uint32_t** a) {
         off.assign((size_t)s.nseq + 1, 0);
-        CK(rk_sketch_scaled_batch(ctx, s.bases, s.offsets, s.nseq, ks.data(), (int)ks.size(), max_hash, v, off.data()));
+        if (out.with_abund) CK(rk_sketch_scaled_abund_batch(ctx, s.bases, s.offsets, s.nseq, ks.data(), (int)ks.size(), max_hash, v, a, off.data()));
+        else CK(rk_sketch_scaled_batch(ctx, s.bases, s.offsets, s.nseq, ks.data(), (int)ks.size(), max_hash, v, off.data()));
     };
-    auto row = [&](const uint64_t* b, const uint64_t* e) { out.values.insert(out.values.end(), b, e); out.off.push_back(out.values.size()); };
+    auto row = [&](const uint64_t* b, const uint64_t* e, const uint32_t* a) {
+        out.values.insert(out.values.end(), b, e);
+        if (out.with_abund) out.abund.insert(out.abund.end(), a, a + (e - b));
+        out.off.push_back(out.values.size());
+    };
     walk_files(files, whole_files, out.names, out.seq_len,
                [&](const rk_seqset& s) {
                    uint64_t* v = nullptr;
-                   batch(s, &v);
-                   for (int64_t i = 0; i < s.nseq; ++i) row(v + off[(size_t)i], v + off[(size_t)i + 1]);
+                   uint32_t* a = nullptr;
+                   batch(s, &v, &a);
+                   for (int64_t i = 0; i < s.nseq; ++i) row(v + off[(size_t)i], v + off[(size_t)i + 1], a ? a + off[(size_t)i] : nullptr);
                    rk_free(v);
+                   rk_free(a);
                },
                [&](const rk_seqset& s) {
                    uint64_t *v = nullptr, *u = nullptr;
+                   uint32_t *a = nullptr, *ua = nullptr;
                    uint64_t nu = 0;
-                   batch(s, &v);
-                   CK(rk_merge_scaled(v, off.data(), (int)s.nseq, max_hash, &u, &nu));
-                   row(u, u + nu);
-                   rk_free(u);
-                   rk_free(v);
+                   batch(s, &v, &a);
+                   if (out.with_abund) CK(rk_merge_scaled_abund(v, a, off.data(), (int)s.nseq, max_hash, &u, &ua, &nu));
+                   else CK(rk_merge_scaled(v, off.data(), (int)s.nseq, max_hash, &u, &nu));
+                   row(u, u + nu, ua);
+                   for (void* p : {(void*)u, (void*)ua, (void*)v, (void*)a}) rk_free(p);
                });
 }
 
@@ -93,7 +101,13 @@ void write_sketch_json(FILE* fo, const std::vector<std::string>& names, const st
         std::string name;
         json_escape(name, names[i].c_str());
         if (i) o.append(",");
-        o.append(head + name + "\",\"preserveCase\":\"false\"," + scaled_key + "\"seqLen\":" + std::to_string(seq_len[i]) + ",\"sketches\":{\"comment\":\"\",\"hashes\":[");
+        o.append(head + name + "\",\"preserveCase\":\"false\"," + scaled_key + "\"seqLen\":" + std::to_string(seq_len[i]) + ",\"sketches\":{");
+        if (rows[i].abund) { // (in its alphabetical place)
+            o.append("\"abundances\":[");
+            for (uint64_t j = 0; j < rows[i].n; ++j) o.appendf(j ? ",%u" : "%u", (unsigned)rows[i].abund[j]);
+            o.append("],");
+        }
+        o.append("\"comment\":\"\",\"hashes\":[");
         for (uint64_t j = 0; j < rows[i].n; ++j) o.appendf(j ? ",%llu" : "%llu", (unsigned long long)rows[i].hashes[j]);
         o.append("],\"length\":" + std::to_string(rows[i].length) + ",\"name\":\"" + name + "\"}}");
         o.end_row();
@@ -151,7 +165,7 @@ int one_k(const CompareInputs& in, const CompareRules& rules) {
 }
 void load_sketch_files(const CompareInputs& in, const CompareRules& rules, LoadedSides& ld) {
     bool any_bottom = false;
-    auto load = [&](const std::vector<const char*>& paths, SketchSet& into, std::vector<LoadedSketches>& sc_into) {
+    auto load = [&](const std::vector<const char*>& paths, SketchSet& into, std::vector<LoadedSketches>& sc_into, bool need_abund) {
         for (const char* path : paths) {
             const std::string p(path);
             LoadedSketches L;
@@ -175,6 +189,7 @@ void load_sketch_files(const CompareInputs& in, const CompareRules& rules, Loade
                 if (ld.S != 0) refuse(rules, p + " holds scaled sketches (scaled = " + std::to_string(L.scaled) + "); -s is for bottom-s sketches");
                 if (in.scaled_given && L.scaled > in.scaled)
                     refuse(rules, p + " holds sketches of scaled = " + std::to_string(L.scaled) + ": they cannot be made finer, --scaled must be at least that");
+                if (need_abund && !L.has_abund) refuse(rules, p + " holds no abundances; --abund needs query sketches of `rkmh sketch --scaled <n> --abund`");
                 ld.largest_scaled = std::max(ld.largest_scaled, L.scaled);
                 sc_into.push_back(std::move(L));
                 continue;
@@ -188,8 +203,8 @@ void load_sketch_files(const CompareInputs& in, const CompareRules& rules, Loade
         }
     };
     ld.S = in.S;
-    load(in.ref_json, ld.refs, ld.sc_refs);
-    load(in.query_json, ld.queries, ld.sc_queries);
+    load(in.ref_json, ld.refs, ld.sc_refs, false);
+    load(in.query_json, ld.queries, ld.sc_queries, in.abund);
 }
 
 static void cut_scaled_files(const std::vector<LoadedSketches>& from, uint64_t max_hash, ScaledSet& into) {
@@ -199,6 +214,7 @@ static void cut_scaled_files(const std::vector<LoadedSketches>& from, uint64_t m
             const uint64_t* e = std::upper_bound(b, L.sk.data() + L.off[i + 1], max_hash);
             into.names.push_back(L.names[i]);
             into.values.insert(into.values.end(), b, e);
+            if (into.with_abund) into.abund.insert(into.abund.end(), L.abund.begin() + (ptrdiff_t)L.off[i], L.abund.begin() + (ptrdiff_t)(L.off[i] + (uint64_t)(e - b)));
             into.off.push_back(into.values.size());
         }
 }
@@ -206,6 +222,7 @@ void start_scaled_run(const CompareInputs& in, const CompareRules& rules, const 
     uint64_t max_hash = 0;
     CK(rk_scaled_max_hash(in.scaled_given ? in.scaled : ld.largest_scaled, &max_hash));
     ScaledSet &sr = run.refs, &sq = run.own_queries;
+    sq.with_abund = in.abund; // (the references' abundances play no part)
     cut_scaled_files(ld.sc_refs, max_hash, sr);
     cut_scaled_files(ld.sc_queries, max_hash, sq);
     if (in.ref_files.empty() && sr.names.empty()) refuse(rules, "no reference sketches");

@@ -13,7 +13,14 @@ the query is the union of --parts of them plus as many foreign values.  The refe
             at the fastest of lanes = 1, 8, 64, tried once each), argmax on the host, the remaining query rebuilt on the host and
             uploaded again each round; host clock around the loop, one warm-up, median of --base-runs
 All three answers must be equal.  Prints one JSON line; fails unless the device entry is faster than both baselines' medians by more
-than the larger of their spreads (max - min)."""
+than the larger of their spreads (max - min).
+
+    python tools/bench_gather.py --abund [--root <tree>]
+
+The device entry alone on the same input, for comparing two builds in one job (run it once per build, alternating; --root: the tree
+whose package and library are loaded, this one by default): rk_gather_scaled_device, and, where the library has it,
+rk_gather_scaled_abund_device with abundances of 1 to 500 on the query -- the same rows, plus wunique.  One JSON line with the median,
+min and max of --runs of each."""
 import argparse
 import json
 import os
@@ -23,7 +30,6 @@ import time
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
 
 
 def make_input(nref, size, parts, seed=1):
@@ -57,7 +63,10 @@ def main():
     ap.add_argument("--runs", type=int, default=7)
     ap.add_argument("--base-runs", type=int, default=3)
     ap.add_argument("--threads", type=int, default=16)
+    ap.add_argument("--abund", action="store_true")
+    ap.add_argument("--root", default=ROOT)
     o = ap.parse_args()
+    sys.path.insert(0, os.path.abspath(o.root))
     import torch
     import rkmh_amd
     from rkmh_amd import api
@@ -73,7 +82,7 @@ def main():
         return ctx.gather_scaled_device(d_q.data_ptr(), nq, d_rv.data_ptr(), d_ro.data_ptr(), nref, len(rv), d_out.data_ptr(),
                                         min_shared=o.min_shared, max_rounds=max_rounds, stream=st.cuda_stream)
 
-    def timed_device(max_rounds):
+    def timed_device(max_rounds, device=device):
         for _ in range(2):
             n = device(max_rounds)
         torch.cuda.synchronize()
@@ -88,6 +97,32 @@ def main():
         torch.cuda.synchronize()
         return stats(times), d_out.cpu().numpy()[:n].copy()
     dev, rows_dev = timed_device(nref)
+    if o.abund:
+        res = {"bench": "gather_abund", "root": os.path.abspath(o.root), "nref": nref, "size": o.size, "query": nq, "rows": len(rows_dev),
+               "plain_seconds": dev, "weighted_seconds": None}
+        if hasattr(ctx, "gather_scaled_abund_device"):
+            rng = np.random.default_rng(2)
+            qa = rng.integers(1, 501, size=nq, dtype=np.uint32)
+            d_qa = torch.from_numpy(qa.view(np.int32)).cuda()
+            d_wu = torch.full((nref,), -1, dtype=torch.int64, device="cuda")
+
+            def weighted(max_rounds):
+                return ctx.gather_scaled_abund_device(d_q.data_ptr(), d_qa.data_ptr(), nq, d_rv.data_ptr(), d_ro.data_ptr(), nref, len(rv), d_out.data_ptr(),
+                                                      d_wu.data_ptr(), min_shared=o.min_shared, max_rounds=max_rounds, stream=st.cuda_stream)
+            wdev, rows_w = timed_device(nref, weighted)
+            wu = d_wu.cpu().numpy()[:len(rows_w)]
+            alive, want = np.ones(nq, dtype=bool), []
+            for r in rows_w[:, 0].tolist():                      # the weights, recomputed from the rows
+                hit = np.isin(q, rv[int(ro[r]):int(ro[r + 1])], assume_unique=True) & alive
+                want.append(int(qa[hit].astype(np.uint64).sum()))
+                alive &= ~hit
+            res.update(weighted_seconds=wdev, weighted_over_plain=wdev["median"] / dev["median"],
+                       equal=bool(rows_w.shape == rows_dev.shape and (rows_w == rows_dev).all() and wu.tolist() == want))
+        print(json.dumps(res), flush=True)
+        ctx.close()
+        if res.get("equal") is False:
+            sys.exit("the weighted call's rows or weights are wrong")
+        return
     one, _ = timed_device(1)
     nrounds = len(rows_dev)
 

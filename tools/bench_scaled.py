@@ -5,6 +5,8 @@ plain two-pointer loop on 16 host threads (GPU box).
     g++ -O3 -fopenmp -o tools/ubench/scaled_cpu tools/ubench/scaled_cpu.cpp      (built on first use when missing)
     python tools/bench_scaled.py [--n 2048] [--sizes 800,5000] [--runs 7] [--threads 16] [--cpu-runs 5]
     python tools/bench_scaled.py --keep        (the keep step of the general path next to the hashing: RKMH_INDEX_TIMING lines on stderr)
+    python tools/bench_scaled.py --keep [--abund] [--root <tree>]     (the same with abundances; --root: the tree whose package and library
+                                               are loaded, this one by default -- for comparing two builds in one job)
 
 Input: 2 x n sets of `size` values each, a tenth of every set drawn from a pool all sets share (planted overlap).  800 values: a viral
 genome at scaled 10; 5 000: a bacterial genome at scaled 1000.  Device: the resident-input entry (rk_compare_scaled_device) on
@@ -22,7 +24,6 @@ import tempfile
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
 
 
 def make_input(n, size, seed=1):
@@ -102,7 +103,7 @@ def bench_pairs(o):
         sys.exit("; ".join(failures))
 
 
-def bench_keep():
+def bench_keep(abund):
     os.environ["RKMH_INDEX_TIMING"] = "1"      # read once, at the first batch of the general path
     import rkmh_amd
     from rkmh_amd import api, synth
@@ -115,8 +116,11 @@ def bench_keep():
     rb, ro = api.pack([one])
     for what, b, off, ks, scaled in (("one sequence of 300 000 bases, k = 21, scaled 1", rb, ro, [21], 1), ("3 000 reads of 150 bases, k = 16, scaled 1000", qb, qo, [16], 1000)):
         for rep in range(3):
-            print("---- %s (run %d)" % (what, rep), file=sys.stderr, flush=True)
-            v, so = ctx.sketch_scaled_batch(b, off, ks, api.scaled_max_hash(scaled))
+            print("---- %s%s (run %d)" % (what, ", with abundances" if abund else "", rep), file=sys.stderr, flush=True)
+            if abund:
+                v, _, so = ctx.sketch_scaled_abund_batch(b, off, ks, api.scaled_max_hash(scaled))
+            else:
+                v, so = ctx.sketch_scaled_batch(b, off, ks, api.scaled_max_hash(scaled))
         print("---- kept %d values in %d sketches" % (len(v), len(so) - 1), file=sys.stderr, flush=True)
     ctx.close()
 
@@ -129,9 +133,12 @@ def main():
     ap.add_argument("--cpu-runs", type=int, default=5)
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--keep", action="store_true")
+    ap.add_argument("--abund", action="store_true")
+    ap.add_argument("--root", default=ROOT)
     o = ap.parse_args()
+    sys.path.insert(0, os.path.abspath(o.root))
     if o.keep:
-        bench_keep()
+        bench_keep(o.abund)
     else:
         bench_pairs(o)
 
