@@ -751,6 +751,56 @@ int rk_gather_scaled_abund_host(const uint64_t* q_values, const uint32_t* q_abun
                                 const uint64_t* r_offsets, int nref, int min_shared, int max_rounds, int threads, int32_t* out4,
                                 uint64_t* wunique, int* nrounds);
 
+/* ------------------------------------------------------------------------------------------------
+ * WEIGHTED COMPARISON (`rkmh dist --abund`: two abundance sketches compared by the angle between their abundance vectors, as the
+ * sourmash family compares samples once abundances are tracked).  These are this library's own definitions; no compatibility with any
+ * other tool's files is claimed.
+ *   Inputs: an abundance sketch is values[] (ascending, distinct, non-zero uint64) and a parallel uint32 abund[], every entry >= 1; a
+ *   batch is the CSR of scaled sketches plus one uint32 per value, as rk_sketch_scaled_abund_batch returns it.  wA(x) = the abundance
+ *   of value x in sketch A.
+ *   Per pair (row i of a, row j of b), four uint64 at out4[(i * nb + j) * 4]:
+ *     0 shared   |A & B|: rk_compare_scaled's number for the pair
+ *     1 dot      sum over x in A & B of wA(x) * wB(x); every product fits 64 bits, the SUM SATURATES at 2^64 - 1
+ *     2 wa_in    sum over x in A & B of wA(x)
+ *     3 wb_in    sum over x in A & B of wB(x)
+ *   Saturating addition of non-negative numbers is associative and commutative: the result is min(true sum, 2^64 - 1) in whatever
+ *   order the lanes add, so it is the same for every `lanes` value.  wa_in and wb_in cannot overflow (fewer than 2^31 values, each
+ *   below 2^32).
+ *   Per sketch (rk_abund_row_sums*), two uint64 at out2[i * 2]: sum = the sum of its abundances, exact; sumsq = the sum of their
+ *   squares, saturating at 2^64 - 1.
+ *   It follows that with all abundances 1 dot = wa_in = wb_in = shared; that swapping the sides swaps fields 2 and 3 and keeps 0 and
+ *   1; and that a sketch against itself gives dot = sumsq, wa_in = wb_in = sum and shared = its length.
+ *   Floating point, host only: rk_angular_similarity(dot, sumsq_a, sumsq_b): cosine = (double)dot / sqrt((double)sumsq_a *
+ *   (double)sumsq_b), clamped to at most 1; angular = 1 - 2 acos(cosine) / pi.  When either sumsq is 0 both results are 0.  The root is
+ *   taken of the product, not of each factor: sqrt(fl(s) * fl(s)) is fl(s) exactly in IEEE binary arithmetic, so a sketch compared
+ *   with itself gives cosine 1 and angular similarity 1.  RK_ERR_ARG when dot is positive and one of the sumsq is 0; a saturated
+ *   input is taken as the number it is.  Either result pointer may be NULL.
+ * rk_compare_scaled_abund: host arrays; the checks of rk_compare_scaled, and RK_ERR_ARG for a NULL abundance array where there are
+ * values and for an abundance of 0.  a and b may be the same arrays: uploaded once, abundances included.  The answer is downloaded in
+ * row blocks of at most 64 MB (a row is nb * 32 bytes).  lanes as for rk_compare_scaled; the answer never depends on it.
+ * rk_compare_scaled_abund_device: resident arrays (d_x_abund: x_nvalues uint32 parallel to d_x_values; d_out4: na * nb * 32 bytes),
+ * asynchronous on hip_stream; every row is clamped on the device to lie inside [0, nvalues], and every abundance is read at an index
+ * at which a value of that clamped row was just read; rows that are not ascending give meaningless numbers and nothing worse.  This
+ * entry cannot check the abundances cheaply: a 0 adds nothing.
+ * rk_abund_row_sums: host arrays, n >= 1; RK_ERR_ARG for NULL, offsets that decrease, a row of 2^31 values or more, an abundance of
+ * 0.  rk_abund_row_sums_device: resident arrays (nvalues = the number of uint32 behind d_abund; d_out2: n * 16 bytes), asynchronous,
+ * rows clamped as above.
+ * The kernels (rk_scaled.hip): k_scaled_pairs_w<1 | 8 | 64> -- k_scaled_pairs's layout, slices and merge carrying four sums instead
+ * of one count -- and k_abund_row_sums, one wave per row.
+ * rk_compare_scaled_abund_host, rk_abund_row_sums_host, rk_angular_similarity: host code, usable without a GPU (rk_scaled_host.cpp);
+ * the checks of the entries on host arrays; `threads` host threads share the rows of a (below 1: one). */
+int rk_compare_scaled_abund(rk_ctx* ctx, const uint64_t* a_values, const uint32_t* a_abund, const uint64_t* a_offsets, int na,
+                            const uint64_t* b_values, const uint32_t* b_abund, const uint64_t* b_offsets, int nb, int lanes, uint64_t* out4);
+int rk_compare_scaled_abund_device(rk_ctx* ctx, const void* d_a_values, const void* d_a_abund, const void* d_a_offsets, int na, uint64_t a_nvalues,
+                                   const void* d_b_values, const void* d_b_abund, const void* d_b_offsets, int nb, uint64_t b_nvalues, int lanes,
+                                   void* d_out4, void* hip_stream);
+int rk_abund_row_sums(rk_ctx* ctx, const uint32_t* abund, const uint64_t* offsets, int n, uint64_t* out2);
+int rk_abund_row_sums_device(rk_ctx* ctx, const void* d_abund, const void* d_offsets, int n, uint64_t nvalues, void* d_out2, void* hip_stream);
+int rk_compare_scaled_abund_host(const uint64_t* a_values, const uint32_t* a_abund, const uint64_t* a_offsets, int na, const uint64_t* b_values,
+                                 const uint32_t* b_abund, const uint64_t* b_offsets, int nb, int threads, uint64_t* out4);
+int rk_abund_row_sums_host(const uint32_t* abund, const uint64_t* offsets, int n, uint64_t* out2);
+int rk_angular_similarity(uint64_t dot, uint64_t sumsq_a, uint64_t sumsq_b, double* cosine, double* angular);
+
 #ifdef __cplusplus
 }
 #endif

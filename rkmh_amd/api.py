@@ -259,6 +259,14 @@ _SIGS = {
     "rk_gather_scaled_abund_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_int,
                                                 C.c_int, C.c_void_p, C.c_void_p, _ip, C.c_void_p]),
     "rk_gather_scaled_abund_host": (C.c_int, [_u64p, _u32p, C.c_uint64, _u64p, _u64p, C.c_int, C.c_int, C.c_int, C.c_int, _i32p, _u64p, _ip]),
+    "rk_compare_scaled_abund": (C.c_int, [C.c_void_p, _u64p, _u32p, _u64p, C.c_int, _u64p, _u32p, _u64p, C.c_int, C.c_int, _u64p]),
+    "rk_compare_scaled_abund_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.c_int, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p]),
+    "rk_abund_row_sums": (C.c_int, [C.c_void_p, _u32p, _u64p, C.c_int, _u64p]),
+    "rk_abund_row_sums_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "rk_compare_scaled_abund_host": (C.c_int, [_u64p, _u32p, _u64p, C.c_int, _u64p, _u32p, _u64p, C.c_int, C.c_int, _u64p]),
+    "rk_abund_row_sums_host": (C.c_int, [_u32p, _u64p, C.c_int, _u64p]),
+    "rk_angular_similarity": (C.c_int, [C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
 }
 
 
@@ -1030,6 +1038,52 @@ def gather_scaled_abund_host(q, q_abund, r_values, r_offsets, min_shared=1, max_
     return out[: n.value].copy(), wu[: n.value].copy()
 
 
+def _abund_sides(a_values, a_abund, a_offsets, b_values, b_abund, b_offsets):
+    """both sides of a weighted comparison, checked (b None: a itself, the same arrays) -> (av, aw, ao, bv, bw, bo, out uint64 [na, nb, 4])"""
+    a_values, a_offsets = _csr(a_values, a_offsets)
+    a_abund = _abund(a_abund, a_values)
+    if b_values is None:
+        if b_abund is not None or b_offsets is not None:
+            raise ValueError("b_abund and b_offsets go with b_values")
+        b_values, b_abund, b_offsets = a_values, a_abund, a_offsets
+    else:
+        b_values, b_offsets = _csr(b_values, b_offsets)
+        b_abund = _abund(b_abund, b_values)
+    out = np.zeros((max(len(a_offsets) - 1, 0), max(len(b_offsets) - 1, 0), 4), dtype=np.uint64)
+    return a_values, a_abund, a_offsets, b_values, b_abund, b_offsets, out
+
+
+def _abund_rows(abund, offsets):
+    abund = np.ascontiguousarray(abund, dtype=np.uint32)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    if abund.ndim != 1 or len(offsets) < 1 or int(offsets.max()) > len(abund):
+        raise ValueError("offsets run past the %d abundances" % abund.size)
+    return abund, offsets, np.zeros((len(offsets) - 1, 2), dtype=np.uint64)
+
+
+def compare_scaled_abund_host(a_values, a_abund, a_offsets, b_values=None, b_abund=None, b_offsets=None, threads=1):
+    """rk_compare_scaled_abund_host (host code, no GPU): what Context.compare_scaled_abund gives, from plain loops on `threads` host threads."""
+    av, aw, ao, bv, bw, bo, out = _abund_sides(a_values, a_abund, a_offsets, b_values, b_abund, b_offsets)
+    _chk(load_library().rk_compare_scaled_abund_host(_p(av, C.c_uint64), _p(aw, C.c_uint32), _p(ao, C.c_uint64), len(ao) - 1, _p(bv, C.c_uint64),
+                                                     _p(bw, C.c_uint32), _p(bo, C.c_uint64), len(bo) - 1, int(threads), _p(out, C.c_uint64)))
+    return out
+
+
+def abund_row_sums_host(abund, offsets):
+    """rk_abund_row_sums_host (host code, no GPU): uint64 [n, 2], per CSR row of abundances (sum, sum of squares saturating at 2^64 - 1)."""
+    abund, offsets, out = _abund_rows(abund, offsets)
+    _chk(load_library().rk_abund_row_sums_host(_p(abund, C.c_uint32), _p(offsets, C.c_uint64), len(offsets) - 1, _p(out, C.c_uint64)))
+    return out
+
+
+def angular_similarity(dot, sumsq_a, sumsq_b):
+    """rk_angular_similarity (host code, no GPU): (cosine, angular) = (dot / sqrt(sumsq_a * sumsq_b) clamped to 1, 1 - 2 acos(cosine) / pi);
+    both 0 when a sumsq is 0."""
+    c, a = C.c_double(), C.c_double()
+    _chk(load_library().rk_angular_similarity(C.c_uint64(int(dot)), C.c_uint64(int(sumsq_a)), C.c_uint64(int(sumsq_b)), C.byref(c), C.byref(a)))
+    return c.value, a.value
+
+
 class Context:
     """One GPU. Methods are named after the reference's functions they replace."""
 
@@ -1208,6 +1262,40 @@ class Context:
         _chk(self._lib.rk_compare_scaled_device(self._h, C.c_void_p(d_a_values_ptr), C.c_void_p(d_a_offsets_ptr), na, C.c_uint64(int(a_nvalues)),
                                                 C.c_void_p(d_b_values_ptr), C.c_void_p(d_b_offsets_ptr), nb, C.c_uint64(int(b_nvalues)),
                                                 int(lanes), C.c_void_p(d_shared_ptr), C.c_void_p(stream)))
+
+    # ---- weighted comparison ---------------------------------------------------------------------
+    def compare_scaled_abund(self, a_values, a_abund, a_offsets, b_values=None, b_abund=None, b_offsets=None, lanes=0):
+        """rk_compare_scaled_abund: every CSR abundance sketch of `a` against every one of `b` (None: of `a` itself) -> uint64
+        [na, nb, 4]: (shared, dot = sum of wA * wB over the shared values, saturating at 2^64 - 1, wa_in, wb_in = the abundances of the
+        shared values summed per side).  lanes as for compare_scaled; the answer is the same."""
+        av, aw, ao, bv, bw, bo, out = _abund_sides(a_values, a_abund, a_offsets, b_values, b_abund, b_offsets)
+        _chk(self._lib.rk_compare_scaled_abund(self._h, _p(av, C.c_uint64), _p(aw, C.c_uint32), _p(ao, C.c_uint64), len(ao) - 1, _p(bv, C.c_uint64),
+                                               _p(bw, C.c_uint32), _p(bo, C.c_uint64), len(bo) - 1, int(lanes), _p(out, C.c_uint64)))
+        return out
+
+    def compare_scaled_abund_device(self, d_a_values_ptr, d_a_abund_ptr, d_a_offsets_ptr, na, a_nvalues, d_b_values_ptr, d_b_abund_ptr, d_b_offsets_ptr,
+                                    nb, b_nvalues, d_out4_ptr, lanes=0, stream=None):
+        """Resident CSR arrays and their abundances (raw device pointers; d_out4: na * nb * 4 uint64); asynchronous.  Rows are clamped to
+        [0, nvalues] on the device; an abundance of 0 adds nothing.  stream as for compare_sketches_device."""
+        if stream is None:
+            stream = self.stream
+        _chk(self._lib.rk_compare_scaled_abund_device(self._h, C.c_void_p(d_a_values_ptr), C.c_void_p(d_a_abund_ptr), C.c_void_p(d_a_offsets_ptr), na,
+                                                      C.c_uint64(int(a_nvalues)), C.c_void_p(d_b_values_ptr), C.c_void_p(d_b_abund_ptr),
+                                                      C.c_void_p(d_b_offsets_ptr), nb, C.c_uint64(int(b_nvalues)), int(lanes), C.c_void_p(d_out4_ptr),
+                                                      C.c_void_p(stream)))
+
+    def abund_row_sums(self, abund, offsets):
+        """rk_abund_row_sums: uint64 [n, 2], per CSR row of abundances (sum, sum of squares saturating at 2^64 - 1)."""
+        abund, offsets, out = _abund_rows(abund, offsets)
+        _chk(self._lib.rk_abund_row_sums(self._h, _p(abund, C.c_uint32), _p(offsets, C.c_uint64), len(offsets) - 1, _p(out, C.c_uint64)))
+        return out
+
+    def abund_row_sums_device(self, d_abund_ptr, d_offsets_ptr, n, nvalues, d_out2_ptr, stream=None):
+        """Resident arrays (raw device pointers; d_out2: n * 2 uint64); asynchronous; rows are clamped to [0, nvalues] on the device."""
+        if stream is None:
+            stream = self.stream
+        _chk(self._lib.rk_abund_row_sums_device(self._h, C.c_void_p(d_abund_ptr), C.c_void_p(d_offsets_ptr), n, C.c_uint64(int(nvalues)),
+                                                C.c_void_p(d_out2_ptr), C.c_void_p(stream)))
 
     # ---- gather ----------------------------------------------------------------------------------
     def gather_scaled(self, q, r_values, r_offsets, min_shared=1, max_rounds=None):

@@ -1,7 +1,8 @@
 // rk_scaled.hip -- scaled (FracMinHash) sketches (include/rkmh_amd.h, "SCALED SKETCHES"): the step of the general path that turns a
 // chunk's window hashes into one variable-length set per sequence (keep / sort / drop repeats), and k_scaled_pairs, which intersects
 // every pair of such sets.  The host-only half (threshold, union, distance) is rk_scaled_host.cpp; semantics, routes, the lane rule
-// and measurements: DESIGN.md section 11; the abundances (the run lengths of the drop-repeats step): section 13.
+// and measurements: DESIGN.md section 11; the abundances (the run lengths of the drop-repeats step): section 13; the weighted pairs
+// (k_scaled_pairs_w, k_abund_row_sums, at the end of the file): section 14.
 #include "rk_api_internal.hpp"
 
 namespace {
@@ -442,5 +443,224 @@ extern "C" int rk_compare_scaled(rk_ctx* c, const uint64_t* a_values, const uint
         HIPCHK(hipMemcpyAsync(shared + r0 * (size_t)nb, c->w_out.p, (size_t)n * row_bytes, hipMemcpyDeviceToHost, c->st));
         HIPCHK(hipStreamSynchronize(c->st));
     }
+    return RK_OK;
+}
+
+// ---- weighted pairs (include/rkmh_amd.h, "WEIGHTED COMPARISON") ------------------------------------------
+// These stand behind everything else in the file so that the kernels above keep the code they had.
+namespace {
+
+// min(a + b, 2^64 - 1).  Associative and commutative on non-negative numbers: the result is min(true sum, 2^64 - 1) in any order.
+__device__ __forceinline__ uint64_t sat_add(uint64_t a, uint64_t b) {
+    const uint64_t s = a + b;
+    return s < a ? ~0ull : s;
+}
+// a 64-bit value from lane (self ^ d), as two halves
+__device__ __forceinline__ uint64_t shfl_xor_u64(uint64_t v, int d) {
+    const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, d, 64), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), d, 64);
+    return ((uint64_t)hi << 32) | lo;
+}
+
+// k_scaled_pairs with abundances: the same pair layout, clamps, slices, search and merge; on an equal pair the lane also loads the
+// two abundances, which lie parallel to the values, so at the index (inside its clamped row) at which it has just read the value.
+// X is the shorter row whichever side it is: the sums are kept per row of the merge (wx, wy) and given their sides at the end.  Four
+// partial results per lane -- shared, dot (saturating), wx, wy -- are added over the aligned group of L lanes with shuffles; no LDS,
+// no atomics; the group's first lane stores the four uint64.  wx and wy cannot overflow: fewer than 2^31 values below 2^32 each.
+template <int L>
+__global__ __launch_bounds__(PAIRS_T) void k_scaled_pairs_w(const uint64_t* __restrict__ av, const uint32_t* __restrict__ aw, const uint64_t* __restrict__ aoff,
+                                                            int na, uint64_t an, const uint64_t* __restrict__ bv, const uint32_t* __restrict__ bw,
+                                                            const uint64_t* __restrict__ boff, int nb, uint64_t bn, uint64_t* __restrict__ out) {
+    const uint64_t npairs = (uint64_t)na * (uint64_t)nb;
+    const uint64_t p = (uint64_t)blockIdx.x * (PAIRS_T / L) + threadIdx.x / L;
+    const uint32_t sub = threadIdx.x % L;
+    const bool live = p < npairs; // lanes without a pair still take part in the shuffles
+    uint64_t cnt = 0, dot = 0, wx = 0, wy = 0;
+    bool a_short = true;
+    if (live) {
+        const uint64_t i = p / (uint64_t)nb, j = p % (uint64_t)nb;
+        const uint64_t a0 = min(aoff[i], an), a1 = max(min(aoff[i + 1], an), a0);
+        const uint64_t b0 = min(boff[j], bn), b1 = max(min(boff[j + 1], bn), b0);
+        const uint32_t la = (uint32_t)min(a1 - a0, (uint64_t)0x7fffffffu), lb = (uint32_t)min(b1 - b0, (uint64_t)0x7fffffffu);
+        a_short = la <= lb;
+        const uint64_t* __restrict__ X = a_short ? av + a0 : bv + b0;
+        const uint64_t* __restrict__ Y = a_short ? bv + b0 : av + a0;
+        const uint32_t* __restrict__ XW = a_short ? aw + a0 : bw + b0;
+        const uint32_t* __restrict__ YW = a_short ? bw + b0 : aw + a0;
+        const uint32_t lx = a_short ? la : lb, ly = a_short ? lb : la;
+        const uint32_t s0 = (uint32_t)((uint64_t)lx * sub / L), s1 = (uint32_t)((uint64_t)lx * (sub + 1) / L);
+        if (s0 < s1 && ly > 0) {
+            uint64_t x = X[s0];
+            uint32_t lo = 0, hi = ly; // first Y >= x
+            if (L > 1 && s0 > 0)
+                while (lo < hi) {
+                    const uint32_t mid = lo + ((hi - lo) >> 1);
+                    if (Y[mid] < x) lo = mid + 1; else hi = mid;
+                }
+            uint32_t ii = s0, jj = lo;
+            if (jj < ly) {
+                uint64_t y = Y[jj];
+                for (;;) {
+                    const bool ax = x <= y, ay = y <= x;
+                    if (ax && ay) { // ii < s1 <= lx and jj < ly: the indices at which x and y were read
+                        const uint64_t u = XW[ii], w = YW[jj];
+                        cnt += 1;
+                        dot = sat_add(dot, u * w); // (2^32 - 1)^2 < 2^64
+                        wx += u;
+                        wy += w;
+                    }
+                    ii += ax ? 1u : 0u;
+                    jj += ay ? 1u : 0u;
+                    if (ii >= s1 || jj >= ly) break;
+                    if (ax) x = X[ii];
+                    if (ay) y = Y[jj];
+                }
+            }
+        }
+    }
+    for (int d = L >> 1; d > 0; d >>= 1) {
+        cnt += shfl_xor_u64(cnt, d);
+        dot = sat_add(dot, shfl_xor_u64(dot, d));
+        wx += shfl_xor_u64(wx, d);
+        wy += shfl_xor_u64(wy, d);
+    }
+    if (live && sub == 0) { // a_short is the group's: every lane of it has the same pair
+        uint64_t* __restrict__ o = out + p * 4;
+        o[0] = cnt;
+        o[1] = dot;
+        o[2] = a_short ? wx : wy;
+        o[3] = a_short ? wy : wx;
+    }
+}
+
+// out[i * 2] = sum of row i's abundances, out[i * 2 + 1] = sum of their squares, saturating.  One wave per row, grid-stride; the
+// lanes stride the row.  Rows are clamped to [0, nvalues] and to 2^31 - 1 entries, so the sum is exact.
+constexpr int SUMS_T = 256;
+__global__ __launch_bounds__(SUMS_T) void k_abund_row_sums(const uint32_t* __restrict__ w, const uint64_t* __restrict__ off, int n, uint64_t nvalues,
+                                                           uint64_t* __restrict__ out) {
+    const uint32_t lane = threadIdx.x & 63;
+    for (uint64_t i = (uint64_t)blockIdx.x * (SUMS_T / 64) + (threadIdx.x >> 6); i < (uint64_t)n; i += (uint64_t)gridDim.x * (SUMS_T / 64)) { // whole waves
+        const uint64_t r0 = min(off[i], nvalues), r1 = max(min(off[i + 1], nvalues), r0);
+        const uint64_t len = min(r1 - r0, (uint64_t)0x7fffffffu);
+        uint64_t sum = 0, sq = 0;
+        for (uint64_t t = lane; t < len; t += 64) {
+            const uint64_t u = w[r0 + t];
+            sum += u;
+            sq = sat_add(sq, u * u);
+        }
+        for (int d = 32; d > 0; d >>= 1) {
+            sum += shfl_xor_u64(sum, d);
+            sq = sat_add(sq, shfl_xor_u64(sq, d));
+        }
+        if (lane == 0) { out[i * 2] = sum; out[i * 2 + 1] = sq; }
+    }
+}
+
+int launch_scaled_pairs_w(const uint64_t* av, const uint32_t* aw, const uint64_t* aoff, int na, uint64_t an, const uint64_t* bv, const uint32_t* bw,
+                          const uint64_t* boff, int nb, uint64_t bn, int lanes, uint64_t* out, hipStream_t st) {
+    const int L = lanes ? lanes : auto_lanes(an, na, bn, nb);
+    const uint64_t per = (uint64_t)(PAIRS_T / L), blocks = ((uint64_t)na * (uint64_t)nb + per - 1) / per;
+    if (blocks > 0x7fffffffull) return fail(RK_ERR_LIMIT, "%d x %d sketches are more pairs than one launch takes", na, nb);
+    const dim3 grid((uint32_t)blocks), block(PAIRS_T);
+    if (L == 1) hipLaunchKernelGGL(k_scaled_pairs_w<1>, grid, block, 0, st, av, aw, aoff, na, an, bv, bw, boff, nb, bn, out);
+    else if (L == 8) hipLaunchKernelGGL(k_scaled_pairs_w<8>, grid, block, 0, st, av, aw, aoff, na, an, bv, bw, boff, nb, bn, out);
+    else hipLaunchKernelGGL(k_scaled_pairs_w<64>, grid, block, 0, st, av, aw, aoff, na, an, bv, bw, boff, nb, bn, out);
+    HIPCHK(hipGetLastError());
+    return RK_OK;
+}
+int launch_row_sums(const uint32_t* w, const uint64_t* off, int n, uint64_t nvalues, uint64_t* out, hipStream_t st) {
+    const uint32_t blocks = (uint32_t)std::min<uint64_t>(((uint64_t)n + SUMS_T / 64 - 1) / (SUMS_T / 64), 16384);
+    hipLaunchKernelGGL(k_abund_row_sums, dim3(blocks), dim3(SUMS_T), 0, st, w, off, n, nvalues, out);
+    HIPCHK(hipGetLastError());
+    return RK_OK;
+}
+// every abundance of rows [off[0], off[n]) is at least 1
+int check_abund(const uint32_t* w, const uint64_t* off, int n, const char* side) {
+    for (uint64_t t = off[0]; t < off[n]; ++t)
+        if (w[t] == 0) return fail(RK_ERR_ARG, "abundance 0 at value %llu of %s", (unsigned long long)t, side);
+    return RK_OK;
+}
+
+} // namespace
+
+extern "C" int rk_compare_scaled_abund_device(rk_ctx* c, const void* d_a_values, const void* d_a_abund, const void* d_a_offsets, int na, uint64_t a_nvalues,
+                                              const void* d_b_values, const void* d_b_abund, const void* d_b_offsets, int nb, uint64_t b_nvalues, int lanes,
+                                              void* d_out4, void* hip_stream) {
+    if (!c || !d_a_offsets || !d_b_offsets || !d_out4 || ((!d_a_values || !d_a_abund) && a_nvalues) || ((!d_b_values || !d_b_abund) && b_nvalues))
+        return fail(RK_ERR_ARG, "bad arguments");
+    RKCHK(check_pairs_shape(na, nb, lanes));
+    RKCHK(set_dev(c));
+    return launch_scaled_pairs_w((const uint64_t*)d_a_values, (const uint32_t*)d_a_abund, (const uint64_t*)d_a_offsets, na, a_nvalues, (const uint64_t*)d_b_values,
+                                 (const uint32_t*)d_b_abund, (const uint64_t*)d_b_offsets, nb, b_nvalues, lanes, (uint64_t*)d_out4, (hipStream_t)hip_stream);
+}
+
+extern "C" int rk_compare_scaled_abund(rk_ctx* c, const uint64_t* a_values, const uint32_t* a_abund, const uint64_t* a_offsets, int na, const uint64_t* b_values,
+                                       const uint32_t* b_abund, const uint64_t* b_offsets, int nb, int lanes, uint64_t* out4) {
+    if (!c || !a_offsets || !b_offsets || !out4) return fail(RK_ERR_ARG, "bad arguments");
+    RKCHK(check_pairs_shape(na, nb, lanes));
+    RKCHK(check_csr(a_offsets, na, "a"));
+    RKCHK(check_csr(b_offsets, nb, "b"));
+    const uint64_t an = a_offsets[na], bn = b_offsets[nb];
+    if ((an && (!a_values || !a_abund)) || (bn && (!b_values || !b_abund))) return fail(RK_ERR_ARG, "bad arguments");
+    const bool self = a_values == b_values && a_abund == b_abund && a_offsets == b_offsets && na == nb;
+    RKCHK(check_abund(a_abund, a_offsets, na, "a"));
+    if (!self) RKCHK(check_abund(b_abund, b_offsets, nb, "b"));
+    RKCHK(set_dev(c));
+    std::lock_guard<std::mutex> lk(c->general_mu); // the general path's work buffers serve here too
+    RKCHK(c->w_sk.reserve((size_t)(an + (self ? 0 : bn)) * 8 + 8));
+    RKCHK(c->w_sc_ab.reserve((size_t)(an + (self ? 0 : bn)) * 4 + 4));
+    RKCHK(c->w_sc_off.reserve(((size_t)na + 1 + (self ? 0 : (size_t)nb + 1)) * 8));
+    uint64_t* d_av = c->w_sk.as<uint64_t>();
+    uint64_t* d_bv = self ? d_av : d_av + an;
+    uint32_t* d_aw = c->w_sc_ab.as<uint32_t>();
+    uint32_t* d_bw = self ? d_aw : d_aw + an;
+    uint64_t* d_ao = c->w_sc_off.as<uint64_t>();
+    uint64_t* d_bo = self ? d_ao : d_ao + na + 1;
+    if (an) HIPCHK(hipMemcpyAsync(d_av, a_values, (size_t)an * 8, hipMemcpyHostToDevice, c->st));
+    if (an) HIPCHK(hipMemcpyAsync(d_aw, a_abund, (size_t)an * 4, hipMemcpyHostToDevice, c->st));
+    HIPCHK(hipMemcpyAsync(d_ao, a_offsets, ((size_t)na + 1) * 8, hipMemcpyHostToDevice, c->st));
+    if (!self) {
+        if (bn) HIPCHK(hipMemcpyAsync(d_bv, b_values, (size_t)bn * 8, hipMemcpyHostToDevice, c->st));
+        if (bn) HIPCHK(hipMemcpyAsync(d_bw, b_abund, (size_t)bn * 4, hipMemcpyHostToDevice, c->st));
+        HIPCHK(hipMemcpyAsync(d_bo, b_offsets, ((size_t)nb + 1) * 8, hipMemcpyHostToDevice, c->st));
+    }
+    const int L = lanes ? lanes : auto_lanes(an, na, bn, nb); // one choice for all row blocks
+    // the rows of the answer leave in blocks of at most 64 MB (one row when nb alone is wider than that)
+    const size_t row_bytes = (size_t)nb * 32;
+    size_t rows = std::max<size_t>(1, ((size_t)64 << 20) / row_bytes);
+    if (rows > (size_t)na) rows = (size_t)na;
+    RKCHK(c->w_out.reserve(rows * row_bytes));
+    for (size_t r0 = 0; r0 < (size_t)na; r0 += rows) {
+        const int n = (int)std::min(rows, (size_t)na - r0);
+        RKCHK(launch_scaled_pairs_w(d_av, d_aw, d_ao + r0, n, an, d_bv, d_bw, d_bo, nb, bn, L, c->w_out.as<uint64_t>(), c->st));
+        HIPCHK(hipMemcpyAsync(out4 + r0 * (size_t)nb * 4, c->w_out.p, (size_t)n * row_bytes, hipMemcpyDeviceToHost, c->st));
+        HIPCHK(hipStreamSynchronize(c->st));
+    }
+    return RK_OK;
+}
+
+extern "C" int rk_abund_row_sums_device(rk_ctx* c, const void* d_abund, const void* d_offsets, int n, uint64_t nvalues, void* d_out2, void* hip_stream) {
+    if (!c || !d_offsets || !d_out2 || (!d_abund && nvalues)) return fail(RK_ERR_ARG, "bad arguments");
+    if (n < 1) return fail(RK_ERR_ARG, "need at least one sketch, got %d", n);
+    RKCHK(set_dev(c));
+    return launch_row_sums((const uint32_t*)d_abund, (const uint64_t*)d_offsets, n, nvalues, (uint64_t*)d_out2, (hipStream_t)hip_stream);
+}
+
+extern "C" int rk_abund_row_sums(rk_ctx* c, const uint32_t* abund, const uint64_t* offsets, int n, uint64_t* out2) {
+    if (!c || !offsets || !out2) return fail(RK_ERR_ARG, "bad arguments");
+    if (n < 1) return fail(RK_ERR_ARG, "need at least one sketch, got %d", n);
+    RKCHK(check_csr(offsets, n, "the sketches"));
+    const uint64_t nv = offsets[n];
+    if (nv && !abund) return fail(RK_ERR_ARG, "bad arguments");
+    RKCHK(check_abund(abund, offsets, n, "the sketches"));
+    RKCHK(set_dev(c));
+    std::lock_guard<std::mutex> lk(c->general_mu);
+    RKCHK(c->w_sc_ab.reserve((size_t)nv * 4 + 4));
+    RKCHK(c->w_sc_off.reserve(((size_t)n + 1) * 8));
+    RKCHK(c->w_out.reserve((size_t)n * 16));
+    if (nv) HIPCHK(hipMemcpyAsync(c->w_sc_ab.p, abund, (size_t)nv * 4, hipMemcpyHostToDevice, c->st));
+    HIPCHK(hipMemcpyAsync(c->w_sc_off.p, offsets, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, c->st));
+    RKCHK(launch_row_sums(c->w_sc_ab.as<uint32_t>(), c->w_sc_off.as<uint64_t>(), n, nv, c->w_out.as<uint64_t>(), c->st));
+    HIPCHK(hipMemcpyAsync(out2, c->w_out.p, (size_t)n * 16, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(hipStreamSynchronize(c->st));
     return RK_OK;
 }

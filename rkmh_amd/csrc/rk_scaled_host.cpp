@@ -1,7 +1,7 @@
 // rk_scaled_host.cpp -- the host half of scaled (FracMinHash) sketches (include/rkmh_amd.h, "SCALED SKETCHES"): the threshold of a
 // `scaled` value, the union of sketches (what `-g` reduces the records of a file with, and what cuts a sketch down to a larger
-// `scaled`), and the one place where counts become floating point.  Host code only, usable without a GPU; the kernels are
-// rk_scaled.hip.
+// `scaled`), the host forms of gather and of the weighted comparison, and the places where counts become floating point.  Host code
+// only, usable without a GPU; the kernels are rk_scaled.hip.
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -178,6 +178,86 @@ extern "C" int rk_gather_scaled_abund_host(const uint64_t* q, const uint32_t* q_
         for (uint64_t i = 0; i < nq; ++i)
             if (q_abund[i] == 0) return bad(who + ": abundance 0 at query value " + std::to_string(i));
     return gather_host(who, q, q_abund, nq, rv, roff, nref, min_shared, max_rounds, threads, out4, wunique, nrounds);
+}
+
+// ---- weighted comparison on the host (include/rkmh_amd.h, "WEIGHTED COMPARISON"): the sums of k_scaled_pairs_w and k_abund_row_sums
+// from plain loops, and the one place where they become floating point.
+namespace {
+inline uint64_t sat_add(uint64_t a, uint64_t b) { const uint64_t s = a + b; return s < a ? ~0ull : s; }
+// the checks of one side: offsets that ascend, rows below 2^31 values, arrays where there are values, no abundance of 0
+int check_abund_side(const std::string& who, const char* side, const uint64_t* values, bool need_values, const uint32_t* abund, const uint64_t* off, int n) {
+    for (int i = 0; i < n; ++i) {
+        if (off[i + 1] < off[i]) return bad(who + ": offsets of " + side + " decrease at sketch " + std::to_string(i));
+        if (off[i + 1] - off[i] > 0x7fffffffull) return bad(who + ": sketch " + std::to_string(i) + " of " + side + " holds 2^31 values or more");
+    }
+    if (off[n] > 0 && ((need_values && !values) || !abund)) return bad(who + ": values or abundances of " + side + " are NULL");
+    for (uint64_t t = off[0]; t < off[n]; ++t)
+        if (abund[t] == 0) return bad(who + ": abundance 0 at value " + std::to_string(t) + " of " + side);
+    return RK_OK;
+}
+} // namespace
+
+extern "C" int rk_compare_scaled_abund_host(const uint64_t* av, const uint32_t* aw, const uint64_t* aoff, int na, const uint64_t* bv, const uint32_t* bw,
+                                            const uint64_t* boff, int nb, int threads, uint64_t* out4) {
+    const std::string who = "rk_compare_scaled_abund_host";
+    if (!aoff || !boff || !out4) return bad(who + ": bad arguments");
+    if (na < 1 || nb < 1) return bad(who + ": need at least one sketch on each side");
+    if (int r = check_abund_side(who, "a", av, true, aw, aoff, na)) return r;
+    if (int r = check_abund_side(who, "b", bv, true, bw, boff, nb)) return r;
+    on_threads((size_t)na, threads, 1, [&](size_t lo, size_t hi) {
+        for (size_t i = lo; i < hi; ++i)
+            for (size_t j = 0; j < (size_t)nb; ++j) {
+                uint64_t ii = aoff[i], jj = boff[j], cnt = 0, dot = 0, wa = 0, wb = 0;
+                const uint64_t ie = aoff[i + 1], je = boff[j + 1];
+                while (ii < ie && jj < je) {
+                    const uint64_t x = av[ii], y = bv[jj];
+                    if (x == y) {
+                        cnt += 1;
+                        dot = sat_add(dot, (uint64_t)aw[ii] * (uint64_t)bw[jj]);
+                        wa += aw[ii];
+                        wb += bw[jj];
+                    }
+                    ii += x <= y;
+                    jj += y <= x;
+                }
+                uint64_t* o = out4 + (i * (size_t)nb + j) * 4;
+                o[0] = cnt; o[1] = dot; o[2] = wa; o[3] = wb;
+            }
+    });
+    return RK_OK;
+}
+
+extern "C" int rk_abund_row_sums_host(const uint32_t* abund, const uint64_t* offsets, int n, uint64_t* out2) {
+    const std::string who = "rk_abund_row_sums_host";
+    if (!offsets || !out2) return bad(who + ": bad arguments");
+    if (n < 1) return bad(who + ": need at least one sketch");
+    if (int r = check_abund_side(who, "the sketches", nullptr, false, abund, offsets, n)) return r;
+    for (int i = 0; i < n; ++i) {
+        uint64_t sum = 0, sq = 0;
+        for (uint64_t t = offsets[i]; t < offsets[i + 1]; ++t) {
+            const uint64_t u = abund[t];
+            sum += u;
+            sq = sat_add(sq, u * u);
+        }
+        out2[(size_t)i * 2] = sum;
+        out2[(size_t)i * 2 + 1] = sq;
+    }
+    return RK_OK;
+}
+
+// cosine = dot / sqrt(sumsq_a * sumsq_b), at most 1; angular = 1 - 2 acos(cosine) / pi.  The root is taken of the product: sqrt(fl(s) *
+// fl(s)) is fl(s) exactly, so a sketch against itself gives 1 and 1.  Either sumsq 0: both 0.  A saturated input is the number it is.
+extern "C" int rk_angular_similarity(uint64_t dot, uint64_t sumsq_a, uint64_t sumsq_b, double* cosine, double* angular) {
+    if (dot > 0 && (sumsq_a == 0 || sumsq_b == 0)) return bad("rk_angular_similarity: a positive dot product needs both sums of squares positive");
+    double c = 0.0, a = 0.0;
+    if (sumsq_a != 0 && sumsq_b != 0) {
+        c = (double)dot / std::sqrt((double)sumsq_a * (double)sumsq_b);
+        if (c > 1.0) c = 1.0;
+        a = 1.0 - 2.0 * std::acos(c) / 3.141592653589793;
+    }
+    if (cosine) *cosine = c;
+    if (angular) *angular = a;
+    return RK_OK;
 }
 
 // rk_mash_distance's formula and clamps on j = shared / (la + lb - shared): j = 0 and the distance 1 when the union is empty; the

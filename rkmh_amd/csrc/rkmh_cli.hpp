@@ -112,7 +112,7 @@ struct CompareInputs {
     std::vector<int> ks;
     int S = 0, device = 0; // S: 0 without -s, -1 for a -s below 1
     bool whole_files = false, scaled_given = false, scaled_ok = true;
-    bool abund = false; // gather --abund: the queries carry abundances
+    bool abund = false; // gather --abund: the queries carry abundances; dist --abund: both sides do
     uint64_t scaled = 0;
     bool self() const { return query_files.empty() && query_json.empty(); }
 };
@@ -127,6 +127,7 @@ struct CompareRules { // where the two differ in what they accept and in their w
     const char* no_bottom;       // what a bottom-s file is told after "<path> holds bottom-s sketches; "; nullptr: such files are welcome
     bool file_is_one_query;      // every -f file is ONE query, whatever -g says of the -r files
     const char* too_many_loaded; // refusal of more than 2^31-1 loaded sketches on a side before a context exists; nullptr: none
+    bool abund_both_sides = false; // --abund: the references carry abundances as the queries do (dist); false: the queries alone (gather)
 };
 [[noreturn]] void refuse(const CompareRules& rules, const std::string& why);
 int one_k(const CompareInputs& in, const CompareRules& rules); // -k, 0 without one; several are refused

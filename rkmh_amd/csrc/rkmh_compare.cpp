@@ -11,7 +11,7 @@ static void help_sketch() {
             "  --scaled <n>: scaled (FracMinHash) sketches instead of bottom-s ones: every distinct hash up to (2^64 - 1) / n, so the size\n"
             "  grows with the sequence; objects gain \"scaled\" and \"maxHash\"; such files serve `rkmh dist` only\n"
             "  --abund (with --scaled): \"sketches\" gains \"abundances\", parallel to \"hashes\": how many windows of the sequence hash to each\n"
-            "  value (with -g: summed over the file's records); `rkmh gather --abund -Q` needs them, every other reader ignores them\n"
+            "  value (with -g: summed over the file's records); `rkmh gather --abund -Q` and `rkmh dist --abund -R / -Q` need them, every other reader ignores them\n"
             "  `rkmh stream -R <out.json>` loads it instead of sketching references again;\n"
             "  --kmer-cache <file>: also enumerates the k-mers behind these sketches (k 8 .. 18) into <file>, which\n"
             "  `rkmh stream -R <out.json> --kmer-cache <file>` then loads instead of enumerating them at every start\n"
@@ -102,11 +102,12 @@ static int run_k(const CompareRules& rules, int k) {
 // ------------------------------------------------------------------------------------------------------------------------
 // dist: the Mash distance of every (query, reference) pair of sketches -- `mash dist`, which the reference has no command for.  The
 // four counts of a pair come from one launch over all pairs (rk_compare_sketches); the floating point is rk_mash_distance's.  With
-// scaled sketches: their shared values (rk_compare_scaled) and rk_scaled_distance.
+// scaled sketches: their shared values (rk_compare_scaled) and rk_scaled_distance; with --abund on top of that the four sums of
+// rk_compare_scaled_abund, the row sums of both sides and rk_angular_similarity: three more columns.
 // Everything that can be refused is refused before a context exists: nothing is printed by a run that fails.
 static void help_dist() {
     fprintf(stderr,
-            "rkmh dist (-r <refs.fa> ... | -R <refs.json>) [-f <queries.fa|fq> ... | -Q <queries.json>] [-k <k>] [-s <sketch> | --scaled <n>] [-g] [-d <maxdist>]\n"
+            "rkmh dist (-r <refs.fa> ... | -R <refs.json>) [-f <queries.fa|fq> ... | -Q <queries.json>] [-k <k>] [-s <sketch> | --scaled <n> [--abund]] [-g] [-d <maxdist>]\n"
             "  prints one line per (query, reference) pair, query by query: reference, query, Mash distance, common/denom of the merged\n"
             "  bottom-s sketch, shared hashes (the multiset intersection `stream` counts); without -f / -Q every reference is compared\n"
             "  with every reference\n"
@@ -115,26 +116,49 @@ static void help_dist() {
             "  -R / -Q files hold sketches of `rkmh sketch --scaled <m>`, m <= n, and are cut down to n (without --scaled: to the largest m\n"
             "  among them); a line is then: reference, query, distance from shared/union, shared/union, shared/|query|, shared/|reference|\n"
             "  (the last two: how much of the query is contained in the reference, and the reverse); not with -s\n"
+            "  --abund (scaled runs only): both sides keep how many of their windows hash to each value (-r / -f files are sketched so, with -g\n"
+            "  summed over a file's records; -R / -Q files must come from `rkmh sketch --scaled <m> --abund`); a line keeps its six columns and\n"
+            "  gains three: the angular similarity of the two abundance vectors, 1 - 2 acos(cosine) / pi (1: the same proportions, 0: nothing\n"
+            "  shared), wq_in/wq_total (the query's windows whose hash the reference holds / all windows the query kept) and wr_in/wr_total\n"
+            "  (the same for the reference); -d still filters on the distance column\n"
             "  -g: one sketch per input FILE, as Mash sketches an assembly;  -d <x>: only pairs at distance <= x;  --device <id>: GPU to use\n" HASH_POLICY_HELP);
 }
-static const CompareRules dist_rules = {"dist", "a distance", nullptr, false, "more than 2^31-1 sketches on one side"};
+static const CompareRules dist_rules = {"dist", "a distance", nullptr, false, "more than 2^31-1 sketches on one side", true};
 static int dist_scaled(const CompareInputs& in, const LoadedSides& ld, int k, double max_dist) {
     ScaledRun run;
     start_scaled_run(in, dist_rules, ld, k, run);
     const ScaledSet &q = *run.queries, &sr = run.refs;
     const size_t nq = q.names.size(), nr = sr.names.size();
     if (nq > 0x7fffffffull || nr > 0x7fffffffull) refuse(dist_rules, "more than 2^31-1 sketches on one side");
-    std::vector<int32_t> shared(nq * nr);
-    CK(rk_compare_scaled(run.ctx, q.values.data(), q.off.data(), (int)nq, sr.values.data(), sr.off.data(), (int)nr, 0, shared.data()));
+    std::vector<int32_t> shared(in.abund ? 0 : nq * nr);
+    std::vector<uint64_t> out4(in.abund ? nq * nr * 4 : 0), qsums, rsums; // --abund: the four sums of every pair, (sum, sumsq) of every sketch
+    if (in.abund) {
+        CK(rk_compare_scaled_abund(run.ctx, q.values.data(), q.abund.data(), q.off.data(), (int)nq, sr.values.data(), sr.abund.data(), sr.off.data(), (int)nr, 0, out4.data()));
+        rsums.resize(nr * 2);
+        CK(rk_abund_row_sums(run.ctx, sr.abund.data(), sr.off.data(), (int)nr, rsums.data()));
+        if (&q != &sr) {
+            qsums.resize(nq * 2);
+            CK(rk_abund_row_sums(run.ctx, q.abund.data(), q.off.data(), (int)nq, qsums.data()));
+        }
+    } else
+        CK(rk_compare_scaled(run.ctx, q.values.data(), q.off.data(), (int)nq, sr.values.data(), sr.off.data(), (int)nr, 0, shared.data()));
+    const std::vector<uint64_t>& qs = &q != &sr ? qsums : rsums;
     OutBuf o(stdout);
     for (size_t i = 0; i < nq; ++i)
         for (size_t j = 0; j < nr; ++j) {
-            const long long sh = shared[i * nr + j], lq = (long long)(q.off[i + 1] - q.off[i]), lr = (long long)(sr.off[j + 1] - sr.off[j]);
+            const uint64_t* w = in.abund ? &out4[(i * nr + j) * 4] : nullptr;
+            const long long sh = w ? (long long)w[0] : shared[i * nr + j], lq = (long long)(q.off[i + 1] - q.off[i]), lr = (long long)(sr.off[j + 1] - sr.off[j]);
             double jac = 0, d = 1;
             CK(rk_scaled_distance(sh, lq, lr, k, &jac, &d));
             if (d > max_dist) continue;
             o.append(sr.names[j]); o.append("\t"); o.append(q.names[i]);
-            o.appendf("\t%.6g\t%lld/%lld\t%lld/%lld\t%lld/%lld\n", d, sh, lq + lr - sh, sh, lq, sh, lr);
+            o.appendf("\t%.6g\t%lld/%lld\t%lld/%lld\t%lld/%lld", d, sh, lq + lr - sh, sh, lq, sh, lr);
+            if (w) {
+                double angular = 0;
+                CK(rk_angular_similarity(w[1], qs[i * 2 + 1], rsums[j * 2 + 1], nullptr, &angular));
+                o.appendf("\t%.6g\t%llu/%llu\t%llu/%llu", angular, (unsigned long long)w[2], (unsigned long long)qs[i * 2], (unsigned long long)w[3], (unsigned long long)rsums[j * 2]);
+            }
+            o.append("\n");
             o.end_row();
         }
     o.flush();
@@ -175,7 +199,7 @@ int main_dist(int argc, char** argv) {
     CompareInputs in;
     double max_dist = 2.0;
     if (argc <= 2) { help_dist(); exit(1); }
-    static struct option long_options[] = {COMPARE_OPTIONS, {"max-dist", required_argument, 0, 'd'}, {"threads", required_argument, 0, 't'}, {0, 0, 0, 0}};
+    static struct option long_options[] = {COMPARE_OPTIONS, {"max-dist", required_argument, 0, 'd'}, {"threads", required_argument, 0, 't'}, {"abund", no_argument, 0, 1008}, {0, 0, 0, 0}};
     optind = 2;
     int c;
     while ((c = getopt_long(argc, argv, "hgk:f:r:R:Q:s:d:t:", long_options, nullptr)) != -1) {
@@ -183,6 +207,7 @@ int main_dist(int argc, char** argv) {
         switch (c) {
             case 'd': max_dist = atof(optarg); break;
             case 't': break;
+            case 1008: in.abund = true; break;
             default: help_dist(); exit(1);
         }
     }
@@ -190,11 +215,14 @@ int main_dist(int argc, char** argv) {
     ld.k = one_k(in, dist_rules);
     if (in.scaled_given && !in.scaled_ok) refuse(dist_rules, "--scaled takes a number of at least 1");
     if (in.scaled_given && in.S != 0) refuse(dist_rules, "--scaled and -s are two kinds of sketch; give one of them");
+    if (in.abund && in.S != 0) refuse(dist_rules, "--abund compares scaled sketches (--scaled <n>, or files of `rkmh sketch --scaled <n> --abund`); -s makes bottom-s ones, which keep no abundances");
     if (in.S != 0 && (in.S < 1 || in.S > RK_MAX_SKETCH)) refuse(dist_rules, "sketch size outside 1 .. " + std::to_string(RK_MAX_SKETCH));
     if (in.ref_files.empty() == in.ref_json.empty()) refuse(dist_rules, "references come from -r <fasta> ... or from -R <sketches.json> ..., one of the two");
     if (!in.query_files.empty() && !in.query_json.empty()) refuse(dist_rules, "queries come from -f <fasta|fastq> ... or from -Q <sketches.json> ..., not both");
     if (in.whole_files && in.ref_files.empty() && in.query_files.empty()) refuse(dist_rules, "-g says how -r / -f files are sketched; sketches loaded with -R / -Q are what they are");
     load_sketch_files(in, dist_rules, ld);
+    if (in.abund && !in.scaled_given && ld.largest_scaled == 0)
+        refuse(dist_rules, "--abund compares scaled sketches: give --scaled <n>, or -R / -Q files of `rkmh sketch --scaled <n> --abund`");
     const int k = run_k(dist_rules, ld.k);
     return in.scaled_given || ld.largest_scaled ? dist_scaled(in, ld, k, max_dist) : dist_bottom(in, ld, k, max_dist);
 }

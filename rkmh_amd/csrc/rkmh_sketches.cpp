@@ -182,6 +182,7 @@ void load_sketch_files(const CompareInputs& in, const CompareRules& rules, Loade
             if (L.ks.size() != 1) refuse(rules, p + " holds sketches of " + std::to_string(L.ks.size()) + " k-mer sizes; " + rules.noun + " needs one");
             if (ld.k != 0 && L.ks[0] != ld.k) refuse(rules, p + " holds sketches of k = " + std::to_string(L.ks[0]) + ", the others (or -k) say " + std::to_string(ld.k));
             if (!L.scaled && rules.no_bottom) refuse(rules, p + " holds bottom-s sketches; " + rules.no_bottom);
+            if (!L.scaled && in.abund) refuse(rules, p + " holds bottom-s sketches, which keep no abundances; --abund needs sketches of `rkmh sketch --scaled <n> --abund`");
             if (!L.scaled) any_bottom = true;
             if ((L.scaled || ld.largest_scaled) && any_bottom) refuse(rules, p + ": scaled and bottom-s sketches cannot be compared with each other");
             ld.k = L.ks[0];
@@ -189,7 +190,7 @@ void load_sketch_files(const CompareInputs& in, const CompareRules& rules, Loade
                 if (ld.S != 0) refuse(rules, p + " holds scaled sketches (scaled = " + std::to_string(L.scaled) + "); -s is for bottom-s sketches");
                 if (in.scaled_given && L.scaled > in.scaled)
                     refuse(rules, p + " holds sketches of scaled = " + std::to_string(L.scaled) + ": they cannot be made finer, --scaled must be at least that");
-                if (need_abund && !L.has_abund) refuse(rules, p + " holds no abundances; --abund needs query sketches of `rkmh sketch --scaled <n> --abund`");
+                if (need_abund && !L.has_abund) refuse(rules, p + " holds no abundances; --abund needs " + (rules.abund_both_sides ? "" : "query ") + "sketches of `rkmh sketch --scaled <n> --abund`");
                 ld.largest_scaled = std::max(ld.largest_scaled, L.scaled);
                 sc_into.push_back(std::move(L));
                 continue;
@@ -203,7 +204,7 @@ void load_sketch_files(const CompareInputs& in, const CompareRules& rules, Loade
         }
     };
     ld.S = in.S;
-    load(in.ref_json, ld.refs, ld.sc_refs, false);
+    load(in.ref_json, ld.refs, ld.sc_refs, in.abund && rules.abund_both_sides);
     load(in.query_json, ld.queries, ld.sc_queries, in.abund);
 }
 
@@ -222,7 +223,8 @@ void start_scaled_run(const CompareInputs& in, const CompareRules& rules, const 
     uint64_t max_hash = 0;
     CK(rk_scaled_max_hash(in.scaled_given ? in.scaled : ld.largest_scaled, &max_hash));
     ScaledSet &sr = run.refs, &sq = run.own_queries;
-    sq.with_abund = in.abund; // (the references' abundances play no part)
+    sq.with_abund = in.abund;
+    sr.with_abund = in.abund && rules.abund_both_sides; // (gather: the references' abundances play no part)
     cut_scaled_files(ld.sc_refs, max_hash, sr);
     cut_scaled_files(ld.sc_queries, max_hash, sq);
     if (in.ref_files.empty() && sr.names.empty()) refuse(rules, "no reference sketches");

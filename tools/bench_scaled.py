@@ -4,6 +4,8 @@ plain two-pointer loop on 16 host threads (GPU box).
 
     g++ -O3 -fopenmp -o tools/ubench/scaled_cpu tools/ubench/scaled_cpu.cpp      (built on first use when missing)
     python tools/bench_scaled.py [--n 2048] [--sizes 800,5000] [--runs 7] [--threads 16] [--cpu-runs 5]
+    python tools/bench_scaled.py --abund [--n 2048] [--sizes 800,5000] [--runs 7] [--threads 16] [--cpu-runs 5]
+                                               (the weighted form, k_scaled_pairs_w, next to the plain launch at the same `lanes`; see below)
     python tools/bench_scaled.py --keep        (the keep step of the general path next to the hashing: RKMH_INDEX_TIMING lines on stderr)
     python tools/bench_scaled.py --keep [--abund] [--root <tree>]     (the same with abundances; --root: the tree whose package and library
                                                are loaded, this one by default -- for comparing two builds in one job)
@@ -13,7 +15,14 @@ genome at scaled 10; 5 000: a bacterial genome at scaled 1000.  Device: the resi
 torch's stream, timed with device events around one launch: two warm-up launches, then the median of --runs, at lanes = 1, 8, 64 and
 0 (automatic).  Host: tools/ubench/scaled_cpu on --threads OpenMP threads, median of --cpu-runs, same box, same job.  All answers must
 be equal.  Prints one JSON line per size; fails when the automatic choice does not beat the host threads, or is slower than the best
-forced `lanes` by more than the spread (max - min) of that one's runs."""
+forced `lanes` by more than the spread (max - min) of that one's runs.
+
+--abund: the same sets with abundances of 1 .. 500.  Per `lanes` value the weighted launch (rk_compare_scaled_abund_device) and the plain
+one (rk_compare_scaled_device) are timed one after the other in the same way, in the same job; the host baseline is
+rk_compare_scaled_abund_host on --threads threads (host clock, median of --cpu-runs).  All weighted answers must be equal to the
+host's, and their `shared` to the plain launch's.  Prints one JSON line per size with the ratio weighted / plain per `lanes`; fails
+when the automatic choice does not beat the host median by more than the larger of the two spreads.  Whether lanes = 0 is still the
+best choice for the weighted kernel is reported (auto_over_best, best_spread_seconds), not enforced."""
 import argparse
 import json
 import os
@@ -103,6 +112,82 @@ def bench_pairs(o):
         sys.exit("; ".join(failures))
 
 
+def _timed(launch, st, runs):
+    import torch
+    for _ in range(2):
+        launch()
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(max(5, runs)):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(st)
+        launch()
+        e1.record(st)
+        e1.synchronize()
+        times.append(e0.elapsed_time(e1) * 1e-3)
+    times.sort()
+    torch.cuda.synchronize()
+    return dict(median=times[len(times) // 2], min=times[0], max=times[-1], runs=len(times))
+
+
+def bench_pairs_abund(o):
+    import time
+    import torch
+    import rkmh_amd
+    from rkmh_amd import api
+    ctx = rkmh_amd.Context(0)      # no GPU: this raises, nothing is timed
+    n, failures = o.n, []
+    for size in [int(x) for x in o.sizes.split(",")]:
+        av, ao, bv, bo = make_input(n, size)
+        rng = np.random.default_rng(2)
+        aw, bw = (rng.integers(1, 501, size=len(x), dtype=np.uint32) for x in (av, bv))
+        d_av, d_ao, d_bv, d_bo = (torch.from_numpy(x.view(np.int64)).cuda() for x in (av, ao, bv, bo))
+        d_aw, d_bw = (torch.from_numpy(x.view(np.int32)).cuda() for x in (aw, bw))
+        d_out4 = torch.empty((n, n, 4), dtype=torch.int64, device="cuda")
+        d_out = torch.empty((n, n), dtype=torch.int32, device="cuda")
+        st = torch.cuda.Stream()
+        cpu_times, want = [], None
+        for _ in range(max(3, o.cpu_runs)):
+            t0 = time.perf_counter()
+            want = api.compare_scaled_abund_host(av, aw, ao, bv, bw, bo, threads=o.threads)
+            cpu_times.append(time.perf_counter() - t0)
+        cpu_times.sort()
+        cpu = dict(median=cpu_times[len(cpu_times) // 2], min=cpu_times[0], max=cpu_times[-1], runs=len(cpu_times))
+        res_w, res_p, equal = {}, {}, True
+        for lanes in (1, 8, 64, 0):
+            def weighted():
+                ctx.compare_scaled_abund_device(d_av.data_ptr(), d_aw.data_ptr(), d_ao.data_ptr(), n, len(av), d_bv.data_ptr(), d_bw.data_ptr(), d_bo.data_ptr(),
+                                                n, len(bv), d_out4.data_ptr(), lanes=lanes, stream=st.cuda_stream)
+
+            def plain():
+                ctx.compare_scaled_device(d_av.data_ptr(), d_ao.data_ptr(), n, len(av), d_bv.data_ptr(), d_bo.data_ptr(), n, len(bv), d_out.data_ptr(),
+                                          lanes=lanes, stream=st.cuda_stream)
+            d_out4.fill_(-1)
+            d_out.fill_(-1)
+            torch.cuda.synchronize()
+            res_w[lanes] = _timed(weighted, st, o.runs)
+            res_p[lanes] = _timed(plain, st, o.runs)
+            got = d_out4.cpu().numpy().view(np.uint64)
+            equal = equal and bool((got == want).all()) and bool((d_out.cpu().numpy().astype(np.uint64) == want[:, :, 0]).all())
+        best = min((1, 8, 64), key=lambda l: res_w[l]["median"])
+        auto, spread = res_w[0]["median"], res_w[best]["max"] - res_w[best]["min"]
+        margin = max(cpu["max"] - cpu["min"], res_w[0]["max"] - res_w[0]["min"])
+        print(json.dumps({"bench": "scaled_pairs_abund", "n": n, "size": size, "pairs": n * n, "weighted_seconds": {str(l): res_w[l] for l in res_w},
+                          "plain_seconds": {str(l): res_p[l] for l in res_p}, "weighted_over_plain": {str(l): res_w[l]["median"] / res_p[l]["median"] for l in res_w},
+                          "best_forced_lanes": best, "auto_seconds_median": auto, "auto_over_best": auto / res_w[best]["median"], "best_spread_seconds": spread,
+                          "auto_within_best_spread": bool(auto <= res_w[best]["median"] + spread), "auto_pairs_per_second": n * n / auto,
+                          "auto_row_bytes_per_second": n * n * 2 * size * 8 / auto, "auto_stored_bytes_per_second": n * n * 32 / auto,
+                          "cpu_threads": o.threads, "cpu_seconds": cpu, "cpu_over_auto": cpu["median"] / auto, "larger_spread_seconds": margin, "equal": equal,
+                          "shared_mean": float(want[:, :, 0].mean()), "dot_mean": float(want[:, :, 1].mean())}), flush=True)
+        if not equal:
+            failures.append("size %d: device and host answers differ" % size)
+        if not cpu["median"] - auto > margin:
+            failures.append("size %d: the automatic choice does not beat %d host threads by more than the larger spread" % (size, o.threads))
+    ctx.close()
+    if failures:
+        sys.exit("; ".join(failures))
+
+
 def bench_keep(abund):
     os.environ["RKMH_INDEX_TIMING"] = "1"      # read once, at the first batch of the general path
     import rkmh_amd
@@ -139,6 +224,8 @@ def main():
     sys.path.insert(0, os.path.abspath(o.root))
     if o.keep:
         bench_keep(o.abund)
+    elif o.abund:
+        bench_pairs_abund(o)
     else:
         bench_pairs(o)
 

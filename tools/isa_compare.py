@@ -7,7 +7,8 @@ source can be added with  hipcc --offload-arch=gfx950 -O3 -std=c++17 -save-temps
     git worktree add /tmp/base <commit> && make -C /tmp/base && make
     python tools/isa_compare.py /tmp/base/build build [--all]
 
-For every *gfx950*.s found under both directories: kernels whose instruction streams are identical, identical up to the
+For every *gfx950*.s found under both directories: kernels whose instruction streams are identical (the compiler numbers its branch
+labels by function, `.LBB7_3`: that number is masked, so a kernel added before another one in the file does not change it), identical up to the
 offsets of scalar loads from the kernel-argument segment (an argument struct changed size), or different (with the
 instruction counts, and how many of those differ in scalar code only); and, from the .amdhsa_kernel blocks, every kernel whose VGPR count, SGPR count or scratch bytes moved -- a
 branch that adds no instruction to a path can still cost it registers or a spill.  No GPU needed."""
@@ -34,7 +35,7 @@ def kernels(path):
         t = line.split(";")[0].strip()
         if not t or t.startswith(".") or t.endswith(":"):
             continue
-        body.append(re.sub(r"\s+", " ", t))
+        body.append(re.sub(r"\.LBB\d+_", ".LBB_", re.sub(r"\s+", " ", t)))
     return out
 
 
