@@ -801,6 +801,73 @@ int rk_compare_scaled_abund_host(const uint64_t* a_values, const uint32_t* a_abu
 int rk_abund_row_sums_host(const uint32_t* abund, const uint64_t* offsets, int n, uint64_t* out2);
 int rk_angular_similarity(uint64_t dot, uint64_t sumsq_a, uint64_t sumsq_b, double* cosine, double* angular);
 
+/* ------------------------------------------------------------------------------------------------
+ * SEARCH (`rkmh manysearch`; what the sourmash family calls manysearch: many query sketches against a large collection of reference
+ * sketches, reporting only the pairs that match).  These are this library's own definitions.
+ *   Inputs: a reference batch of scaled sketches in CSR (uint64 values[], uint64 offsets[nref + 1]), every row ascending, distinct and
+ *   non-zero; a query batch of the same form with nq rows; a scalar min_shared >= 1 and an optional int32 q_min[nq].  A NULL q_min:
+ *   every query's threshold is min_shared; otherwise query i's threshold is max(min_shared, q_min[i]).
+ *   Index: for each distinct value over all reference rows, the ascending list of the references that hold it (its posting list):
+ *     keys[nkeys]          ascending distinct uint64
+ *     post_off[nkeys + 1]  uint64; the list of keys[j] is post[post_off[j], post_off[j + 1])
+ *     post[npost]          uint32 reference ids, ascending within a key; npost = the number of reference values
+ *   Answer: an array of hits rk_search_hit = {int32 query, int32 ref, int32 shared}: one hit per pair with shared = |Q_query & R_ref|
+ *   at or above that query's threshold, nothing for any other pair, sorted by (query, ref) ascending.  It follows that with every
+ *   threshold at 1 the hits are exactly the non-zero entries of rk_compare_scaled on the same inputs, in row-major order, with the same
+ *   counts; and that an empty query or an empty reference gives no hit.
+ * rk_scaled_index_create: host arrays; RK_ERR_ARG for NULL, nref < 1, offsets that decrease, a row of 2^31 values or more; RK_ERR_LIMIT
+ * for more than 2^31 - 1 rows or 2^32 - 1 values.  The values are uploaded, the index is built on the device once (a kernel writes the
+ * reference id of every value position, a stable radix sort orders the (value, id) pairs by value, the first of every value is kept
+ * as its key) and stays resident until rk_scaled_index_destroy.  It belongs to the context it was made on and is used with no other;
+ * it may be destroyed before or after it.  Searches on one index take turns (its work buffers are its own).
+ * rk_scaled_index_create_device: resident arrays (nvalues = the number of uint64 behind d_values; they are only read, and not needed
+ * after the call); runs on hip_stream (NULL = HIP's null stream) and SYNCHRONISES it.  Every row is clamped on the device to lie
+ * inside [0, nvalues], as k_scaled_pairs clamps its rows; npost = nvalues; a position no row covers gets the id 2^32 - 1, which no
+ * search counts.  Rows that are not ascending give a meaningless index and nothing worse.
+ * rk_scaled_index_stats: the caller sets out->struct_size as for rk_index_stats; longest_posting = the entries of the longest list.
+ * rk_search_scaled: host arrays; *hits is malloc'd (rk_free; never NULL on success), *nhits the number of hits.
+ * rk_search_scaled_device: resident arrays (q_nvalues = the number of uint64 behind d_q_values; d_q_min NULL or nq int32; d_hits takes
+ * cap_hits hits of 12 bytes, and may be NULL when cap_hits = 0).  Writes the first min(total, cap_hits) hits in order and returns the
+ * total in *nhits.  It runs on hip_stream and SYNCHRONISES it, as rk_gather_scaled_device does: the total is read on the host between
+ * the counting pass and the writing pass.  Query rows are clamped to [0, q_nvalues]; a d_q_min entry below 1 counts as 1 (this entry
+ * cannot check them cheaply); every index is checked before it is used; rows that are not ascending give meaningless hits and nothing
+ * worse.
+ * All entries refuse (RK_ERR_ARG, a size beyond its limit RK_ERR_LIMIT) before anything is launched: NULL, nq < 1, min_shared < 1, a
+ * q_min entry below 1 (host arrays only), more than 2^31 - 1 rows on a side, more than 2^24 - 1 workgroups in one call (nq times the
+ * number of reference blocks: search the queries in several calls), an index of another context.
+ * The kernels (rk_search.hip): k_search_block<EMIT>, one workgroup per (query, block of RK_SEARCH_REF_BLOCK consecutive references)
+ * with the block's int32 counters in LDS; lanes stride the query's values, look each up in keys (at most 32 halvings), narrow its
+ * posting list to the block's ids (two more searches) and add 1 to the counter of every reference in that range (a list of 64
+ * entries or more inside the block is walked by the whole wave).  Integer adds commute: the counts do not depend on the order of
+ * arrival.  Pass 1 stores the number of counters at or above the threshold per workgroup, an exclusive 64-bit scan gives every
+ * workgroup its place, pass 2 recomputes the counters and writes its hits in ascending reference order.  No atomics on global memory.
+ * rk_search_scaled_host: host code, usable without a GPU (rk_scaled_host.cpp): the same array from an index built on the host, on
+ * `threads` host threads (below 1: one); the checks of rk_search_scaled.
+ * rk_search_min_count: host only; *t = the smallest integer t with (double)t / (double)len >= x, the count that a containment
+ * shared / |query| >= x asks of a query of len values (0 for x = 0 or len = 0; never above len).  `rkmh manysearch --min-containment`
+ * passes max(1, t) as q_min.  RK_ERR_ARG for x outside [0, 1] (a NaN included), RK_ERR_LIMIT for len > 2^31 - 1. */
+#define RK_SEARCH_REF_BLOCK 8192 /* references per workgroup of the search kernel: 32 KB of int32 counters in LDS */
+typedef struct rk_search_hit { int32_t query, ref, shared; } rk_search_hit;
+typedef struct rk_scaled_index rk_scaled_index;
+typedef struct rk_scaled_index_stats_t {
+    uint32_t struct_size;
+    uint32_t nref;
+    uint64_t npost, nkeys;
+    uint32_t longest_posting, reserved;
+} rk_scaled_index_stats_t;
+int rk_scaled_index_create(rk_ctx* ctx, const uint64_t* r_values, const uint64_t* r_offsets, int64_t nref, rk_scaled_index** idx);
+int rk_scaled_index_create_device(rk_ctx* ctx, const void* d_values, const void* d_offsets, int64_t nref, uint64_t nvalues, void* hip_stream,
+                                  rk_scaled_index** idx);
+void rk_scaled_index_destroy(rk_scaled_index* idx);
+int rk_scaled_index_stats(const rk_scaled_index* idx, rk_scaled_index_stats_t* out);
+int rk_search_scaled(rk_ctx* ctx, rk_scaled_index* idx, const uint64_t* q_values, const uint64_t* q_offsets, int64_t nq, int min_shared,
+                     const int32_t* q_min, rk_search_hit** hits, uint64_t* nhits);
+int rk_search_scaled_device(rk_ctx* ctx, rk_scaled_index* idx, const void* d_q_values, const void* d_q_offsets, int64_t nq, uint64_t q_nvalues,
+                            int min_shared, const void* d_q_min, void* d_hits, uint64_t cap_hits, uint64_t* nhits, void* hip_stream);
+int rk_search_scaled_host(const uint64_t* r_values, const uint64_t* r_offsets, int64_t nref, const uint64_t* q_values, const uint64_t* q_offsets,
+                          int64_t nq, int min_shared, const int32_t* q_min, int threads, rk_search_hit** hits, uint64_t* nhits);
+int rk_search_min_count(double min_containment, uint64_t len, int32_t* t);
+
 #ifdef __cplusplus
 }
 #endif

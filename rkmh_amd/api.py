@@ -267,6 +267,16 @@ _SIGS = {
     "rk_compare_scaled_abund_host": (C.c_int, [_u64p, _u32p, _u64p, C.c_int, _u64p, _u32p, _u64p, C.c_int, C.c_int, _u64p]),
     "rk_abund_row_sums_host": (C.c_int, [_u32p, _u64p, C.c_int, _u64p]),
     "rk_angular_similarity": (C.c_int, [C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "rk_scaled_index_create": (C.c_int, [C.c_void_p, _u64p, _u64p, C.c_int64, C.POINTER(C.c_void_p)]),
+    "rk_scaled_index_create_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_uint64, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "rk_scaled_index_destroy": (None, [C.c_void_p]),
+    "rk_scaled_index_stats": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "rk_search_scaled": (C.c_int, [C.c_void_p, C.c_void_p, _u64p, _u64p, C.c_int64, C.c_int, _i32p, C.POINTER(_i32p), C.POINTER(C.c_uint64)]),
+    "rk_search_scaled_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p,
+                                          C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p]),
+    "rk_search_scaled_host": (C.c_int, [_u64p, _u64p, C.c_int64, _u64p, _u64p, C.c_int64, C.c_int, _i32p, C.c_int, C.POINTER(_i32p),
+                                        C.POINTER(C.c_uint64)]),
+    "rk_search_min_count": (C.c_int, [C.c_double, C.c_uint64, C.POINTER(C.c_int32)]),
 }
 
 
@@ -1001,6 +1011,103 @@ def gather_scaled_host(q, r_values, r_offsets, min_shared=1, max_rounds=None, th
     return out[: n.value].copy()
 
 
+RK_SEARCH_REF_BLOCK = 8192  # include/rkmh_amd.h: references per workgroup of the search kernel
+
+
+class ScaledIndexStats(C.Structure):
+    """rk_scaled_index_stats_t (rkmh_amd.h, "SEARCH")"""
+    _fields_ = [("struct_size", C.c_uint32), ("nref", C.c_uint32), ("npost", C.c_uint64), ("nkeys", C.c_uint64), ("longest_posting", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+def _q_min(q_min, nq):
+    """the per-query thresholds: None, or int32 [nq]"""
+    if q_min is None:
+        return None
+    q_min = np.ascontiguousarray(q_min, dtype=np.int32)
+    if q_min.ndim != 1 or len(q_min) != nq:
+        raise ValueError("%d thresholds for %d queries" % (q_min.size, nq))
+    return q_min
+
+
+def _hits(lib, out, n):
+    """the malloc'd hits of a search -> int32 [n, 3] (query, reference, shared); releases them"""
+    r = np.ctypeslib.as_array(out, shape=(max(n, 1) * 3,))[: n * 3].copy().reshape(n, 3)
+    lib.rk_free(out)
+    return r
+
+
+def search_scaled_host(r_values, r_offsets, q_values, q_offsets, min_shared=1, q_min=None, threads=1):
+    """rk_search_scaled_host (host code, no GPU): every pair of a CSR query sketch and a CSR reference sketch that shares at least
+    max(min_shared, q_min[query]) values -> int32 [n, 3], rows (query, reference, shared) sorted by (query, reference)."""
+    r_values, r_offsets = _csr(r_values, r_offsets)
+    q_values, q_offsets = _csr(q_values, q_offsets)
+    nq = len(q_offsets) - 1
+    q_min = _q_min(q_min, nq)
+    out, n = _i32p(), C.c_uint64()
+    lib = load_library()
+    _chk(lib.rk_search_scaled_host(_p(r_values, C.c_uint64), _p(r_offsets, C.c_uint64), len(r_offsets) - 1, _p(q_values, C.c_uint64),
+                                   _p(q_offsets, C.c_uint64), nq, int(min_shared), None if q_min is None else _p(q_min, C.c_int32), int(threads),
+                                   C.byref(out), C.byref(n)))
+    return _hits(lib, out, int(n.value))
+
+
+def search_min_count(min_containment, length):
+    """rk_search_min_count (host code, no GPU): the smallest t with t / length >= min_containment, the count `rkmh manysearch
+    --min-containment` asks of a query of `length` values (0 for an empty query)."""
+    t = C.c_int32()
+    _chk(load_library().rk_search_min_count(float(min_containment), C.c_uint64(int(length)), C.byref(t)))
+    return int(t.value)
+
+
+class ScaledIndex:
+    """rk_scaled_index: the resident inverted index of a collection of scaled sketches (Context.scaled_index)."""
+
+    def __init__(self, ctx, handle):
+        self._ctx, self._lib, self._h = ctx, ctx._lib, handle
+
+    def close(self):
+        if self._h:
+            self._lib.rk_scaled_index_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def stats(self):
+        """-> dict(nref, npost, nkeys, longest_posting)"""
+        s = ScaledIndexStats()
+        s.struct_size = C.sizeof(ScaledIndexStats)
+        _chk(self._lib.rk_scaled_index_stats(self._h, C.byref(s)))
+        return dict(nref=int(s.nref), npost=int(s.npost), nkeys=int(s.nkeys), longest_posting=int(s.longest_posting))
+
+    def search(self, q_values, q_offsets, min_shared=1, q_min=None):
+        """rk_search_scaled: the CSR query sketches against the index -> int32 [n, 3], rows (query, reference, shared) of every pair
+        that shares at least max(min_shared, q_min[query]) values, sorted by (query, reference)."""
+        q_values, q_offsets = _csr(q_values, q_offsets)
+        nq = len(q_offsets) - 1
+        q_min = _q_min(q_min, nq)
+        out, n = _i32p(), C.c_uint64()
+        _chk(self._lib.rk_search_scaled(self._ctx._h, self._h, _p(q_values, C.c_uint64), _p(q_offsets, C.c_uint64), nq, int(min_shared),
+                                        None if q_min is None else _p(q_min, C.c_int32), C.byref(out), C.byref(n)))
+        return _hits(self._lib, out, int(n.value))
+
+    def search_device(self, d_q_values_ptr, d_q_offsets_ptr, nq, q_nvalues, d_hits_ptr, cap_hits, min_shared=1, d_q_min_ptr=None, stream=None):
+        """Resident CSR queries (raw device pointers; d_q_min: nq int32 or None; d_hits: cap_hits rows of 3 int32) -> the total number
+        of hits; the first min(total, cap_hits) are written, in order.  Runs on `stream` (as for compare_sketches_device) and
+        synchronises it.  Query rows are clamped to [0, q_nvalues] on the device."""
+        if stream is None:
+            stream = self._ctx.stream
+        n = C.c_uint64()
+        _chk(self._lib.rk_search_scaled_device(self._ctx._h, self._h, C.c_void_p(d_q_values_ptr), C.c_void_p(d_q_offsets_ptr), int(nq),
+                                               C.c_uint64(int(q_nvalues)), int(min_shared), C.c_void_p(d_q_min_ptr), C.c_void_p(d_hits_ptr),
+                                               C.c_uint64(int(cap_hits)), C.byref(n), C.c_void_p(stream)))
+        return int(n.value)
+
+
 def _abund(abund, values):
     """the abundances that lie parallel to `values`: uint32, one per value"""
     abund = np.ascontiguousarray(abund, dtype=np.uint32)
@@ -1296,6 +1403,25 @@ class Context:
             stream = self.stream
         _chk(self._lib.rk_abund_row_sums_device(self._h, C.c_void_p(d_abund_ptr), C.c_void_p(d_offsets_ptr), n, C.c_uint64(int(nvalues)),
                                                 C.c_void_p(d_out2_ptr), C.c_void_p(stream)))
+
+    # ---- search ----------------------------------------------------------------------------------
+    def scaled_index(self, r_values, r_offsets):
+        """rk_scaled_index_create: the inverted index of the CSR reference sketches, built on the device and resident until its
+        close() -> ScaledIndex (stats, search, search_device)."""
+        r_values, r_offsets = _csr(r_values, r_offsets)
+        h = C.c_void_p()
+        _chk(self._lib.rk_scaled_index_create(self._h, _p(r_values, C.c_uint64), _p(r_offsets, C.c_uint64), len(r_offsets) - 1, C.byref(h)))
+        return ScaledIndex(self, h)
+
+    def scaled_index_device(self, d_values_ptr, d_offsets_ptr, nref, nvalues, stream=None):
+        """rk_scaled_index_create_device: the index of resident CSR reference sketches (raw device pointers, only read); rows are
+        clamped to [0, nvalues] on the device.  Runs on `stream` and synchronises it."""
+        if stream is None:
+            stream = self.stream
+        h = C.c_void_p()
+        _chk(self._lib.rk_scaled_index_create_device(self._h, C.c_void_p(d_values_ptr), C.c_void_p(d_offsets_ptr), int(nref), C.c_uint64(int(nvalues)),
+                                                     C.c_void_p(stream), C.byref(h)))
+        return ScaledIndex(self, h)
 
     # ---- gather ----------------------------------------------------------------------------------
     def gather_scaled(self, q, r_values, r_offsets, min_shared=1, max_rounds=None):

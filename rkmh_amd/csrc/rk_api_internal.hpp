@@ -10,6 +10,7 @@
 //   rk_pairs.hip     all-pairs comparison of bottom-S sketches
 //   rk_scaled.hip    scaled sketches: the keep step of the general path, all-pairs intersection of variable-length sets
 //   rk_gather.hip    gather: the greedy decomposition of a scaled sketch into reference sketches, its state resident across rounds
+//   rk_search.hip    search: the resident inverted index of scaled sketches (value -> references) and the thresholded search on it
 #pragma once
 #include "../../include/rkmh_amd.h"
 #include "rk_kernels.hpp"

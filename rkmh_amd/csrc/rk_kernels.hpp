@@ -185,6 +185,10 @@ hipError_t launch_fastq_first_start(const uint8_t* text, uint32_t n, uint32_t fr
 // whole-array ascending sort of u64 keys in place (rk_sort.hip: rocPRIM radix sort); tmp holds sort_u64_temp_bytes(n) bytes
 hipError_t sort_u64_temp_bytes(uint64_t n, size_t* bytes);
 hipError_t launch_sort_u64(uint64_t* keys, uint64_t n, void* tmp, size_t tmp_bytes, hipStream_t st);
+// stable sort of (u64 key, u32 payload) pairs by key into keys_out / vals_out (rk_sort.hip); tmp holds sort_pairs_u64_u32_temp_bytes(n) bytes
+hipError_t sort_pairs_u64_u32_temp_bytes(uint64_t n, size_t* bytes);
+hipError_t launch_sort_pairs_u64_u32(const uint64_t* keys_in, uint64_t* keys_out, const uint32_t* vals_in, uint32_t* vals_out, uint64_t n, void* tmp,
+                                     size_t tmp_bytes, hipStream_t st);
 // bits[s / 32] bit (s % 32) = the count of slot s passes mask_by_frequency's threshold (one streaming pass over the table)
 hipError_t launch_keep_bits(const int32_t* counter, uint64_t slots, int min_occ, const DevPolicy& pol, uint32_t* bits, hipStream_t st);
 // -M with a bounded min_num: keep bit per index key, the masked copy of the exact k-mer map, min(min_num, bound) per read

@@ -1,6 +1,6 @@
 // rk_scaled_host.cpp -- the host half of scaled (FracMinHash) sketches (include/rkmh_amd.h, "SCALED SKETCHES"): the threshold of a
 // `scaled` value, the union of sketches (what `-g` reduces the records of a file with, and what cuts a sketch down to a larger
-// `scaled`), the host forms of gather and of the weighted comparison, and the places where counts become floating point.  Host code
+// `scaled`), the host forms of gather, of search and of the weighted comparison, and the places where counts become floating point.  Host code
 // only, usable without a GPU; the kernels are rk_scaled.hip.
 #include <algorithm>
 #include <cmath>
@@ -178,6 +178,90 @@ extern "C" int rk_gather_scaled_abund_host(const uint64_t* q, const uint32_t* q_
         for (uint64_t i = 0; i < nq; ++i)
             if (q_abund[i] == 0) return bad(who + ": abundance 0 at query value " + std::to_string(i));
     return gather_host(who, q, q_abund, nq, rv, roff, nref, min_shared, max_rounds, threads, out4, wunique, nrounds);
+}
+
+// ---- search on the host (include/rkmh_amd.h, "SEARCH"): the inverted index of rk_search.hip from a stable sort of (value, reference)
+// pairs, then per query one counter per reference, the touched ones read out in ascending order.  Host memory: the index, one counter
+// array per thread and the hits -- never nq x nref.
+extern "C" int rk_search_scaled_host(const uint64_t* rv, const uint64_t* roff, int64_t nref, const uint64_t* qv, const uint64_t* qoff, int64_t nq,
+                                     int min_shared, const int32_t* q_min, int threads, rk_search_hit** hits, uint64_t* nhits) {
+    const std::string who = "rk_search_scaled_host";
+    if (!roff || !qoff || !hits || !nhits) return bad(who + ": bad arguments");
+    if (nref < 1 || nq < 1) return bad(who + ": need at least one sketch on each side");
+    if (min_shared < 1) return bad(who + ": min_shared must be at least 1");
+    if (nref > 0x7fffffffll || nq > 0x7fffffffll) { rk__set_error((who + ": more than 2^31-1 sketches on one side").c_str()); return RK_ERR_LIMIT; }
+    for (int side = 0; side < 2; ++side) {
+        const uint64_t* off = side ? qoff : roff;
+        const char* name = side ? "the queries" : "the references";
+        for (int64_t i = 0; i < (side ? nq : nref); ++i) {
+            if (off[i + 1] < off[i]) return bad(who + ": offsets of " + name + " decrease at sketch " + std::to_string(i));
+            if (off[i + 1] - off[i] > 0x7fffffffull) return bad(who + ": sketch " + std::to_string(i) + " of " + name + " holds 2^31 values or more");
+        }
+    }
+    if ((roff[nref] > roff[0] && !rv) || (qoff[nq] > qoff[0] && !qv)) return bad(who + ": values are NULL");
+    if (q_min)
+        for (int64_t i = 0; i < nq; ++i)
+            if (q_min[i] < 1) return bad(who + ": q_min of query " + std::to_string(i) + " is below 1");
+    // the index: pairs ordered by value, the references of one value ascending (they are pushed in reference order; the sort is stable)
+    std::vector<std::pair<uint64_t, uint32_t>> pairs;
+    pairs.reserve((size_t)(roff[nref] - roff[0]));
+    for (int64_t r = 0; r < nref; ++r)
+        for (uint64_t t = roff[r]; t < roff[r + 1]; ++t) pairs.emplace_back(rv[t], (uint32_t)r);
+    std::stable_sort(pairs.begin(), pairs.end(), [](const std::pair<uint64_t, uint32_t>& a, const std::pair<uint64_t, uint32_t>& b) { return a.first < b.first; });
+    std::vector<uint64_t> keys, post_off;
+    for (size_t t = 0; t < pairs.size(); ++t)
+        if (t == 0 || pairs[t - 1].first != pairs[t].first) { keys.push_back(pairs[t].first); post_off.push_back(t); }
+    post_off.push_back(pairs.size());
+    std::vector<std::vector<rk_search_hit>> per_query((size_t)nq);
+    on_threads((size_t)nq, threads, 1, [&](size_t lo, size_t hi) {
+        std::vector<int32_t> count((size_t)nref, 0);
+        std::vector<uint32_t> touched;
+        for (size_t q = lo; q < hi; ++q) {
+            const int32_t thr = q_min ? std::max(min_shared, q_min[q]) : min_shared;
+            touched.clear();
+            for (uint64_t t = qoff[q]; t < qoff[q + 1]; ++t) {
+                const size_t j = (size_t)(std::lower_bound(keys.begin(), keys.end(), qv[t]) - keys.begin());
+                if (j == keys.size() || keys[j] != qv[t]) continue;
+                for (uint64_t p = post_off[j]; p < post_off[j + 1]; ++p) {
+                    const uint32_t r = pairs[(size_t)p].second;
+                    if (count[r]++ == 0) touched.push_back(r);
+                }
+            }
+            std::sort(touched.begin(), touched.end());
+            for (uint32_t r : touched) {
+                if (count[r] >= thr) per_query[q].push_back({(int32_t)q, (int32_t)r, count[r]});
+                count[r] = 0;
+            }
+        }
+    });
+    size_t total = 0;
+    for (const auto& h : per_query) total += h.size();
+    rk_search_hit* out = (rk_search_hit*)malloc(sizeof(rk_search_hit) * (total ? total : 1));
+    if (!out) { rk__set_error((who + ": malloc").c_str()); return RK_ERR_NOMEM; }
+    size_t at = 0;
+    for (const auto& h : per_query) {
+        if (!h.empty()) memcpy(out + at, h.data(), h.size() * sizeof(rk_search_hit));
+        at += h.size();
+    }
+    *hits = out;
+    *nhits = (uint64_t)total;
+    return RK_OK;
+}
+
+// *t = the smallest integer t with (double)t / (double)len >= x: what a containment of at least x asks a query of len values to share.
+// 0 for x = 0 or an empty query; never above len.
+extern "C" int rk_search_min_count(double x, uint64_t len, int32_t* t) {
+    if (!t) return bad("rk_search_min_count: t is NULL");
+    if (!(x >= 0.0 && x <= 1.0)) return bad("rk_search_min_count: the containment must lie in [0, 1]");
+    if (len > 0x7fffffffull) { rk__set_error("rk_search_min_count: a query of more than 2^31-1 values"); return RK_ERR_LIMIT; }
+    int64_t n = 0;
+    if (len) {
+        n = (int64_t)((double)len * x); // near the answer; the two loops settle it by the definition
+        while (n > 0 && (double)(n - 1) / (double)len >= x) --n;
+        while ((double)n / (double)len < x) ++n;
+    }
+    *t = (int32_t)n;
+    return RK_OK;
 }
 
 // ---- weighted comparison on the host (include/rkmh_amd.h, "WEIGHTED COMPARISON"): the sums of k_scaled_pairs_w and k_abund_row_sums

@@ -34,4 +34,22 @@ hipError_t launch_sort_u64(uint64_t* keys, uint64_t n, void* tmp, size_t tmp_byt
     return e;
 }
 
+// ---- pairs: (uint64 key, uint32 payload) sorted by key, for the inverted index of scaled sketches (rk_search.hip).  LSD radix sort is
+// stable: payloads of equal keys keep the order they came in.  The inputs are left as they are.
+hipError_t sort_pairs_u64_u32_temp_bytes(uint64_t n, size_t* bytes) {
+    size_t tb = 0;
+    hipError_t e = hipcub::DeviceRadixSort::SortPairs(nullptr, tb, (const uint64_t*)nullptr, (uint64_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr,
+                                                      (size_t)n, 0, 64, nullptr);
+    if (e != hipSuccess) return e;
+    *bytes = tb + 256;
+    return hipSuccess;
+}
+
+// keys_out[0, n), vals_out[0, n) = the pairs of keys_in, vals_in ascending by key; tmp holds sort_pairs_u64_u32_temp_bytes(n) bytes
+hipError_t launch_sort_pairs_u64_u32(const uint64_t* keys_in, uint64_t* keys_out, const uint32_t* vals_in, uint32_t* vals_out, uint64_t n, void* tmp,
+                                     size_t tmp_bytes, hipStream_t st) {
+    if (n == 0) return hipSuccess;
+    return hipcub::DeviceRadixSort::SortPairs(tmp, tmp_bytes, keys_in, keys_out, vals_in, vals_out, (size_t)n, 0, 64, st);
+}
+
 } // namespace rk

@@ -1,4 +1,5 @@
-// rkmh_compare.cpp -- the commands on sketch sets (rkmh_sketches.cpp): sketch writes them, dist compares all pairs, gather decomposes.
+// rkmh_compare.cpp -- the commands on sketch sets (rkmh_sketches.cpp): sketch writes them, dist compares all pairs, gather decomposes,
+// manysearch reports the pairs that match.
 #include <algorithm>
 
 #include "rkmh_cli.hpp"
@@ -123,6 +124,11 @@ static void help_dist() {
             "  (the same for the reference); -d still filters on the distance column\n"
             "  -g: one sketch per input FILE, as Mash sketches an assembly;  -d <x>: only pairs at distance <= x;  --device <id>: GPU to use\n" HASH_POLICY_HELP);
 }
+// the six columns of a pair of scaled sketches, without the end of the line: dist --scaled and manysearch print a pair alike
+static void append_scaled_pair(OutBuf& o, const std::string& ref, const std::string& query, double d, long long sh, long long lq, long long lr) {
+    o.append(ref); o.append("\t"); o.append(query);
+    o.appendf("\t%.6g\t%lld/%lld\t%lld/%lld\t%lld/%lld", d, sh, lq + lr - sh, sh, lq, sh, lr);
+}
 static const CompareRules dist_rules = {"dist", "a distance", nullptr, false, "more than 2^31-1 sketches on one side", true};
 static int dist_scaled(const CompareInputs& in, const LoadedSides& ld, int k, double max_dist) {
     ScaledRun run;
@@ -151,8 +157,7 @@ static int dist_scaled(const CompareInputs& in, const LoadedSides& ld, int k, do
             double jac = 0, d = 1;
             CK(rk_scaled_distance(sh, lq, lr, k, &jac, &d));
             if (d > max_dist) continue;
-            o.append(sr.names[j]); o.append("\t"); o.append(q.names[i]);
-            o.appendf("\t%.6g\t%lld/%lld\t%lld/%lld\t%lld/%lld", d, sh, lq + lr - sh, sh, lq, sh, lr);
+            append_scaled_pair(o, sr.names[j], q.names[i], d, sh, lq, lr);
             if (w) {
                 double angular = 0;
                 CK(rk_angular_similarity(w[1], qs[i * 2 + 1], rsums[j * 2 + 1], nullptr, &angular));
@@ -336,5 +341,101 @@ int main_gather(int argc, char** argv) {
     fflush(stdout);
     for (void* p : {d_rv, d_ro, d_q, d_out, d_qa, d_wu}) if (p) rk_device_free(ctx, p);
     rk_ctx_destroy(ctx);
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------
+// manysearch: many queries against a collection of references, only the pairs that match (include/rkmh_amd.h, "SEARCH").  Both sides
+// are scaled sketches, made or loaded as `dist --scaled` makes and loads them; the references become a resident inverted index once
+// (rk_scaled_index_create), the queries are searched against it in one call (rk_search_scaled).  Host memory is the two sides and
+// the hits, never queries x references.  Everything that can be refused is refused before a context exists.
+static void help_manysearch() {
+    fprintf(stderr,
+            "rkmh manysearch (-r <refs.fa> ... | -R <refs.json> ...) (-f <queries.fa|fq> ... | -Q <queries.json> ...) [-k <k>] [--scaled <n>] [-g]\n"
+            "                [--min-shared <n>] [--min-containment <x>] [--device <id>]\n"
+            "  searches every query sketch against every reference sketch through an inverted index of the references (hash -> the references\n"
+            "  that hold it) and prints only the pairs that match: one line per pair that shares at least --min-shared hashes (default 1),\n"
+            "  query by query, references in input order, in the six columns of `dist --scaled`: reference, query, distance from\n"
+            "  shared/union, shared/union, shared/|query|, shared/|reference|; a line is the line `dist --scaled` prints for that pair\n"
+            "  --min-containment <x> (0 .. 1, default 0): only pairs with shared/|query| >= x as well: the query's threshold is the larger of\n"
+            "  --min-shared and the smallest count t with t / |query| >= x; an empty query matches nothing\n"
+            "  -r: one reference per record, with -g one per FILE;  -f: one query per record, with -g one per FILE; without -f / -Q the\n"
+            "  references are searched against themselves;  -R / -Q: scaled sketches written by `rkmh sketch --scaled <m>`\n"
+            "  --scaled <n>: -r / -f files are sketched at n, -R / -Q files (m <= n) are cut down to n; without it: the largest m among the\n"
+            "  files; not with -s (bottom-s sketches) and not with --abund (abundances play no part in a search)\n" HASH_POLICY_HELP);
+}
+static const CompareRules manysearch_rules = {"manysearch", "manysearch", "manysearch searches scaled ones (rkmh sketch --scaled)", false,
+                                              "more than 2^31-1 sketches on one side"};
+int main_manysearch(int argc, char** argv) {
+    CompareInputs in;
+    int min_shared = 1;
+    bool min_ok = true, cont_ok = true, abund = false;
+    double min_cont = 0.0;
+    if (argc <= 2) { help_manysearch(); exit(1); }
+    static struct option long_options[] = {COMPARE_OPTIONS, {"min-shared", required_argument, 0, 1006}, {"abund", no_argument, 0, 1008},
+                                           {"min-containment", required_argument, 0, 1009}, {0, 0, 0, 0}};
+    optind = 2;
+    int c;
+    while ((c = getopt_long(argc, argv, "hgk:f:r:R:Q:s:", long_options, nullptr)) != -1) {
+        if (shared_option(c, in)) continue;
+        switch (c) {
+            case 1006: min_ok = parse_at_least_1(optarg, min_shared); break;
+            case 1008: abund = true; break;
+            case 1009: {
+                char* e = nullptr;
+                min_cont = strtod(optarg, &e);
+                cont_ok = e != optarg && *e == 0 && min_cont >= 0.0 && min_cont <= 1.0; // (a NaN fails both comparisons)
+                break;
+            }
+            default: help_manysearch(); exit(1);
+        }
+    }
+    LoadedSides ld;
+    ld.k = one_k(in, manysearch_rules);
+    if (in.S != 0) refuse(manysearch_rules, "-s makes bottom-s sketches; manysearch works on scaled ones (--scaled)");
+    if (abund) refuse(manysearch_rules, "--abund has no meaning here: a search counts shared hashes, abundances play no part");
+    if (in.scaled_given && !in.scaled_ok) refuse(manysearch_rules, "--scaled takes a number of at least 1");
+    if (!min_ok) refuse(manysearch_rules, "--min-shared takes a number of at least 1");
+    if (!cont_ok) refuse(manysearch_rules, "--min-containment takes a number from 0 to 1");
+    if (in.ref_files.empty() == in.ref_json.empty()) refuse(manysearch_rules, "references come from -r <fasta> ... or from -R <sketches.json> ..., one of the two");
+    if (!in.query_files.empty() && !in.query_json.empty()) refuse(manysearch_rules, "queries come from -f <fasta|fastq> ... or from -Q <sketches.json> ..., not both");
+    if (in.whole_files && in.ref_files.empty() && in.query_files.empty()) refuse(manysearch_rules, "-g says how -r / -f files are sketched; sketches loaded with -R / -Q are what they are");
+    load_sketch_files(in, manysearch_rules, ld);
+    if (!in.scaled_given && ld.largest_scaled == 0) refuse(manysearch_rules, "no sketch file says at which scaled to sketch: give --scaled <n>");
+    const int k = run_k(manysearch_rules, ld.k);
+    ScaledRun run;
+    start_scaled_run(in, manysearch_rules, ld, k, run);
+    const ScaledSet &q = *run.queries, &sr = run.refs;
+    const size_t nq = q.names.size(), nr = sr.names.size();
+    if (nq > 0x7fffffffull || nr > 0x7fffffffull) refuse(manysearch_rules, "more than 2^31-1 sketches on one side");
+    std::vector<int32_t> q_min(nq, 1); // per query: the count that --min-containment asks of it
+    for (size_t i = 0; i < nq; ++i) {
+        const uint64_t lq = q.off[i + 1] - q.off[i];
+        if (lq > 0x7fffffffull) refuse(manysearch_rules, "a query of more than 2^31-1 hashes");
+        int32_t t = 0;
+        CK(rk_search_min_count(min_cont, lq, &t));
+        q_min[i] = std::max(t, 1);
+    }
+    rk_scaled_index* idx = nullptr;
+    CK(rk_scaled_index_create(run.ctx, sr.values.data(), sr.off.data(), (int64_t)nr, &idx));
+    rk_search_hit* hits = nullptr;
+    uint64_t nhits = 0;
+    CK(rk_search_scaled(run.ctx, idx, q.values.data(), q.off.data(), (int64_t)nq, min_shared, q_min.data(), &hits, &nhits));
+    OutBuf o(stdout);
+    for (uint64_t h = 0; h < nhits; ++h) {
+        const size_t i = (size_t)hits[h].query, j = (size_t)hits[h].ref;
+        if (i >= nq || j >= nr) { fprintf(stderr, "rkmh manysearch: hit %llu names query %d and reference %d of %zu x %zu\n", (unsigned long long)h, hits[h].query, hits[h].ref, nq, nr); exit(1); }
+        const long long sh = hits[h].shared, lq = (long long)(q.off[i + 1] - q.off[i]), lr = (long long)(sr.off[j + 1] - sr.off[j]);
+        double jac = 0, d = 1;
+        CK(rk_scaled_distance(sh, lq, lr, k, &jac, &d));
+        append_scaled_pair(o, sr.names[j], q.names[i], d, sh, lq, lr);
+        o.append("\n");
+        o.end_row();
+    }
+    o.flush();
+    fflush(stdout);
+    rk_free(hits);
+    rk_scaled_index_destroy(idx);
+    rk_ctx_destroy(run.ctx);
     return 0;
 }
