@@ -785,8 +785,8 @@ int rk_gather_scaled_abund_host(const uint64_t* q_values, const uint32_t* q_abun
  * rk_abund_row_sums: host arrays, n >= 1; RK_ERR_ARG for NULL, offsets that decrease, a row of 2^31 values or more, an abundance of
  * 0.  rk_abund_row_sums_device: resident arrays (nvalues = the number of uint32 behind d_abund; d_out2: n * 16 bytes), asynchronous,
  * rows clamped as above.
- * The kernels (rk_scaled.hip): k_scaled_pairs_w<1 | 8 | 64> -- k_scaled_pairs's layout, slices and merge carrying four sums instead
- * of one count -- and k_abund_row_sums, one wave per row.
+ * The kernels (rk_scaled.hip): k_scaled_pairs<1 | 8 | 64, PairsWeighted> -- the layout, slices and merge of the plain comparison
+ * (k_scaled_pairs<L, PairsPlain>) carrying four sums instead of one count -- and k_abund_row_sums, one wave per row.
  * rk_compare_scaled_abund_host, rk_abund_row_sums_host, rk_angular_similarity: host code, usable without a GPU (rk_scaled_host.cpp);
  * the checks of the entries on host arrays; `threads` host threads share the rows of a (below 1: one). */
 int rk_compare_scaled_abund(rk_ctx* ctx, const uint64_t* a_values, const uint32_t* a_abund, const uint64_t* a_offsets, int na,

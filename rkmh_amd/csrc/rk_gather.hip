@@ -3,7 +3,7 @@
 // the device across rounds: one byte per query value (alive), and per candidate reference the list of the query indices it holds.
 // The host-only form of the same loop is rk_gather_scaled_host (rk_scaled_host.cpp); semantics, bounds and measurements: DESIGN.md
 // section 12.  With the query's abundances every row also gets the weight it explains (k_gather_remove_w; section 13).
-#include "rk_api_internal.hpp"
+#include "rk_sets.hpp"
 
 namespace {
 
@@ -20,13 +20,6 @@ struct GatherState {
     int32_t remaining;  // |alive|
     int32_t pad[4];
 };
-
-// row r of the references, clamped to [0, nvalues] and to 2^31 - 1 values (as k_scaled_pairs clamps its rows)
-__device__ __forceinline__ void clamped_row(const uint64_t* __restrict__ off, uint32_t r, uint64_t nvalues, uint64_t& r0, uint64_t& r1) {
-    r0 = min(off[r], nvalues);
-    r1 = max(min(off[r + 1], nvalues), r0);
-    r1 = r0 + min(r1 - r0, (uint64_t)0x7fffffffu);
-}
 
 // One wave per reference, grid-stride.  Lanes stride the row; each looks its value up in Q (first element not below it: at most 32
 // halvings, nq < 2^31) and writes the query index, or MISS, into hit[], which lies parallel to the reference values.  The hits of a
@@ -45,11 +38,7 @@ __global__ __launch_bounds__(GATHER_T) void k_gather_probe(const uint64_t* __res
             bool found = false;
             if (t < r1) {
                 const uint64_t x = rv[t];
-                uint32_t lo = 0, hi = nq;
-                while (lo < hi) {
-                    const uint32_t mid = lo + ((hi - lo) >> 1);
-                    if (q[mid] < x) lo = mid + 1; else hi = mid;
-                }
+                const uint32_t lo = first_not_below(q, 0u, nq, x);
                 found = lo < nq && q[lo] == x;
                 hit[t] = found ? lo : MISS;
             }
@@ -180,10 +169,6 @@ __global__ __launch_bounds__(GATHER_T) void k_gather_remove_w(const GatherState*
     if ((threadIdx.x & 63) == 0 && sum != 0 && row >= 0 && row < max_rounds) atomicAdd(wunique + row, sum);
 }
 
-uint32_t wave_grid(uint64_t nwaves_wanted) { // workgroups of GATHER_WAVES waves for that many waves; the kernels stride beyond 2^16 of them
-    return (uint32_t)std::min<uint64_t>(std::max<uint64_t>((nwaves_wanted + GATHER_WAVES - 1) / GATHER_WAVES, 1), 1u << 16);
-}
-
 // The loop on resident arrays, on stream st, with the context's work buffers (the caller holds general_mu).  d_out4 takes at most
 // max_rounds rows.  d_wunique != nullptr: a weighted call (d_q_abund: one uint32 per query value), d_wunique takes one uint64 per row and is zeroed as far as rows can be
 // written.  Synchronises st.
@@ -201,7 +186,7 @@ int gather_run(rk_ctx* c, const uint64_t* d_q, const uint32_t* d_q_abund, uint64
     int32_t* d_total = c->w_g_total.as<int32_t>();
     uint8_t* d_alive = c->w_g_alive.as<uint8_t>();
     GatherState* d_state = c->w_g_state.as<GatherState>();
-    hipLaunchKernelGGL(k_gather_probe, dim3(wave_grid((uint64_t)nref)), dim3(GATHER_T), 0, st, d_q, nq32, d_rv, d_ro, (uint32_t)nref, r_nvalues, d_hit, d_total);
+    hipLaunchKernelGGL(k_gather_probe, dim3(wave_grid((uint64_t)nref, GATHER_WAVES)), dim3(GATHER_T), 0, st, d_q, nq32, d_rv, d_ro, (uint32_t)nref, r_nvalues, d_hit, d_total);
     HIPCHK(hipGetLastError());
     std::vector<int32_t> total((size_t)nref);
     HIPCHK(hipMemcpyAsync(total.data(), d_total, (size_t)nref * 4, hipMemcpyDeviceToHost, st));
@@ -232,7 +217,7 @@ int gather_run(rk_ctx* c, const uint64_t* d_q, const uint32_t* d_q_abund, uint64
     uint32_t* d_list = c->w_g_list.as<uint32_t>();
     HIPCHK(hipMemcpyAsync(d_cand, cand.data(), (size_t)ncand * 4, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(d_coff, coff.data(), ((size_t)ncand + 1) * 8, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_gather_compact, dim3(wave_grid(ncand)), dim3(GATHER_T), 0, st, d_ro, (uint32_t)nref, r_nvalues, d_hit, d_cand, d_coff, ncand, nlist, d_list);
+    hipLaunchKernelGGL(k_gather_compact, dim3(wave_grid(ncand, GATHER_WAVES)), dim3(GATHER_T), 0, st, d_ro, (uint32_t)nref, r_nvalues, d_hit, d_cand, d_coff, ncand, nlist, d_list);
     HIPCHK(hipGetLastError());
     // 3. the state of this call: every query value alive, no row written (nothing of an earlier call on this context survives)
     GatherState s0{};
@@ -242,7 +227,7 @@ int gather_run(rk_ctx* c, const uint64_t* d_q, const uint32_t* d_q_abund, uint64
     HIPCHK(hipStreamSynchronize(st)); // (cand, coff and s0 are pageable host memory: they live until here)
     // 4. rounds, in groups of RK_GATHER_BATCH: no reference is picked twice, so min(max_rounds, ncand) rounds are all there can be
     const int rounds = (int)std::min<uint64_t>((uint64_t)max_rounds, ncand);
-    const dim3 count_grid(wave_grid(ncand)), remove_grid((uint32_t)std::min<uint64_t>((longest + GATHER_T - 1) / GATHER_T, 1024));
+    const dim3 count_grid(wave_grid(ncand, GATHER_WAVES)), remove_grid((uint32_t)std::min<uint64_t>((longest + GATHER_T - 1) / GATHER_T, 1024));
     GatherState s{};
     for (int launched = 0; launched < rounds;) {
         const int group = std::min(RK_GATHER_BATCH, rounds - launched);
@@ -292,14 +277,9 @@ int gather_uploaded(rk_ctx* c, const uint64_t* q_values, const uint32_t* q_abund
     RKCHK(check_gather_shape(nq, nref, min_shared, max_rounds));
     for (uint64_t i = 0; i < nq; ++i)
         if (q_values[i] == 0 || (i && q_values[i] <= q_values[i - 1])) return fail(RK_ERR_ARG, "gather: the query is not ascending, distinct and non-zero at value %llu", (unsigned long long)i);
-    if (wunique)
-        for (uint64_t i = 0; i < nq; ++i)
-            if (q_abund[i] == 0) return fail(RK_ERR_ARG, "gather: abundance 0 at query value %llu", (unsigned long long)i);
-    for (int i = 0; i < nref; ++i) {
-        if (r_offsets[i + 1] < r_offsets[i]) return fail(RK_ERR_ARG, "gather: offsets of the references decrease at sketch %d", i);
-        if (r_offsets[i + 1] - r_offsets[i] > 0x7fffffffull) return fail(RK_ERR_LIMIT, "gather: reference sketch %d holds 2^31 values or more", i);
-    }
-    const uint64_t r0 = r_offsets[0], rn = r_offsets[nref] - r0; // the values the rows cover
+    if (wunique) RKCHK(check_abund(q_abund, 0, nq, "gather: ", "the query"));
+    RKCHK(check_csr(r_offsets, nref, "gather: ", "the references", RK_ERR_LIMIT));
+    const uint64_t rn = r_offsets[nref] - r_offsets[0]; // the values the rows cover
     if (rn && !r_values) return fail(RK_ERR_ARG, "bad arguments");
     RKCHK(set_dev(c));
     std::lock_guard<std::mutex> lk(c->general_mu); // the general path's work buffers serve here too
@@ -318,11 +298,9 @@ int gather_uploaded(rk_ctx* c, const uint64_t* q_values, const uint32_t* q_abund
         d_qa = (uint32_t*)(d_wu + rows);
         if (nq) HIPCHK(hipMemcpyAsync(d_qa, q_abund, (size_t)nq * 4, hipMemcpyHostToDevice, c->st));
     }
-    std::vector<uint64_t> off((size_t)nref + 1);
-    for (int i = 0; i <= nref; ++i) off[(size_t)i] = r_offsets[i] - r0;
+    std::vector<uint64_t> off;
     if (nq) HIPCHK(hipMemcpyAsync(d_q, q_values, (size_t)nq * 8, hipMemcpyHostToDevice, c->st));
-    if (rn) HIPCHK(hipMemcpyAsync(d_rv, r_values + r0, (size_t)rn * 8, hipMemcpyHostToDevice, c->st));
-    HIPCHK(hipMemcpyAsync(d_ro, off.data(), ((size_t)nref + 1) * 8, hipMemcpyHostToDevice, c->st));
+    RKCHK(upload_csr(r_values, r_offsets, nref, d_rv, d_ro, off, c->st));
     RKCHK(gather_run(c, d_q, d_qa, nq, d_rv, d_ro, nref, rn, min_shared, rows, c->w_out.as<int32_t>(), d_wu, nrounds, c->st)); // (synchronises: off lives until there)
     if (*nrounds) HIPCHK(hipMemcpyAsync(out4, c->w_out.p, (size_t)*nrounds * 16, hipMemcpyDeviceToHost, c->st));
     if (wunique) HIPCHK(hipMemcpyAsync(wunique, d_wu, (size_t)rows * 8, hipMemcpyDeviceToHost, c->st));

@@ -1,127 +1,11 @@
 // rk_scaled.hip -- scaled (FracMinHash) sketches (include/rkmh_amd.h, "SCALED SKETCHES"): the step of the general path that turns a
 // chunk's window hashes into one variable-length set per sequence (keep / sort / drop repeats), and k_scaled_pairs, which intersects
-// every pair of such sets.  The host-only half (threshold, union, distance) is rk_scaled_host.cpp; semantics, routes, the lane rule
-// and measurements: DESIGN.md section 11; the abundances (the run lengths of the drop-repeats step): section 13; the weighted pairs
-// (k_scaled_pairs_w, k_abund_row_sums, at the end of the file): section 14.
-#include "rk_api_internal.hpp"
+// every pair of such sets, plainly or weighted by abundance.  The compaction behind keep and drop repeats is rk_sets.hpp's.  The
+// host-only half (threshold, union, distance) is rk_scaled_host.cpp; semantics, routes, the lane rule and measurements: DESIGN.md
+// section 11; the abundances (the run lengths of the drop-repeats step): section 13; the weighted pairs and k_abund_row_sums: section 14.
+#include "rk_sets.hpp"
 
 namespace {
-
-// ---- keeping: an order-preserving compaction of a flat array, run twice per chunk -------------------------------------------
-//   KEEP_HASH      v = the chunk's window hashes:          element t stays when 0 < v[t] <= max_hash
-//   KEEP_FIRST     v = the kept values, sorted by segment: element t stays when it is the first of its value in its segment
-// Because the order is kept, a sequence's values stay together; where a sequence begins in the output is the number of elements kept
-// before its first one (k_keep_bounds).  Count first (k_keep_count), scan the block counts (k_scan_blocks), size the output, scatter
-// (k_keep_scatter): no atomics, positions come from wave ballots.
-enum { KEEP_HASH = 0, KEEP_FIRST = 1 };
-constexpr int KEEP_T = 256, KEEP_ROUNDS = 4, KEEP_BLK = KEEP_T * KEEP_ROUNDS; // elements of one workgroup: round r, thread t -> element r * 256 + t
-
-// does a segment begin at element t?  off[0 .. nseg] ascending (equal entries: empty segments); at most 33 halvings
-__device__ __forceinline__ bool segment_starts_at(const uint64_t* __restrict__ off, uint32_t nseg, uint64_t t) {
-    uint32_t lo = 0, hi = nseg + 1; // first entry >= t
-    while (lo < hi) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if (off[mid] < t) lo = mid + 1; else hi = mid;
-    }
-    return lo <= nseg && off[lo] == t;
-}
-template <int MODE>
-__device__ __forceinline__ bool keeps(const uint64_t* __restrict__ v, uint64_t t, uint64_t max_hash, const uint64_t* __restrict__ off, uint32_t nseg) {
-    const uint64_t x = v[t];
-    if (MODE == KEEP_HASH) return x != 0 && x <= max_hash;
-    if (t == 0 || v[t - 1] != x) return true;
-    return segment_starts_at(off, nseg, t); // equal to the element before it: stays only as the first of the next segment
-}
-
-template <int MODE>
-__global__ __launch_bounds__(KEEP_T) void k_keep_count(const uint64_t* __restrict__ v, uint64_t n, uint64_t max_hash, const uint64_t* __restrict__ off,
-                                                       uint32_t nseg, uint32_t* __restrict__ block_count) {
-    __shared__ uint32_t wsum[KEEP_T / 64];
-    const uint64_t base = (uint64_t)blockIdx.x * KEEP_BLK;
-    uint32_t cnt = 0; // wave-uniform
-    for (int r = 0; r < KEEP_ROUNDS; ++r) {
-        const uint64_t t = base + (uint64_t)(r * KEEP_T) + threadIdx.x;
-        cnt += (uint32_t)__popcll(__ballot(t < n && keeps<MODE>(v, t, max_hash, off, nseg)));
-    }
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = cnt;
-    __syncthreads();
-    if (threadIdx.x == 0) block_count[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-}
-
-// pre[b] = block_count[0] + ... + block_count[b - 1] for b in [0, nblocks]; one workgroup of 1024, each thread a contiguous span
-__global__ __launch_bounds__(1024) void k_scan_blocks(const uint32_t* __restrict__ block_count, uint64_t nblocks, uint64_t* __restrict__ pre) {
-    __shared__ uint64_t part[1024];
-    const uint64_t per = (nblocks + 1023) / 1024;
-    const uint64_t b0 = min((uint64_t)threadIdx.x * per, nblocks), b1 = min(b0 + per, nblocks);
-    uint64_t sum = 0;
-    for (uint64_t b = b0; b < b1; ++b) sum += block_count[b];
-    part[threadIdx.x] = sum;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint64_t acc = 0;
-        for (int i = 0; i < 1024; ++i) { const uint64_t s = part[i]; part[i] = acc; acc += s; }
-        pre[nblocks] = acc;
-    }
-    __syncthreads();
-    uint64_t acc = part[threadIdx.x];
-    for (uint64_t b = b0; b < b1; ++b) { pre[b] = acc; acc += block_count[b]; }
-}
-
-// out_off[s] = elements kept before element off[s], for s in [0, nseg]: one wave per boundary counts the part of its block before it
-template <int MODE>
-__global__ __launch_bounds__(KEEP_T) void k_keep_bounds(const uint64_t* __restrict__ v, uint64_t n, uint64_t max_hash, const uint64_t* __restrict__ off,
-                                                        uint32_t nseg, const uint64_t* __restrict__ pre, uint64_t* __restrict__ out_off) {
-    const uint32_t s = blockIdx.x * (KEEP_T / 64) + (threadIdx.x >> 6);
-    if (s > nseg) return; // whole waves leave
-    const uint64_t p = min(off[s], n);
-    const uint64_t blk = p / KEEP_BLK; // <= number of blocks; pre has an entry for it
-    uint64_t cnt = 0;
-    for (uint64_t t0 = blk * KEEP_BLK; t0 < p; t0 += 64) { // at most 16 rounds
-        const uint64_t t = t0 + (threadIdx.x & 63);
-        cnt += (uint64_t)__popcll(__ballot(t < p && keeps<MODE>(v, t, max_hash, off, nseg)));
-    }
-    if ((threadIdx.x & 63) == 0) out_off[s] = pre[blk] + cnt;
-}
-
-// the scatter of one workgroup; SRC: the index t of every kept element also goes to src[], parallel to out[]
-template <int MODE, bool SRC>
-__device__ __forceinline__ void keep_scatter_block(const uint64_t* __restrict__ v, uint64_t n, uint64_t max_hash, const uint64_t* __restrict__ off,
-                                                   uint32_t nseg, const uint64_t* __restrict__ pre, uint64_t* __restrict__ out, uint64_t* __restrict__ src,
-                                                   uint64_t out_cap) {
-    __shared__ uint32_t wcnt[KEEP_ROUNDS * (KEEP_T / 64)]; // kept by (round, wave), in element order
-    const uint64_t base = (uint64_t)blockIdx.x * KEEP_BLK;
-    const uint32_t wave = threadIdx.x >> 6;
-    uint64_t x[KEEP_ROUNDS];
-    uint32_t rank[KEEP_ROUNDS];
-    bool keep[KEEP_ROUNDS];
-    for (int r = 0; r < KEEP_ROUNDS; ++r) {
-        const uint64_t t = base + (uint64_t)(r * KEEP_T) + threadIdx.x;
-        keep[r] = t < n && keeps<MODE>(v, t, max_hash, off, nseg);
-        x[r] = t < n ? v[t] : 0;
-        const uint64_t bal = __ballot(keep[r]);
-        rank[r] = lanes_below(bal);
-        if ((threadIdx.x & 63) == 0) wcnt[r * (KEEP_T / 64) + wave] = (uint32_t)__popcll(bal);
-    }
-    __syncthreads();
-    const uint64_t first = pre[blockIdx.x];
-    uint32_t before = 0;
-    for (int r = 0; r < KEEP_ROUNDS; ++r)
-        for (uint32_t w = 0; w < KEEP_T / 64; ++w) {
-            if (w == wave && keep[r]) {
-                const uint64_t at = first + before + rank[r];
-                if (at < out_cap) { // (always: out holds pre[nblocks] values)
-                    out[at] = x[r];
-                    if (SRC) src[at] = base + (uint64_t)(r * KEEP_T) + threadIdx.x;
-                }
-            }
-            before += wcnt[r * (KEEP_T / 64) + w];
-        }
-}
-template <int MODE>
-__global__ __launch_bounds__(KEEP_T) void k_keep_scatter(const uint64_t* __restrict__ v, uint64_t n, uint64_t max_hash, const uint64_t* __restrict__ off,
-                                                         uint32_t nseg, const uint64_t* __restrict__ pre, uint64_t* __restrict__ out, uint64_t out_cap) {
-    keep_scatter_block<MODE, false>(v, n, max_hash, off, nseg, pre, out, nullptr, out_cap);
-}
 
 // ---- abundances (include/rkmh_amd.h, "ABUNDANCE"): the length of every run that KEEP_FIRST collapses.  Every element of the sorted
 // array is the first of its value in its segment or a repeat of the element before it, so run j ends where run j + 1 begins, and the
@@ -140,28 +24,6 @@ __global__ __launch_bounds__(KEEP_T) void k_run_lengths(const uint64_t* __restri
     if (j >= m) return;
     const uint64_t begin = src[j], end = j + 1 < m ? src[j + 1] : n;
     abund[j] = (uint32_t)min(end > begin ? end - begin : (uint64_t)0, (uint64_t)0xffffffffu);
-}
-
-template <int MODE>
-int keep_counts(rk_ctx* c, const uint64_t* v, uint64_t n, uint64_t max_hash, const uint64_t* d_off, uint32_t nseg, uint64_t* d_out_off) {
-    const uint64_t nblocks = (n + KEEP_BLK - 1) / KEEP_BLK;
-    if (nblocks > 0x7fffffffull) return fail(RK_ERR_LIMIT, "%llu hashes are more than one compaction takes", (unsigned long long)n);
-    RKCHK(c->w_sc_cnt.reserve((size_t)(nblocks + 1) * 4));
-    RKCHK(c->w_sc_pre.reserve((size_t)(nblocks + 1) * 8));
-    if (nblocks) hipLaunchKernelGGL(k_keep_count<MODE>, dim3((uint32_t)nblocks), dim3(KEEP_T), 0, c->st, v, n, max_hash, d_off, nseg, c->w_sc_cnt.as<uint32_t>());
-    hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(1024), 0, c->st, c->w_sc_cnt.as<uint32_t>(), nblocks, c->w_sc_pre.as<uint64_t>());
-    hipLaunchKernelGGL(k_keep_bounds<MODE>, dim3((nseg + 1 + KEEP_T / 64 - 1) / (KEEP_T / 64)), dim3(KEEP_T), 0, c->st, v, n, max_hash, d_off, nseg,
-                       c->w_sc_pre.as<uint64_t>(), d_out_off);
-    HIPCHK(hipGetLastError());
-    return RK_OK;
-}
-template <int MODE>
-int keep_scatter(rk_ctx* c, const uint64_t* v, uint64_t n, uint64_t max_hash, const uint64_t* d_off, uint32_t nseg, uint64_t* out, uint64_t out_cap) {
-    const uint64_t nblocks = (n + KEEP_BLK - 1) / KEEP_BLK;
-    if (!nblocks) return RK_OK;
-    hipLaunchKernelGGL(k_keep_scatter<MODE>, dim3((uint32_t)nblocks), dim3(KEEP_T), 0, c->st, v, n, max_hash, d_off, nseg, c->w_sc_pre.as<uint64_t>(), out, out_cap);
-    HIPCHK(hipGetLastError());
-    return RK_OK;
 }
 
 // KEEP_FIRST's scatter with the abundances: d_src and d_abund hold n entries each, as out does; the number of firsts is read on the device
@@ -209,7 +71,7 @@ int scaled_keep_chunk(rk_ctx* c, const std::vector<uint64_t>& seg, uint64_t nhas
     uint64_t* d_koff2 = d_koff1 + cn + 1;
     const uint64_t* d_hashes = c->w_hashes.as<uint64_t>();
     const uint64_t* d_seg = c->w_segoff.as<uint64_t>();
-    RKCHK(keep_counts<KEEP_HASH>(c, d_hashes, nhashes, sink.max_hash, d_seg, nseg, d_koff1));
+    RKCHK(keep_counts<KEEP_HASH>(c->w_sc_cnt, c->w_sc_pre, d_hashes, nhashes, sink.max_hash, d_seg, nseg, d_koff1, c->st));
     std::vector<uint64_t> koff(cn + 1);
     HIPCHK(hipMemcpyAsync(koff.data(), d_koff1, (cn + 1) * 8, hipMemcpyDeviceToHost, c->st));
     HIPCHK(hipStreamSynchronize(c->st));
@@ -223,7 +85,7 @@ int scaled_keep_chunk(rk_ctx* c, const std::vector<uint64_t>& seg, uint64_t nhas
     RKCHK(c->w_sc_b.reserve((size_t)total1 * 8));
     uint64_t* d_a = c->w_sc_a.as<uint64_t>();
     uint64_t* d_b = c->w_sc_b.as<uint64_t>();
-    RKCHK(keep_scatter<KEEP_HASH>(c, d_hashes, nhashes, sink.max_hash, d_seg, nseg, d_a, total1));
+    RKCHK(keep_scatter<KEEP_HASH>(c->w_sc_pre, d_hashes, nhashes, sink.max_hash, d_seg, nseg, d_a, total1, c->st));
     // 2. sort every sequence's kept values in place: up to SORT_MAX_P by the in-LDS sorter, one launch per power of two (the general
     // path's size classes); longer ones by the whole-array radix sort, one call each.  0 or 1 values need no sort.
     std::vector<std::vector<uint32_t>> classes(32);
@@ -256,7 +118,7 @@ int scaled_keep_chunk(rk_ctx* c, const std::vector<uint64_t>& seg, uint64_t nhas
         for (uint32_t q : long_ids) HIPCHK(launch_sort_u64(d_a + koff[q], koff[q + 1] - koff[q], c->w_misc.p, tmp_bytes, c->st));
     }
     // 3. drop repeats: the first of every value in its segment stays
-    RKCHK(keep_counts<KEEP_FIRST>(c, d_a, total1, 0, d_koff1, nseg, d_koff2));
+    RKCHK(keep_counts<KEEP_FIRST>(c->w_sc_cnt, c->w_sc_pre, d_a, total1, 0, d_koff1, nseg, d_koff2, c->st));
     uint32_t* d_abund = nullptr;
     if (sink.with_abund) { // the run lengths leave with the values
         RKCHK(c->w_sc_src.reserve((size_t)total1 * 8));
@@ -264,7 +126,7 @@ int scaled_keep_chunk(rk_ctx* c, const std::vector<uint64_t>& seg, uint64_t nhas
         d_abund = c->w_sc_ab.as<uint32_t>();
         RKCHK(keep_first_abund(c, d_a, total1, d_koff1, nseg, d_b, c->w_sc_src.as<uint64_t>(), d_abund));
     } else
-        RKCHK(keep_scatter<KEEP_FIRST>(c, d_a, total1, 0, d_koff1, nseg, d_b, total1));
+        RKCHK(keep_scatter<KEEP_FIRST>(c->w_sc_pre, d_a, total1, 0, d_koff1, nseg, d_b, total1, c->st));
     std::vector<uint64_t> koff2(cn + 1);
     HIPCHK(hipMemcpyAsync(koff2.data(), d_koff2, (cn + 1) * 8, hipMemcpyDeviceToHost, c->st));
     HIPCHK(hipStreamSynchronize(c->st)); // (the id vectors of step 2 live until here)
@@ -308,179 +170,75 @@ extern "C" int rk_sketch_scaled_abund_batch(rk_ctx* c, const uint8_t* bases, con
 }
 
 // ---- pairs ---------------------------------------------------------------------------------------------------------------
+// ---- pairs, plain and weighted (include/rkmh_amd.h, "WEIGHTED COMPARISON") ------------------------------------
 namespace {
 
 constexpr int PAIRS_T = 256;
 
-// L lanes per pair, 64 / L pairs per wave.  The shorter row X is cut into L contiguous slices, lane `sub` owns X[s0, s1): it finds the
-// first element of the other row Y that is not below X[s0] (binary search, at most 32 halvings) and walks a two-pointer merge from
-// there until its slice or Y ends, counting equal values.  Every element of X belongs to exactly one lane, so a value at a slice
-// boundary is counted once.  Every step advances an index below its length; every read is at an index of a row clamped to
-// [0, nvalues]; compares are 64-bit unsigned.  Rows that are not ascending give meaningless counts and nothing worse.  The L partial
-// counts are added with shuffles inside the group of L lanes; no LDS, no atomics; the group's first lane stores the int32.
-template <int L>
-__global__ __launch_bounds__(PAIRS_T) void k_scaled_pairs(const uint64_t* __restrict__ av, const uint64_t* __restrict__ aoff, int na, uint64_t an,
-                                                          const uint64_t* __restrict__ bv, const uint64_t* __restrict__ boff, int nb, uint64_t bn,
-                                                          int32_t* __restrict__ out) {
-    const uint64_t npairs = (uint64_t)na * (uint64_t)nb;
-    const uint64_t p = (uint64_t)blockIdx.x * (PAIRS_T / L) + threadIdx.x / L;
-    const uint32_t sub = threadIdx.x % L;
-    const bool live = p < npairs; // lanes without a pair still take part in the shuffles
+// What a lane of k_scaled_pairs keeps of its slice of the merge.  equal(eq, ...) sees every step of it: ii and jj are the indices at
+// which x and y were read, inside the clamped rows, so the abundances XW, YW, which lie parallel to the values, may be read there.
+// add_lane(d) adds the partial result of lane (self ^ d); store writes the pair's answer.
+struct PairsPlain { // the number of equal values: one int32 per pair
+    typedef int32_t Out;
+    static constexpr int WIDTH = 1;
+    static constexpr bool WEIGHTED = false;
     int cnt = 0;
-    if (live) {
-        const uint64_t i = p / (uint64_t)nb, j = p % (uint64_t)nb;
-        const uint64_t a0 = min(aoff[i], an), a1 = max(min(aoff[i + 1], an), a0);
-        const uint64_t b0 = min(boff[j], bn), b1 = max(min(boff[j + 1], bn), b0);
-        const uint32_t la = (uint32_t)min(a1 - a0, (uint64_t)0x7fffffffu), lb = (uint32_t)min(b1 - b0, (uint64_t)0x7fffffffu);
-        const bool a_short = la <= lb;
-        const uint64_t* __restrict__ X = a_short ? av + a0 : bv + b0;
-        const uint64_t* __restrict__ Y = a_short ? bv + b0 : av + a0;
-        const uint32_t lx = a_short ? la : lb, ly = a_short ? lb : la;
-        const uint32_t s0 = (uint32_t)((uint64_t)lx * sub / L), s1 = (uint32_t)((uint64_t)lx * (sub + 1) / L);
-        if (s0 < s1 && ly > 0) {
-            uint64_t x = X[s0];
-            uint32_t lo = 0, hi = ly; // first Y >= x
-            if (L > 1 && s0 > 0)
-                while (lo < hi) {
-                    const uint32_t mid = lo + ((hi - lo) >> 1);
-                    if (Y[mid] < x) lo = mid + 1; else hi = mid;
-                }
-            uint32_t ii = s0, jj = lo;
-            if (jj < ly) {
-                uint64_t y = Y[jj];
-                for (;;) {
-                    const bool ax = x <= y, ay = y <= x;
-                    cnt += (ax && ay) ? 1 : 0;
-                    ii += ax ? 1u : 0u;
-                    jj += ay ? 1u : 0u;
-                    if (ii >= s1 || jj >= ly) break;
-                    if (ax) x = X[ii];
-                    if (ay) y = Y[jj];
-                }
-            }
+    __device__ __forceinline__ void equal(bool eq, const uint32_t* __restrict__, const uint32_t* __restrict__, uint32_t, uint32_t) { cnt += eq ? 1 : 0; }
+    __device__ __forceinline__ void add_lane(int d) { cnt += __shfl_xor(cnt, d, 64); }
+    __device__ __forceinline__ void store(Out* out, uint64_t p, bool) const { out[p] = cnt; }
+};
+// shared, dot (saturating), wx, wy: four uint64 per pair.  X is the shorter row whichever side it is: the sums are kept per row of
+// the merge (wx, wy) and given their sides at the end.  wx and wy cannot overflow: fewer than 2^31 values below 2^32 each.
+struct PairsWeighted {
+    typedef uint64_t Out;
+    static constexpr int WIDTH = 4;
+    static constexpr bool WEIGHTED = true;
+    uint64_t cnt = 0, dot = 0, wx = 0, wy = 0;
+    __device__ __forceinline__ void equal(bool eq, const uint32_t* __restrict__ XW, const uint32_t* __restrict__ YW, uint32_t ii, uint32_t jj) {
+        if (eq) {
+            const uint64_t u = XW[ii], w = YW[jj];
+            cnt += 1;
+            dot = sat_add(dot, u * w); // (2^32 - 1)^2 < 2^64
+            wx += u;
+            wy += w;
         }
     }
-    for (int d = L >> 1; d > 0; d >>= 1) cnt += __shfl_xor(cnt, d, 64);
-    if (live && sub == 0) out[p] = cnt;
-}
-
-// The lane rule of lanes = 0: a function of the mean length of the shorter side alone (measured at 800 and 5 000 values: DESIGN.md section 11).
-int auto_lanes(uint64_t an, int na, uint64_t bn, int nb) {
-    const uint64_t mean = std::min(an / (uint64_t)na, bn / (uint64_t)nb);
-    return mean < 16384 ? 1 : mean < 262144 ? 8 : 64;
-}
-
-int launch_scaled_pairs(const uint64_t* av, const uint64_t* aoff, int na, uint64_t an, const uint64_t* bv, const uint64_t* boff, int nb, uint64_t bn,
-                        int lanes, int32_t* out, hipStream_t st) {
-    const int L = lanes ? lanes : auto_lanes(an, na, bn, nb);
-    const uint64_t per = (uint64_t)(PAIRS_T / L), blocks = ((uint64_t)na * (uint64_t)nb + per - 1) / per;
-    if (blocks > 0x7fffffffull) return fail(RK_ERR_LIMIT, "%d x %d sketches are more pairs than one launch takes", na, nb);
-    const dim3 grid((uint32_t)blocks), block(PAIRS_T);
-    if (L == 1) hipLaunchKernelGGL(k_scaled_pairs<1>, grid, block, 0, st, av, aoff, na, an, bv, boff, nb, bn, out);
-    else if (L == 8) hipLaunchKernelGGL(k_scaled_pairs<8>, grid, block, 0, st, av, aoff, na, an, bv, boff, nb, bn, out);
-    else hipLaunchKernelGGL(k_scaled_pairs<64>, grid, block, 0, st, av, aoff, na, an, bv, boff, nb, bn, out);
-    HIPCHK(hipGetLastError());
-    return RK_OK;
-}
-
-int check_pairs_shape(int na, int nb, int lanes) {
-    if (na < 1 || nb < 1) return fail(RK_ERR_ARG, "need at least one sketch on each side, got %d x %d", na, nb);
-    if (lanes != 0 && lanes != 1 && lanes != 8 && lanes != 64) return fail(RK_ERR_ARG, "lanes %d is none of 0, 1, 8, 64", lanes);
-    return RK_OK;
-}
-int check_csr(const uint64_t* off, int n, const char* side) {
-    for (int i = 0; i < n; ++i) {
-        if (off[i + 1] < off[i]) return fail(RK_ERR_ARG, "offsets of %s decrease at sketch %d", side, i);
-        if (off[i + 1] - off[i] > 0x7fffffffull) return fail(RK_ERR_ARG, "sketch %d of %s holds 2^31 values or more", i, side);
+    __device__ __forceinline__ void add_lane(int d) {
+        cnt += shfl_xor_u64(cnt, d);
+        dot = sat_add(dot, shfl_xor_u64(dot, d));
+        wx += shfl_xor_u64(wx, d);
+        wy += shfl_xor_u64(wy, d);
     }
-    return RK_OK;
-}
-
-} // namespace
-
-extern "C" int rk_compare_scaled_device(rk_ctx* c, const void* d_a_values, const void* d_a_offsets, int na, uint64_t a_nvalues,
-                                        const void* d_b_values, const void* d_b_offsets, int nb, uint64_t b_nvalues, int lanes,
-                                        void* d_shared, void* hip_stream) {
-    if (!c || !d_a_offsets || !d_b_offsets || !d_shared || (!d_a_values && a_nvalues) || (!d_b_values && b_nvalues)) return fail(RK_ERR_ARG, "bad arguments");
-    RKCHK(check_pairs_shape(na, nb, lanes));
-    RKCHK(set_dev(c));
-    return launch_scaled_pairs((const uint64_t*)d_a_values, (const uint64_t*)d_a_offsets, na, a_nvalues, (const uint64_t*)d_b_values,
-                               (const uint64_t*)d_b_offsets, nb, b_nvalues, lanes, (int32_t*)d_shared, (hipStream_t)hip_stream);
-}
-
-extern "C" int rk_compare_scaled(rk_ctx* c, const uint64_t* a_values, const uint64_t* a_offsets, int na, const uint64_t* b_values,
-                                 const uint64_t* b_offsets, int nb, int lanes, int32_t* shared) {
-    if (!c || !a_offsets || !b_offsets || !shared) return fail(RK_ERR_ARG, "bad arguments");
-    RKCHK(check_pairs_shape(na, nb, lanes));
-    RKCHK(check_csr(a_offsets, na, "a"));
-    RKCHK(check_csr(b_offsets, nb, "b"));
-    const uint64_t an = a_offsets[na], bn = b_offsets[nb];
-    if ((an && !a_values) || (bn && !b_values)) return fail(RK_ERR_ARG, "bad arguments");
-    RKCHK(set_dev(c));
-    std::lock_guard<std::mutex> lk(c->general_mu); // the general path's work buffers serve here too
-    const bool self = a_values == b_values && a_offsets == b_offsets && na == nb;
-    RKCHK(c->w_sk.reserve((size_t)(an + (self ? 0 : bn)) * 8 + 8));
-    RKCHK(c->w_sc_off.reserve(((size_t)na + 1 + (self ? 0 : (size_t)nb + 1)) * 8));
-    uint64_t* d_av = c->w_sk.as<uint64_t>();
-    uint64_t* d_bv = self ? d_av : d_av + an;
-    uint64_t* d_ao = c->w_sc_off.as<uint64_t>();
-    uint64_t* d_bo = self ? d_ao : d_ao + na + 1;
-    if (an) HIPCHK(hipMemcpyAsync(d_av, a_values, (size_t)an * 8, hipMemcpyHostToDevice, c->st));
-    HIPCHK(hipMemcpyAsync(d_ao, a_offsets, ((size_t)na + 1) * 8, hipMemcpyHostToDevice, c->st));
-    if (!self) {
-        if (bn) HIPCHK(hipMemcpyAsync(d_bv, b_values, (size_t)bn * 8, hipMemcpyHostToDevice, c->st));
-        HIPCHK(hipMemcpyAsync(d_bo, b_offsets, ((size_t)nb + 1) * 8, hipMemcpyHostToDevice, c->st));
+    __device__ __forceinline__ void store(Out* out, uint64_t p, bool a_short) const {
+        uint64_t* o = out + p * 4;
+        o[0] = cnt;
+        o[1] = dot;
+        o[2] = a_short ? wx : wy;
+        o[3] = a_short ? wy : wx;
     }
-    const int L = lanes ? lanes : auto_lanes(an, na, bn, nb); // one choice for all row blocks
-    // the rows of the answer leave in blocks of at most 64 MB (one row when nb alone is wider than that)
-    const size_t row_bytes = (size_t)nb * 4;
-    size_t rows = std::max<size_t>(1, ((size_t)64 << 20) / row_bytes);
-    if (rows > (size_t)na) rows = (size_t)na;
-    RKCHK(c->w_out.reserve(rows * row_bytes));
-    for (size_t r0 = 0; r0 < (size_t)na; r0 += rows) {
-        const int n = (int)std::min(rows, (size_t)na - r0);
-        RKCHK(launch_scaled_pairs(d_av, d_ao + r0, n, an, d_bv, d_bo, nb, bn, L, c->w_out.as<int32_t>(), c->st));
-        HIPCHK(hipMemcpyAsync(shared + r0 * (size_t)nb, c->w_out.p, (size_t)n * row_bytes, hipMemcpyDeviceToHost, c->st));
-        HIPCHK(hipStreamSynchronize(c->st));
-    }
-    return RK_OK;
-}
+};
 
-// ---- weighted pairs (include/rkmh_amd.h, "WEIGHTED COMPARISON") ------------------------------------------
-// These stand behind everything else in the file so that the kernels above keep the code they had.
-namespace {
-
-// min(a + b, 2^64 - 1).  Associative and commutative on non-negative numbers: the result is min(true sum, 2^64 - 1) in any order.
-__device__ __forceinline__ uint64_t sat_add(uint64_t a, uint64_t b) {
-    const uint64_t s = a + b;
-    return s < a ? ~0ull : s;
-}
-// a 64-bit value from lane (self ^ d), as two halves
-__device__ __forceinline__ uint64_t shfl_xor_u64(uint64_t v, int d) {
-    const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, d, 64), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), d, 64);
-    return ((uint64_t)hi << 32) | lo;
-}
-
-// k_scaled_pairs with abundances: the same pair layout, clamps, slices, search and merge; on an equal pair the lane also loads the
-// two abundances, which lie parallel to the values, so at the index (inside its clamped row) at which it has just read the value.
-// X is the shorter row whichever side it is: the sums are kept per row of the merge (wx, wy) and given their sides at the end.  Four
-// partial results per lane -- shared, dot (saturating), wx, wy -- are added over the aligned group of L lanes with shuffles; no LDS,
-// no atomics; the group's first lane stores the four uint64.  wx and wy cannot overflow: fewer than 2^31 values below 2^32 each.
-template <int L>
-__global__ __launch_bounds__(PAIRS_T) void k_scaled_pairs_w(const uint64_t* __restrict__ av, const uint32_t* __restrict__ aw, const uint64_t* __restrict__ aoff,
-                                                            int na, uint64_t an, const uint64_t* __restrict__ bv, const uint32_t* __restrict__ bw,
-                                                            const uint64_t* __restrict__ boff, int nb, uint64_t bn, uint64_t* __restrict__ out) {
+// L lanes per pair, 64 / L pairs per wave.  The shorter row X is cut into L contiguous slices, lane `sub` owns X[s0, s1): it finds the
+// first element of the other row Y that is not below X[s0] (at most 32 halvings) and walks a two-pointer merge from there until its
+// slice or Y ends, handing every step to its Acc.  Every element of X belongs to exactly one lane, so a value at a slice boundary is
+// counted once.  Every step advances an index below its length; every read is at an index of a row clamped to [0, nvalues]; compares
+// are 64-bit unsigned.  Rows that are not ascending give meaningless results and nothing worse.  The L partial results are added
+// with shuffles inside the aligned group of L lanes; no LDS, no atomics; the group's first lane stores.  aw, bw: PairsWeighted only.
+template <int L, typename Acc>
+__global__ __launch_bounds__(PAIRS_T) void k_scaled_pairs(const uint64_t* __restrict__ av, const uint32_t* __restrict__ aw, const uint64_t* __restrict__ aoff,
+                                                          int na, uint64_t an, const uint64_t* __restrict__ bv, const uint32_t* __restrict__ bw,
+                                                          const uint64_t* __restrict__ boff, int nb, uint64_t bn, typename Acc::Out* __restrict__ out) {
     const uint64_t npairs = (uint64_t)na * (uint64_t)nb;
     const uint64_t p = (uint64_t)blockIdx.x * (PAIRS_T / L) + threadIdx.x / L;
     const uint32_t sub = threadIdx.x % L;
     const bool live = p < npairs; // lanes without a pair still take part in the shuffles
-    uint64_t cnt = 0, dot = 0, wx = 0, wy = 0;
+    Acc acc;
     bool a_short = true;
     if (live) {
-        const uint64_t i = p / (uint64_t)nb, j = p % (uint64_t)nb;
-        const uint64_t a0 = min(aoff[i], an), a1 = max(min(aoff[i + 1], an), a0);
-        const uint64_t b0 = min(boff[j], bn), b1 = max(min(boff[j + 1], bn), b0);
-        const uint32_t la = (uint32_t)min(a1 - a0, (uint64_t)0x7fffffffu), lb = (uint32_t)min(b1 - b0, (uint64_t)0x7fffffffu);
+        uint64_t a0, a1, b0, b1;
+        clamped_row(aoff, p / (uint64_t)nb, an, a0, a1);
+        clamped_row(boff, p % (uint64_t)nb, bn, b0, b1);
+        const uint32_t la = (uint32_t)(a1 - a0), lb = (uint32_t)(b1 - b0);
         a_short = la <= lb;
         const uint64_t* __restrict__ X = a_short ? av + a0 : bv + b0;
         const uint64_t* __restrict__ Y = a_short ? bv + b0 : av + a0;
@@ -490,24 +248,12 @@ __global__ __launch_bounds__(PAIRS_T) void k_scaled_pairs_w(const uint64_t* __re
         const uint32_t s0 = (uint32_t)((uint64_t)lx * sub / L), s1 = (uint32_t)((uint64_t)lx * (sub + 1) / L);
         if (s0 < s1 && ly > 0) {
             uint64_t x = X[s0];
-            uint32_t lo = 0, hi = ly; // first Y >= x
-            if (L > 1 && s0 > 0)
-                while (lo < hi) {
-                    const uint32_t mid = lo + ((hi - lo) >> 1);
-                    if (Y[mid] < x) lo = mid + 1; else hi = mid;
-                }
-            uint32_t ii = s0, jj = lo;
+            uint32_t ii = s0, jj = L > 1 && s0 > 0 ? first_not_below(Y, 0u, ly, x) : 0u;
             if (jj < ly) {
                 uint64_t y = Y[jj];
                 for (;;) {
                     const bool ax = x <= y, ay = y <= x;
-                    if (ax && ay) { // ii < s1 <= lx and jj < ly: the indices at which x and y were read
-                        const uint64_t u = XW[ii], w = YW[jj];
-                        cnt += 1;
-                        dot = sat_add(dot, u * w); // (2^32 - 1)^2 < 2^64
-                        wx += u;
-                        wy += w;
-                    }
+                    acc.equal(ax && ay, XW, YW, ii, jj);
                     ii += ax ? 1u : 0u;
                     jj += ay ? 1u : 0u;
                     if (ii >= s1 || jj >= ly) break;
@@ -517,19 +263,8 @@ __global__ __launch_bounds__(PAIRS_T) void k_scaled_pairs_w(const uint64_t* __re
             }
         }
     }
-    for (int d = L >> 1; d > 0; d >>= 1) {
-        cnt += shfl_xor_u64(cnt, d);
-        dot = sat_add(dot, shfl_xor_u64(dot, d));
-        wx += shfl_xor_u64(wx, d);
-        wy += shfl_xor_u64(wy, d);
-    }
-    if (live && sub == 0) { // a_short is the group's: every lane of it has the same pair
-        uint64_t* __restrict__ o = out + p * 4;
-        o[0] = cnt;
-        o[1] = dot;
-        o[2] = a_short ? wx : wy;
-        o[3] = a_short ? wy : wx;
-    }
+    for (int d = L >> 1; d > 0; d >>= 1) acc.add_lane(d);
+    if (live && sub == 0) acc.store(out, p, a_short); // a_short is the group's: every lane of it has the same pair
 }
 
 // out[i * 2] = sum of row i's abundances, out[i * 2 + 1] = sum of their squares, saturating.  One wave per row, grid-stride; the
@@ -539,10 +274,10 @@ __global__ __launch_bounds__(SUMS_T) void k_abund_row_sums(const uint32_t* __res
                                                            uint64_t* __restrict__ out) {
     const uint32_t lane = threadIdx.x & 63;
     for (uint64_t i = (uint64_t)blockIdx.x * (SUMS_T / 64) + (threadIdx.x >> 6); i < (uint64_t)n; i += (uint64_t)gridDim.x * (SUMS_T / 64)) { // whole waves
-        const uint64_t r0 = min(off[i], nvalues), r1 = max(min(off[i + 1], nvalues), r0);
-        const uint64_t len = min(r1 - r0, (uint64_t)0x7fffffffu);
+        uint64_t r0, r1;
+        clamped_row(off, i, nvalues, r0, r1);
         uint64_t sum = 0, sq = 0;
-        for (uint64_t t = lane; t < len; t += 64) {
+        for (uint64_t t = lane; t < r1 - r0; t += 64) {
             const uint64_t u = w[r0 + t];
             sum += u;
             sq = sat_add(sq, u * u);
@@ -555,15 +290,20 @@ __global__ __launch_bounds__(SUMS_T) void k_abund_row_sums(const uint32_t* __res
     }
 }
 
-int launch_scaled_pairs_w(const uint64_t* av, const uint32_t* aw, const uint64_t* aoff, int na, uint64_t an, const uint64_t* bv, const uint32_t* bw,
-                          const uint64_t* boff, int nb, uint64_t bn, int lanes, uint64_t* out, hipStream_t st) {
+// The lane rule of lanes = 0: a function of the mean length of the shorter side alone (measured at 800 and 5 000 values: DESIGN.md section 11).
+int auto_lanes(uint64_t an, int na, uint64_t bn, int nb) {
+    const uint64_t mean = std::min(an / (uint64_t)na, bn / (uint64_t)nb);
+    return mean < 16384 ? 1 : mean < 262144 ? 8 : 64;
+}
+
+template <typename Acc>
+int launch_scaled_pairs(const uint64_t* av, const uint32_t* aw, const uint64_t* aoff, int na, uint64_t an, const uint64_t* bv, const uint32_t* bw,
+                        const uint64_t* boff, int nb, uint64_t bn, int lanes, typename Acc::Out* out, hipStream_t st) {
     const int L = lanes ? lanes : auto_lanes(an, na, bn, nb);
     const uint64_t per = (uint64_t)(PAIRS_T / L), blocks = ((uint64_t)na * (uint64_t)nb + per - 1) / per;
     if (blocks > 0x7fffffffull) return fail(RK_ERR_LIMIT, "%d x %d sketches are more pairs than one launch takes", na, nb);
-    const dim3 grid((uint32_t)blocks), block(PAIRS_T);
-    if (L == 1) hipLaunchKernelGGL(k_scaled_pairs_w<1>, grid, block, 0, st, av, aw, aoff, na, an, bv, bw, boff, nb, bn, out);
-    else if (L == 8) hipLaunchKernelGGL(k_scaled_pairs_w<8>, grid, block, 0, st, av, aw, aoff, na, an, bv, bw, boff, nb, bn, out);
-    else hipLaunchKernelGGL(k_scaled_pairs_w<64>, grid, block, 0, st, av, aw, aoff, na, an, bv, bw, boff, nb, bn, out);
+    auto* kernel = L == 1 ? k_scaled_pairs<1, Acc> : L == 8 ? k_scaled_pairs<8, Acc> : k_scaled_pairs<64, Acc>;
+    hipLaunchKernelGGL(kernel, dim3((uint32_t)blocks), dim3(PAIRS_T), 0, st, av, aw, aoff, na, an, bv, bw, boff, nb, bn, out);
     HIPCHK(hipGetLastError());
     return RK_OK;
 }
@@ -573,15 +313,74 @@ int launch_row_sums(const uint32_t* w, const uint64_t* off, int n, uint64_t nval
     HIPCHK(hipGetLastError());
     return RK_OK;
 }
-// every abundance of rows [off[0], off[n]) is at least 1
-int check_abund(const uint32_t* w, const uint64_t* off, int n, const char* side) {
-    for (uint64_t t = off[0]; t < off[n]; ++t)
-        if (w[t] == 0) return fail(RK_ERR_ARG, "abundance 0 at value %llu of %s", (unsigned long long)t, side);
+
+int check_pairs_shape(int na, int nb, int lanes) {
+    if (na < 1 || nb < 1) return fail(RK_ERR_ARG, "need at least one sketch on each side, got %d x %d", na, nb);
+    if (lanes != 0 && lanes != 1 && lanes != 8 && lanes != 64) return fail(RK_ERR_ARG, "lanes %d is none of 0, 1, 8, 64", lanes);
+    return RK_OK;
+}
+
+// The entry on host arrays behind rk_compare_scaled and rk_compare_scaled_abund (PairsWeighted: with the abundances of both sides).
+// When b is a itself, it is uploaded once.  The rows of the answer leave in blocks of at most 64 MB.
+template <typename Acc>
+int compare_uploaded(rk_ctx* c, const uint64_t* a_values, const uint32_t* a_abund, const uint64_t* a_offsets, int na, const uint64_t* b_values,
+                     const uint32_t* b_abund, const uint64_t* b_offsets, int nb, int lanes, typename Acc::Out* out) {
+    if (!c || !a_offsets || !b_offsets || !out) return fail(RK_ERR_ARG, "bad arguments");
+    RKCHK(check_pairs_shape(na, nb, lanes));
+    RKCHK(check_csr(a_offsets, na, "", "a", RK_ERR_ARG));
+    RKCHK(check_csr(b_offsets, nb, "", "b", RK_ERR_ARG));
+    const uint64_t an = a_offsets[na], bn = b_offsets[nb];
+    if ((an && (!a_values || (Acc::WEIGHTED && !a_abund))) || (bn && (!b_values || (Acc::WEIGHTED && !b_abund)))) return fail(RK_ERR_ARG, "bad arguments");
+    const bool self = a_values == b_values && a_abund == b_abund && a_offsets == b_offsets && na == nb;
+    if (Acc::WEIGHTED) {
+        RKCHK(check_abund(a_abund, a_offsets[0], an, "", "a"));
+        if (!self) RKCHK(check_abund(b_abund, b_offsets[0], bn, "", "b"));
+    }
+    RKCHK(set_dev(c));
+    std::lock_guard<std::mutex> lk(c->general_mu); // the general path's work buffers serve here too
+    RKCHK(c->w_sk.reserve((size_t)(an + (self ? 0 : bn)) * 8 + 8));
+    if (Acc::WEIGHTED) RKCHK(c->w_sc_ab.reserve((size_t)(an + (self ? 0 : bn)) * 4 + 4));
+    RKCHK(c->w_sc_off.reserve(((size_t)na + 1 + (self ? 0 : (size_t)nb + 1)) * 8));
+    uint64_t* d_av = c->w_sk.as<uint64_t>();
+    uint64_t* d_bv = self ? d_av : d_av + an;
+    uint32_t* d_aw = Acc::WEIGHTED ? c->w_sc_ab.as<uint32_t>() : nullptr;
+    uint32_t* d_bw = self || !d_aw ? d_aw : d_aw + an;
+    uint64_t* d_ao = c->w_sc_off.as<uint64_t>();
+    uint64_t* d_bo = self ? d_ao : d_ao + na + 1;
+    if (an) HIPCHK(hipMemcpyAsync(d_av, a_values, (size_t)an * 8, hipMemcpyHostToDevice, c->st));
+    if (an && d_aw) HIPCHK(hipMemcpyAsync(d_aw, a_abund, (size_t)an * 4, hipMemcpyHostToDevice, c->st));
+    HIPCHK(hipMemcpyAsync(d_ao, a_offsets, ((size_t)na + 1) * 8, hipMemcpyHostToDevice, c->st));
+    if (!self) {
+        if (bn) HIPCHK(hipMemcpyAsync(d_bv, b_values, (size_t)bn * 8, hipMemcpyHostToDevice, c->st));
+        if (bn && d_bw) HIPCHK(hipMemcpyAsync(d_bw, b_abund, (size_t)bn * 4, hipMemcpyHostToDevice, c->st));
+        HIPCHK(hipMemcpyAsync(d_bo, b_offsets, ((size_t)nb + 1) * 8, hipMemcpyHostToDevice, c->st));
+    }
+    const int L = lanes ? lanes : auto_lanes(an, na, bn, nb); // one choice for all row blocks
+    // the rows of the answer leave in blocks of at most 64 MB (one row when nb alone is wider than that)
+    const size_t row_bytes = (size_t)nb * Acc::WIDTH * sizeof(typename Acc::Out);
+    size_t rows = std::max<size_t>(1, ((size_t)64 << 20) / row_bytes);
+    if (rows > (size_t)na) rows = (size_t)na;
+    RKCHK(c->w_out.reserve(rows * row_bytes));
+    for (size_t r0 = 0; r0 < (size_t)na; r0 += rows) {
+        const int n = (int)std::min(rows, (size_t)na - r0);
+        RKCHK(launch_scaled_pairs<Acc>(d_av, d_aw, d_ao + r0, n, an, d_bv, d_bw, d_bo, nb, bn, L, c->w_out.as<typename Acc::Out>(), c->st));
+        HIPCHK(hipMemcpyAsync(out + r0 * (size_t)nb * Acc::WIDTH, c->w_out.p, (size_t)n * row_bytes, hipMemcpyDeviceToHost, c->st));
+        HIPCHK(hipStreamSynchronize(c->st));
+    }
     return RK_OK;
 }
 
 } // namespace
 
+extern "C" int rk_compare_scaled_device(rk_ctx* c, const void* d_a_values, const void* d_a_offsets, int na, uint64_t a_nvalues,
+                                        const void* d_b_values, const void* d_b_offsets, int nb, uint64_t b_nvalues, int lanes,
+                                        void* d_shared, void* hip_stream) {
+    if (!c || !d_a_offsets || !d_b_offsets || !d_shared || (!d_a_values && a_nvalues) || (!d_b_values && b_nvalues)) return fail(RK_ERR_ARG, "bad arguments");
+    RKCHK(check_pairs_shape(na, nb, lanes));
+    RKCHK(set_dev(c));
+    return launch_scaled_pairs<PairsPlain>((const uint64_t*)d_a_values, nullptr, (const uint64_t*)d_a_offsets, na, a_nvalues, (const uint64_t*)d_b_values, nullptr,
+                                           (const uint64_t*)d_b_offsets, nb, b_nvalues, lanes, (int32_t*)d_shared, (hipStream_t)hip_stream);
+}
 extern "C" int rk_compare_scaled_abund_device(rk_ctx* c, const void* d_a_values, const void* d_a_abund, const void* d_a_offsets, int na, uint64_t a_nvalues,
                                               const void* d_b_values, const void* d_b_abund, const void* d_b_offsets, int nb, uint64_t b_nvalues, int lanes,
                                               void* d_out4, void* hip_stream) {
@@ -589,53 +388,18 @@ extern "C" int rk_compare_scaled_abund_device(rk_ctx* c, const void* d_a_values,
         return fail(RK_ERR_ARG, "bad arguments");
     RKCHK(check_pairs_shape(na, nb, lanes));
     RKCHK(set_dev(c));
-    return launch_scaled_pairs_w((const uint64_t*)d_a_values, (const uint32_t*)d_a_abund, (const uint64_t*)d_a_offsets, na, a_nvalues, (const uint64_t*)d_b_values,
-                                 (const uint32_t*)d_b_abund, (const uint64_t*)d_b_offsets, nb, b_nvalues, lanes, (uint64_t*)d_out4, (hipStream_t)hip_stream);
+    return launch_scaled_pairs<PairsWeighted>((const uint64_t*)d_a_values, (const uint32_t*)d_a_abund, (const uint64_t*)d_a_offsets, na, a_nvalues,
+                                              (const uint64_t*)d_b_values, (const uint32_t*)d_b_abund, (const uint64_t*)d_b_offsets, nb, b_nvalues, lanes,
+                                              (uint64_t*)d_out4, (hipStream_t)hip_stream);
 }
 
+extern "C" int rk_compare_scaled(rk_ctx* c, const uint64_t* a_values, const uint64_t* a_offsets, int na, const uint64_t* b_values,
+                                 const uint64_t* b_offsets, int nb, int lanes, int32_t* shared) {
+    return compare_uploaded<PairsPlain>(c, a_values, nullptr, a_offsets, na, b_values, nullptr, b_offsets, nb, lanes, shared);
+}
 extern "C" int rk_compare_scaled_abund(rk_ctx* c, const uint64_t* a_values, const uint32_t* a_abund, const uint64_t* a_offsets, int na, const uint64_t* b_values,
                                        const uint32_t* b_abund, const uint64_t* b_offsets, int nb, int lanes, uint64_t* out4) {
-    if (!c || !a_offsets || !b_offsets || !out4) return fail(RK_ERR_ARG, "bad arguments");
-    RKCHK(check_pairs_shape(na, nb, lanes));
-    RKCHK(check_csr(a_offsets, na, "a"));
-    RKCHK(check_csr(b_offsets, nb, "b"));
-    const uint64_t an = a_offsets[na], bn = b_offsets[nb];
-    if ((an && (!a_values || !a_abund)) || (bn && (!b_values || !b_abund))) return fail(RK_ERR_ARG, "bad arguments");
-    const bool self = a_values == b_values && a_abund == b_abund && a_offsets == b_offsets && na == nb;
-    RKCHK(check_abund(a_abund, a_offsets, na, "a"));
-    if (!self) RKCHK(check_abund(b_abund, b_offsets, nb, "b"));
-    RKCHK(set_dev(c));
-    std::lock_guard<std::mutex> lk(c->general_mu); // the general path's work buffers serve here too
-    RKCHK(c->w_sk.reserve((size_t)(an + (self ? 0 : bn)) * 8 + 8));
-    RKCHK(c->w_sc_ab.reserve((size_t)(an + (self ? 0 : bn)) * 4 + 4));
-    RKCHK(c->w_sc_off.reserve(((size_t)na + 1 + (self ? 0 : (size_t)nb + 1)) * 8));
-    uint64_t* d_av = c->w_sk.as<uint64_t>();
-    uint64_t* d_bv = self ? d_av : d_av + an;
-    uint32_t* d_aw = c->w_sc_ab.as<uint32_t>();
-    uint32_t* d_bw = self ? d_aw : d_aw + an;
-    uint64_t* d_ao = c->w_sc_off.as<uint64_t>();
-    uint64_t* d_bo = self ? d_ao : d_ao + na + 1;
-    if (an) HIPCHK(hipMemcpyAsync(d_av, a_values, (size_t)an * 8, hipMemcpyHostToDevice, c->st));
-    if (an) HIPCHK(hipMemcpyAsync(d_aw, a_abund, (size_t)an * 4, hipMemcpyHostToDevice, c->st));
-    HIPCHK(hipMemcpyAsync(d_ao, a_offsets, ((size_t)na + 1) * 8, hipMemcpyHostToDevice, c->st));
-    if (!self) {
-        if (bn) HIPCHK(hipMemcpyAsync(d_bv, b_values, (size_t)bn * 8, hipMemcpyHostToDevice, c->st));
-        if (bn) HIPCHK(hipMemcpyAsync(d_bw, b_abund, (size_t)bn * 4, hipMemcpyHostToDevice, c->st));
-        HIPCHK(hipMemcpyAsync(d_bo, b_offsets, ((size_t)nb + 1) * 8, hipMemcpyHostToDevice, c->st));
-    }
-    const int L = lanes ? lanes : auto_lanes(an, na, bn, nb); // one choice for all row blocks
-    // the rows of the answer leave in blocks of at most 64 MB (one row when nb alone is wider than that)
-    const size_t row_bytes = (size_t)nb * 32;
-    size_t rows = std::max<size_t>(1, ((size_t)64 << 20) / row_bytes);
-    if (rows > (size_t)na) rows = (size_t)na;
-    RKCHK(c->w_out.reserve(rows * row_bytes));
-    for (size_t r0 = 0; r0 < (size_t)na; r0 += rows) {
-        const int n = (int)std::min(rows, (size_t)na - r0);
-        RKCHK(launch_scaled_pairs_w(d_av, d_aw, d_ao + r0, n, an, d_bv, d_bw, d_bo, nb, bn, L, c->w_out.as<uint64_t>(), c->st));
-        HIPCHK(hipMemcpyAsync(out4 + r0 * (size_t)nb * 4, c->w_out.p, (size_t)n * row_bytes, hipMemcpyDeviceToHost, c->st));
-        HIPCHK(hipStreamSynchronize(c->st));
-    }
-    return RK_OK;
+    return compare_uploaded<PairsWeighted>(c, a_values, a_abund, a_offsets, na, b_values, b_abund, b_offsets, nb, lanes, out4);
 }
 
 extern "C" int rk_abund_row_sums_device(rk_ctx* c, const void* d_abund, const void* d_offsets, int n, uint64_t nvalues, void* d_out2, void* hip_stream) {
@@ -648,10 +412,10 @@ extern "C" int rk_abund_row_sums_device(rk_ctx* c, const void* d_abund, const vo
 extern "C" int rk_abund_row_sums(rk_ctx* c, const uint32_t* abund, const uint64_t* offsets, int n, uint64_t* out2) {
     if (!c || !offsets || !out2) return fail(RK_ERR_ARG, "bad arguments");
     if (n < 1) return fail(RK_ERR_ARG, "need at least one sketch, got %d", n);
-    RKCHK(check_csr(offsets, n, "the sketches"));
+    RKCHK(check_csr(offsets, n, "", "the sketches", RK_ERR_ARG));
     const uint64_t nv = offsets[n];
     if (nv && !abund) return fail(RK_ERR_ARG, "bad arguments");
-    RKCHK(check_abund(abund, offsets, n, "the sketches"));
+    RKCHK(check_abund(abund, offsets[0], nv, "", "the sketches"));
     RKCHK(set_dev(c));
     std::lock_guard<std::mutex> lk(c->general_mu);
     RKCHK(c->w_sc_ab.reserve((size_t)nv * 4 + 4));

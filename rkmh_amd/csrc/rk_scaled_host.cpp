@@ -264,7 +264,7 @@ extern "C" int rk_search_min_count(double x, uint64_t len, int32_t* t) {
     return RK_OK;
 }
 
-// ---- weighted comparison on the host (include/rkmh_amd.h, "WEIGHTED COMPARISON"): the sums of k_scaled_pairs_w and k_abund_row_sums
+// ---- weighted comparison on the host (include/rkmh_amd.h, "WEIGHTED COMPARISON"): the sums of k_scaled_pairs<L, PairsWeighted> and k_abund_row_sums
 // from plain loops, and the one place where they become floating point.
 namespace {
 inline uint64_t sat_add(uint64_t a, uint64_t b) { const uint64_t s = a + b; return s < a ? ~0ull : s; }

@@ -2,7 +2,7 @@
 // references that hold it) and the thresholded many-against-many search on top of it.  The work grows with the values the two sides
 // share, not with the number of pairs.  The host-only form is rk_search_scaled_host (rk_scaled_host.cpp); semantics, bounds and
 // measurements: DESIGN.md section 15.
-#include "rk_api_internal.hpp"
+#include "rk_sets.hpp"
 
 struct rk_scaled_index {
     rk_ctx* ctx = nullptr; // compared, never followed: the index may outlive its context
@@ -20,91 +20,27 @@ constexpr int SEARCH_T = 256;                  // threads of a workgroup of ever
 constexpr int SEARCH_WAVES = SEARCH_T / 64;
 constexpr uint32_t RB = RK_SEARCH_REF_BLOCK;   // references per workgroup: its counters are RB int32 in LDS
 constexpr uint32_t WAVE_SPAN = RB / SEARCH_WAVES; // counters one wave reads out, a contiguous span
-constexpr int FIRST_T = 256, FIRST_ROUNDS = 4, FIRST_BLK = FIRST_T * FIRST_ROUNDS; // the compaction, laid out as rk_scaled.hip's
 
 static_assert(RB * 4 <= 32768 && RB % (SEARCH_WAVES * 64) == 0, "the counters of a reference block fit 32 KB and split into whole rounds per wave");
 
 // ---- the build ------------------------------------------------------------------------------------------------------------
-// One wave per row, grid-stride: id[t] = r for every position t of row r, the row clamped to [0, nvalues] and to 2^31 - 1 values as
-// k_scaled_pairs clamps its rows.  (id[] was filled with 2^32 - 1 before: the id of a position that no row covers.)
+// One wave per row, grid-stride: id[t] = r for every position t of the clamped row r.  (id[] was filled with 2^32 - 1 before: the id
+// of a position that no row covers.)
 __global__ __launch_bounds__(SEARCH_T) void k_index_ids(const uint64_t* __restrict__ off, uint32_t nref, uint64_t nvalues, uint32_t* __restrict__ id) {
     const uint32_t lane = threadIdx.x & 63;
     const uint64_t nwaves = (uint64_t)gridDim.x * SEARCH_WAVES;
     for (uint64_t r = (uint64_t)blockIdx.x * SEARCH_WAVES + (threadIdx.x >> 6); r < nref; r += nwaves) { // wave-uniform
-        const uint64_t r0 = min(off[r], nvalues);
-        uint64_t r1 = max(min(off[r + 1], nvalues), r0);
-        r1 = r0 + min(r1 - r0, (uint64_t)0x7fffffffu);
+        uint64_t r0, r1;
+        clamped_row(off, r, nvalues, r0, r1);
         for (uint64_t t = r0 + lane; t < r1; t += 64) id[t] = (uint32_t)r;
     }
 }
 
-// "the first of its value" over the sorted values: the compaction of rk_scaled.hip (count per block, scan the block counts, scatter at
-// positions from ballots) with one segment; the scatter also notes where each first stood: that is where its posting list begins.
-__device__ __forceinline__ bool is_first(const uint64_t* __restrict__ v, uint64_t t) { return t == 0 || v[t - 1] != v[t]; }
-
-__global__ __launch_bounds__(FIRST_T) void k_first_count(const uint64_t* __restrict__ v, uint64_t n, uint32_t* __restrict__ block_count) {
-    __shared__ uint32_t wsum[FIRST_T / 64];
-    const uint64_t base = (uint64_t)blockIdx.x * FIRST_BLK;
-    uint32_t cnt = 0; // wave-uniform
-    for (int r = 0; r < FIRST_ROUNDS; ++r) {
-        const uint64_t t = base + (uint64_t)(r * FIRST_T) + threadIdx.x;
-        cnt += (uint32_t)__popcll(__ballot(t < n && is_first(v, t)));
-    }
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = cnt;
-    __syncthreads();
-    if (threadIdx.x == 0) block_count[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-}
-
-// pre[b] = count[0] + ... + count[b - 1] for b in [0, n]; one workgroup of 1024, each thread a contiguous span (k_scan_blocks of rk_scaled.hip)
-__global__ __launch_bounds__(1024) void k_scan_counts(const uint32_t* __restrict__ count, uint64_t n, uint64_t* __restrict__ pre) {
-    __shared__ uint64_t part[1024];
-    const uint64_t per = (n + 1023) / 1024;
-    const uint64_t b0 = min((uint64_t)threadIdx.x * per, n), b1 = min(b0 + per, n);
-    uint64_t sum = 0;
-    for (uint64_t b = b0; b < b1; ++b) sum += count[b];
-    part[threadIdx.x] = sum;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint64_t acc = 0;
-        for (int i = 0; i < 1024; ++i) { const uint64_t s = part[i]; part[i] = acc; acc += s; }
-        pre[n] = acc;
-    }
-    __syncthreads();
-    uint64_t acc = part[threadIdx.x];
-    for (uint64_t b = b0; b < b1; ++b) { pre[b] = acc; acc += count[b]; }
-}
-
-// keys[j] = the j-th distinct value, post_off[j] = where it first stands; a write lands below nkeys only.  post_off[nkeys] = n.
-__global__ __launch_bounds__(FIRST_T) void k_first_scatter(const uint64_t* __restrict__ v, uint64_t n, const uint64_t* __restrict__ pre,
-                                                           uint64_t* __restrict__ keys, uint64_t* __restrict__ post_off, uint64_t nkeys) {
-    __shared__ uint32_t wcnt[FIRST_ROUNDS * (FIRST_T / 64)]; // firsts by (round, wave), in element order
-    const uint64_t base = (uint64_t)blockIdx.x * FIRST_BLK;
-    const uint32_t wave = threadIdx.x >> 6;
-    uint64_t x[FIRST_ROUNDS];
-    uint32_t rank[FIRST_ROUNDS];
-    bool keep[FIRST_ROUNDS];
-    for (int r = 0; r < FIRST_ROUNDS; ++r) {
-        const uint64_t t = base + (uint64_t)(r * FIRST_T) + threadIdx.x;
-        keep[r] = t < n && is_first(v, t);
-        x[r] = t < n ? v[t] : 0;
-        const uint64_t bal = __ballot(keep[r]);
-        rank[r] = lanes_below(bal);
-        if ((threadIdx.x & 63) == 0) wcnt[r * (FIRST_T / 64) + wave] = (uint32_t)__popcll(bal);
-    }
-    __syncthreads();
-    const uint64_t first = pre[blockIdx.x];
-    uint32_t before = 0;
-    for (int r = 0; r < FIRST_ROUNDS; ++r)
-        for (uint32_t w = 0; w < FIRST_T / 64; ++w) {
-            if (w == wave && keep[r]) {
-                const uint64_t at = first + before + rank[r];
-                if (at < nkeys) { // (always: nkeys is the scan's total)
-                    keys[at] = x[r];
-                    post_off[at] = base + (uint64_t)(r * FIRST_T) + threadIdx.x;
-                }
-            }
-            before += wcnt[r * (FIRST_T / 64) + w];
-        }
+// KEEP_RUN's scatter over the sorted values: keys[j] = the j-th distinct value, post_off[j] = where it first stands, which is where its
+// posting list begins; a write lands below nkeys, the scan's total, only.  post_off[nkeys] = n.
+__global__ __launch_bounds__(KEEP_T) void k_index_keys(const uint64_t* __restrict__ v, uint64_t n, const uint64_t* __restrict__ pre,
+                                                       uint64_t* __restrict__ keys, uint64_t* __restrict__ post_off, uint64_t nkeys) {
+    keep_scatter_block<KEEP_RUN, true>(v, n, 0, nullptr, 0, pre, keys, post_off, nkeys);
     if (blockIdx.x == 0 && threadIdx.x == 0) post_off[nkeys] = n;
 }
 
@@ -124,15 +60,6 @@ __global__ __launch_bounds__(SEARCH_T) void k_longest_list(const uint64_t* __res
 }
 
 // ---- the search -----------------------------------------------------------------------------------------------------------
-// first index in [lo, hi) whose id is not below `bound` (hi when there is none); the list ascends; at most 32 halvings
-__device__ __forceinline__ uint64_t first_id_at_least(const uint32_t* __restrict__ post, uint64_t lo, uint64_t hi, uint32_t bound) {
-    while (lo < hi) {
-        const uint64_t mid = lo + ((hi - lo) >> 1);
-        if (post[mid] < bound) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
 // One workgroup per (query q, reference block b): workgroup w = q * nblk + b counts, for the references [b * RB, b * RB + nrb), how many
 // of q's values each holds, in LDS.  The query row is clamped to [0, q_nvalues]; every posting offset is clamped to npost; every id read
 // from post[] is checked against the block's range before it indexes the counters; w is checked before it indexes count[] / pre[];
@@ -157,23 +84,18 @@ __global__ __launch_bounds__(SEARCH_T) void k_search_block(const uint64_t* __res
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (uint32_t r = threadIdx.x; r < RB; r += SEARCH_T) cnt[r] = 0;
     __syncthreads();
-    const uint64_t q0 = min(qoff[q], q_nvalues);
-    uint64_t q1 = max(min(qoff[q + 1], q_nvalues), q0);
-    q1 = q0 + min(q1 - q0, (uint64_t)0x7fffffffu);
+    uint64_t q0, q1;
+    clamped_row(qoff, q, q_nvalues, q0, q1);
     for (uint64_t t0 = q0 + (uint64_t)wave * 64; t0 < q1; t0 += SEARCH_T) { // wave-uniform: every lane takes part in the ballots below
         const uint64_t t = t0 + lane;
         uint64_t p0 = 0, p1 = 0; // this lane's posting list, narrowed to the block
         if (t < q1) {
             const uint64_t x = qv[t];
-            uint32_t lo = 0, hi = nkeys; // first key >= x
-            while (lo < hi) {
-                const uint32_t mid = lo + ((hi - lo) >> 1);
-                if (keys[mid] < x) lo = mid + 1; else hi = mid;
-            }
+            const uint32_t lo = first_not_below(keys, 0u, nkeys, x);
             if (lo < nkeys && keys[lo] == x) {
                 const uint64_t a = min(post_off[lo], npost), e = max(min(post_off[lo + 1], npost), a);
-                p0 = first_id_at_least(post, a, e, base);
-                p1 = nrb == RB ? first_id_at_least(post, p0, e, base + nrb) : e; // (the last block: nothing valid lies beyond it)
+                p0 = first_not_below(post, a, e, base);
+                p1 = nrb == RB ? first_not_below(post, p0, e, base + nrb) : e; // (the last block: nothing valid lies beyond it)
             }
         }
         const bool wide = p1 - p0 >= 64;
@@ -186,8 +108,7 @@ __global__ __launch_bounds__(SEARCH_T) void k_search_block(const uint64_t* __res
         while (todo) {
             const int src = __ffsll((unsigned long long)todo) - 1;
             todo &= todo - 1;
-            const uint64_t s0 = ((uint64_t)(uint32_t)__shfl((int)(uint32_t)(p0 >> 32), src, 64) << 32) | (uint32_t)__shfl((int)(uint32_t)p0, src, 64);
-            const uint64_t s1 = ((uint64_t)(uint32_t)__shfl((int)(uint32_t)(p1 >> 32), src, 64) << 32) | (uint32_t)__shfl((int)(uint32_t)p1, src, 64);
+            const uint64_t s0 = shfl_u64(p0, src), s1 = shfl_u64(p1, src);
             for (uint64_t i = s0 + lane; i < s1; i += 64) {
                 const uint32_t rel = post[i] - base;
                 if (rel < nrb) atomicAdd(&cnt[rel], 1);
@@ -222,10 +143,6 @@ __global__ __launch_bounds__(SEARCH_T) void k_search_block(const uint64_t* __res
     }
 }
 
-uint32_t wave_grid(uint64_t nwaves_wanted) { // workgroups of SEARCH_WAVES waves for that many waves; the kernels stride beyond 2^16 of them
-    return (uint32_t)std::min<uint64_t>(std::max<uint64_t>((nwaves_wanted + SEARCH_WAVES - 1) / SEARCH_WAVES, 1), 1u << 16);
-}
-
 // The build on resident arrays, on stream st; synchronises it.  The scratch (ids, sorted values, the sort's own) is freed on return.
 int index_build(rk_scaled_index* ix, const uint64_t* d_values, const uint64_t* d_off, uint32_t nref, uint64_t nvalues, hipStream_t st) {
     ix->nref = nref;
@@ -237,7 +154,7 @@ int index_build(rk_scaled_index* ix, const uint64_t* d_values, const uint64_t* d
         // 1. the reference id of every value position
         RKCHK(s.ids.reserve((size_t)nvalues * 4));
         HIPCHK(hipMemsetAsync(s.ids.p, 0xff, (size_t)nvalues * 4, st));
-        hipLaunchKernelGGL(k_index_ids, dim3(wave_grid(nref)), dim3(SEARCH_T), 0, st, d_off, nref, nvalues, s.ids.as<uint32_t>());
+        hipLaunchKernelGGL(k_index_ids, dim3(wave_grid(nref, SEARCH_WAVES)), dim3(SEARCH_T), 0, st, d_off, nref, nvalues, s.ids.as<uint32_t>());
         HIPCHK(hipGetLastError());
         // 2. the pairs ordered by value; the sort is stable, so the ids of one value stay ascending
         size_t tmp_bytes = 0;
@@ -246,18 +163,14 @@ int index_build(rk_scaled_index* ix, const uint64_t* d_values, const uint64_t* d
         RKCHK(s.sorted.reserve((size_t)nvalues * 8));
         HIPCHK(launch_sort_pairs_u64_u32(d_values, s.sorted.as<uint64_t>(), s.ids.as<uint32_t>(), ix->post.as<uint32_t>(), nvalues, s.tmp.p, tmp_bytes, st));
         // 3. the first of every value is its key; where it stands is where its list begins
-        const uint64_t nblocks = (nvalues + FIRST_BLK - 1) / FIRST_BLK; // < 2^23: nvalues < 2^32
-        RKCHK(s.cnt.reserve((size_t)nblocks * 4));
-        RKCHK(s.pre.reserve((size_t)(nblocks + 1) * 8));
-        hipLaunchKernelGGL(k_first_count, dim3((uint32_t)nblocks), dim3(FIRST_T), 0, st, s.sorted.as<uint64_t>(), nvalues, s.cnt.as<uint32_t>());
-        hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(1024), 0, st, s.cnt.as<uint32_t>(), nblocks, s.pre.as<uint64_t>());
-        HIPCHK(hipGetLastError());
+        const uint64_t nblocks = (nvalues + KEEP_BLK - 1) / KEEP_BLK; // < 2^23: nvalues < 2^32
+        RKCHK(keep_counts<KEEP_RUN>(s.cnt, s.pre, s.sorted.as<uint64_t>(), nvalues, 0, nullptr, 0, nullptr, st));
         HIPCHK(hipMemcpyAsync(&nkeys, s.pre.as<uint64_t>() + nblocks, 8, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
         if (nkeys < 1 || nkeys > nvalues) return fail(RK_ERR_HIP, "scaled index: %llu keys of %llu values", (unsigned long long)nkeys, (unsigned long long)nvalues);
         RKCHK(ix->keys.reserve((size_t)nkeys * 8));
         RKCHK(ix->post_off.reserve((size_t)(nkeys + 1) * 8));
-        hipLaunchKernelGGL(k_first_scatter, dim3((uint32_t)nblocks), dim3(FIRST_T), 0, st, s.sorted.as<uint64_t>(), nvalues, s.pre.as<uint64_t>(),
+        hipLaunchKernelGGL(k_index_keys, dim3((uint32_t)nblocks), dim3(KEEP_T), 0, st, s.sorted.as<uint64_t>(), nvalues, s.pre.as<uint64_t>(),
                            ix->keys.as<uint64_t>(), ix->post_off.as<uint64_t>(), nkeys);
         const uint32_t lblocks = (uint32_t)std::min<uint64_t>((nkeys + SEARCH_T - 1) / SEARCH_T, 1024);
         uint32_t* d_max = s.ids.as<uint32_t>(); // (the sort is done with the ids; lblocks <= nvalues entries are there)
@@ -316,7 +229,7 @@ int search_count(rk_scaled_index* ix, const uint64_t* d_qv, const uint64_t* d_qo
     hipLaunchKernelGGL(k_search_block<false>, dim3(nwg), dim3(SEARCH_T), 0, st, ix->keys.as<uint64_t>(), (uint32_t)ix->nkeys, ix->post_off.as<uint64_t>(),
                        ix->post.as<uint32_t>(), ix->npost, ix->nref, d_qv, d_qo, nq, q_nvalues, (int32_t)min_shared, d_qmin, nblk, nwg, ix->w_cnt.as<uint32_t>(),
                        (const uint64_t*)nullptr, (int32_t*)nullptr, (uint64_t)0);
-    hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(1024), 0, st, ix->w_cnt.as<uint32_t>(), (uint64_t)nwg, ix->w_pre.as<uint64_t>());
+    hipLaunchKernelGGL(k_scan_blocks<uint32_t>, dim3(1), dim3(1024), 0, st, ix->w_cnt.as<uint32_t>(), (uint64_t)nwg, ix->w_pre.as<uint64_t>());
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(total, ix->w_pre.as<uint64_t>() + nwg, 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
@@ -363,21 +276,16 @@ extern "C" int rk_scaled_index_create_device(rk_ctx* c, const void* d_values, co
 extern "C" int rk_scaled_index_create(rk_ctx* c, const uint64_t* r_values, const uint64_t* r_offsets, int64_t nref, rk_scaled_index** idx) {
     RKCHK(check_index_shape(c, nref, idx));
     if (!r_offsets) return fail(RK_ERR_ARG, "bad arguments");
-    for (int64_t i = 0; i < nref; ++i) {
-        if (r_offsets[i + 1] < r_offsets[i]) return fail(RK_ERR_ARG, "scaled index: offsets of the references decrease at sketch %lld", (long long)i);
-        if (r_offsets[i + 1] - r_offsets[i] > 0x7fffffffull) return fail(RK_ERR_ARG, "scaled index: reference sketch %lld holds 2^31 values or more", (long long)i);
-    }
-    const uint64_t r0 = r_offsets[0], rn = r_offsets[nref] - r0; // the values the rows cover
+    RKCHK(check_csr(r_offsets, nref, "scaled index: ", "the references", RK_ERR_ARG));
+    const uint64_t rn = r_offsets[nref] - r_offsets[0]; // the values the rows cover
     if (rn && !r_values) return fail(RK_ERR_ARG, "bad arguments");
     RKCHK(check_values_limit(rn));
     RKCHK(set_dev(c));
     struct Up { DevBuf v, o; ~Up() { v.release(); o.release(); } } up;
     RKCHK(up.v.reserve((size_t)rn * 8 + 8));
     RKCHK(up.o.reserve(((size_t)nref + 1) * 8));
-    std::vector<uint64_t> off((size_t)nref + 1);
-    for (int64_t i = 0; i <= nref; ++i) off[(size_t)i] = r_offsets[i] - r0;
-    if (rn) HIPCHK(hipMemcpyAsync(up.v.p, r_values + r0, (size_t)rn * 8, hipMemcpyHostToDevice, c->st));
-    HIPCHK(hipMemcpyAsync(up.o.p, off.data(), ((size_t)nref + 1) * 8, hipMemcpyHostToDevice, c->st));
+    std::vector<uint64_t> off;
+    RKCHK(upload_csr(r_values, r_offsets, nref, up.v.as<uint64_t>(), up.o.as<uint64_t>(), off, c->st));
     return make_index(c, up.v.as<uint64_t>(), up.o.as<uint64_t>(), nref, rn, c->st, idx); // (synchronises: off lives until there)
 }
 
@@ -407,25 +315,21 @@ extern "C" int rk_search_scaled(rk_ctx* c, rk_scaled_index* ix, const uint64_t* 
     uint64_t nwg = 0, total = 0;
     uint32_t nblk = 0;
     RKCHK(check_search_shape(c, ix, nq, min_shared, &nwg, &nblk));
-    for (int64_t i = 0; i < nq; ++i) {
-        if (q_offsets[i + 1] < q_offsets[i]) return fail(RK_ERR_ARG, "search: offsets of the queries decrease at sketch %lld", (long long)i);
-        if (q_offsets[i + 1] - q_offsets[i] > 0x7fffffffull) return fail(RK_ERR_ARG, "search: query sketch %lld holds 2^31 values or more", (long long)i);
-        if (q_min && q_min[i] < 1) return fail(RK_ERR_ARG, "search: q_min %d of query %lld is below 1", q_min[i], (long long)i);
-    }
-    const uint64_t q0 = q_offsets[0], qn = q_offsets[nq] - q0;
+    RKCHK(check_csr(q_offsets, nq, "search: ", "the queries", RK_ERR_ARG));
+    for (int64_t i = 0; q_min && i < nq; ++i)
+        if (q_min[i] < 1) return fail(RK_ERR_ARG, "search: q_min %d of query %lld is below 1", q_min[i], (long long)i);
+    const uint64_t qn = q_offsets[nq] - q_offsets[0];
     if (qn && !q_values) return fail(RK_ERR_ARG, "bad arguments");
     RKCHK(set_dev(c));
     std::lock_guard<std::mutex> lk(ix->mu);
     RKCHK(ix->w_qv.reserve((size_t)qn * 8 + 8));
     RKCHK(ix->w_qo.reserve(((size_t)nq + 1) * 8));
     if (q_min) RKCHK(ix->w_qmin.reserve((size_t)nq * 4));
-    std::vector<uint64_t> off((size_t)nq + 1);
-    for (int64_t i = 0; i <= nq; ++i) off[(size_t)i] = q_offsets[i] - q0;
+    std::vector<uint64_t> off;
     const uint64_t* qv = ix->w_qv.as<uint64_t>();
     const uint64_t* qo = ix->w_qo.as<uint64_t>();
     const int32_t* qm = q_min ? ix->w_qmin.as<int32_t>() : nullptr;
-    if (qn) HIPCHK(hipMemcpyAsync(ix->w_qv.p, q_values + q0, (size_t)qn * 8, hipMemcpyHostToDevice, c->st));
-    HIPCHK(hipMemcpyAsync(ix->w_qo.p, off.data(), ((size_t)nq + 1) * 8, hipMemcpyHostToDevice, c->st));
+    RKCHK(upload_csr(q_values, q_offsets, nq, ix->w_qv.as<uint64_t>(), ix->w_qo.as<uint64_t>(), off, c->st));
     if (q_min) HIPCHK(hipMemcpyAsync(ix->w_qmin.p, q_min, (size_t)nq * 4, hipMemcpyHostToDevice, c->st));
     RKCHK(search_count(ix, qv, qo, (uint32_t)nq, qn, min_shared, qm, nblk, (uint32_t)nwg, c->st, &total)); // (synchronises: off lives until there)
     rk_search_hit* out = (rk_search_hit*)malloc(sizeof(rk_search_hit) * (size_t)std::max<uint64_t>(total, 1));

@@ -106,3 +106,36 @@ def posting_lists(length):
     queries = [np.array([long_v], dtype=np.uint64), np.unique(np.array([short_v, long_v], dtype=np.uint64)),
                np.unique(np.array([long_v, 1000 + 120], dtype=np.uint64))]
     return dict(refs=tuple(refs), queries=tuple(queries))
+
+
+KEY_TOTALS = (1, 63, 64, 65, 1023, 1024, 1025, 2049)   # entries of the sorted value array the index's keys are compacted from
+KEY_EDGES = (64, 1024)                                  # where a wave's 64 elements and a workgroup's 1 024 end in that compaction
+
+
+@functools.lru_cache(maxsize=None)
+def key_edges(total):
+    """-> dict(refs, nkeys, longest, runs): five references whose values, concatenated and sorted, are `total` entries laid out around
+    KEY_EDGES.  The first value and the last one are each held by two references (entries 0, 1 and total - 2, total - 1; at total = 1
+    they are one entry).  At every edge e a value held by three references stands at entries e - 2, e - 1, e wherever these lie
+    between the two pairs (total >= e + 3); at total = e + 1 the last value's pair itself lies across the edge, and below that the
+    edge is not reached.  Every other value is held by one reference.  The value of multiplicity m that is the i-th distinct one is
+    held by references i % 5 ... (i + m - 1) % 5; the last value is 2^64 - 1.  runs: entry where a repeated value begins -> its length."""
+    runs = {} if total < 2 else {0: 2, total - 2: 2}
+    for e in KEY_EDGES:
+        if total >= e + 3:
+            runs[e - 2] = 3
+    mult, t = [], 0
+    while t < total:
+        mult.append(runs.get(t, 1))
+        t += mult[-1]
+    assert t == total
+    values = (np.arange(1, len(mult) + 1, dtype=np.uint64) << np.uint64(20)) + np.uint64(3)
+    values[-1] = np.uint64((1 << 64) - 1)
+    rows = [[] for _ in range(5)]
+    for i, (v, m) in enumerate(zip(values, mult)):
+        for j in range(m):
+            rows[(i + j) % 5].append(v)
+    refs = tuple(np.array(r, dtype=np.uint64) for r in rows)
+    for a in refs:
+        a.setflags(write=False)
+    return dict(refs=refs, nkeys=len(mult), longest=max(mult), runs=runs)

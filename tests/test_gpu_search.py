@@ -138,6 +138,19 @@ def test_posting_lists_around_the_whole_wave_walk(ctx, length):
     idx.close()
 
 
+@pytest.mark.parametrize("total", sec.KEY_TOTALS)
+def test_keys_around_the_edges_of_the_compaction(ctx, total):
+    """the index's keys come out of the compaction that scaled sketches are kept with: repeated values across the end of a wave's and
+    of a workgroup's elements, at the first and at the last entry (the layout is proved by tests/test_search_cpu.py)"""
+    c = sec.key_edges(total)
+    idx = _index(ctx, c["refs"])
+    s = idx.stats()
+    assert s["nref"] == 5 and s["npost"] == total and s["nkeys"] == c["nkeys"] and s["longest_posting"] == c["longest"]
+    for ms in (1, 2):
+        _both_entries(idx, c["refs"], sem.search(c["refs"], c["refs"], ms), (total, ms), min_shared=ms)
+    idx.close()
+
+
 def test_equal_to_the_dense_path_on_the_panel(ctx):
     sk = sc.sketches("sourmash-k21", 10)                                                    # the 40 panel records
     assert len(sk) == 40

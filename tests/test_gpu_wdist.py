@@ -1,4 +1,4 @@
-"""Weighted comparison on the GPU: k_scaled_pairs_w<1 | 8 | 64> through rk_compare_scaled_abund and rk_compare_scaled_abund_device,
+"""Weighted comparison on the GPU: k_scaled_pairs<1 | 8 | 64, PairsWeighted> through rk_compare_scaled_abund and rk_compare_scaled_abund_device,
 k_abund_row_sums through rk_abund_row_sums and its _device form, and `rkmh dist --abund`, against tests/wdist_model.py -- everything
 integer, bit for bit.  What the shared inputs hold is shown on the model's output by tests/test_wdist_cpu.py."""
 import os

@@ -204,3 +204,25 @@ def test_manysearch_refusals(root, tmp_path):
     _refused(_run(root, "manysearch", "-g", "-R", sc10, "-Q", sc10), "-g")
     mixed = _sketch_file(tmp_path / "mixed.json", per_object_scaled=[10, 100])
     _refused(_run(root, "manysearch", "-R", mixed, "-f", fa), "disagree in scaled")
+
+
+@pytest.mark.parametrize("total", sec.KEY_TOTALS)
+def test_key_edge_cases_lie_where_they_say(total):
+    """the layout of search_cases.key_edges, read back from the sorted concatenation alone"""
+    c = sec.key_edges(total)
+    refs = c["refs"]
+    assert all((np.diff(r.astype(object)) > 0).all() for r in refs)                  # rows ascend and hold no value twice
+    flat = np.sort(np.concatenate(refs))
+    assert len(flat) == total
+    values, first, count = np.unique(flat, return_index=True, return_counts=True)
+    assert len(values) == c["nkeys"] and count.max() == c["longest"] == min(total, 2 + (total >= 67))
+    assert {int(f): int(n) for f, n in zip(first, count) if n > 1} == c["runs"]
+    if total > 1:
+        assert count[0] == 2 and count[-1] == 2                                       # the first and the last value: two references each
+    for e in sec.KEY_EDGES:                                                           # a repeated value lies across every edge that is reached
+        across = [(int(f), int(n)) for f, n in zip(first, count) if f < e < f + n]
+        assert across == ([(e - 2, 3)] if total >= e + 3 else [(e - 1, 2)] if total == e + 1 else []), (total, e)
+    want = sem.search(refs, refs)
+    assert len(want) >= sum(len(r) > 0 for r in refs)                                 # every reference with a value finds itself
+    _same(_host(refs, refs, threads=2), want, total)
+    _same(_host(refs, refs, min_shared=2, threads=2), sem.search(refs, refs, 2), (total, 2))

@@ -5,7 +5,7 @@ plain two-pointer loop on 16 host threads (GPU box).
     g++ -O3 -fopenmp -o tools/ubench/scaled_cpu tools/ubench/scaled_cpu.cpp      (built on first use when missing)
     python tools/bench_scaled.py [--n 2048] [--sizes 800,5000] [--runs 7] [--threads 16] [--cpu-runs 5]
     python tools/bench_scaled.py --abund [--n 2048] [--sizes 800,5000] [--runs 7] [--threads 16] [--cpu-runs 5]
-                                               (the weighted form, k_scaled_pairs_w, next to the plain launch at the same `lanes`; see below)
+                                               (the weighted form, k_scaled_pairs<L, PairsWeighted>, next to the plain launch at the same `lanes`; see below)
     python tools/bench_scaled.py --keep        (the keep step of the general path next to the hashing: RKMH_INDEX_TIMING lines on stderr)
     python tools/bench_scaled.py --keep [--abund] [--root <tree>]     (the same with abundances; --root: the tree whose package and library
                                                are loaded, this one by default -- for comparing two builds in one job)
