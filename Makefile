@@ -6,7 +6,7 @@ CSRC := rkmh_amd/csrc
 LIB := rkmh_amd/lib/librkmh_amd.so
 OBJS := $(CSRC)/rk_kernels.o $(CSRC)/rk_classify.o $(CSRC)/rk_kmer.o $(CSRC)/rk_count.o $(CSRC)/rk_call.o $(CSRC)/rk_sort.o $(CSRC)/rk_fastq.o $(CSRC)/rk_fasta.o $(CSRC)/rk_inflate.o $(CSRC)/rk_api.o $(CSRC)/rk_general.o $(CSRC)/rk_route.o $(CSRC)/rk_index.o $(CSRC)/rk_counters.o $(CSRC)/rk_frontend.o $(CSRC)/rk_gunzip.o $(CSRC)/rk_packed.o $(CSRC)/rk_pack.o $(CSRC)/rk_parse.o $(CSRC)/rk_format.o $(CSRC)/rk_synth.o $(CSRC)/rk_policy.o $(CSRC)/rk_pairs.o $(CSRC)/rk_pairs_host.o $(CSRC)/rk_scaled.o $(CSRC)/rk_scaled_host.o $(CSRC)/rk_gather.o $(CSRC)/rk_search.o
 
-API_DEPS := $(CSRC)/rk_api_internal.hpp $(CSRC)/rk_sets.hpp $(CSRC)/rk_kernels.hpp $(CSRC)/rk_device.hpp include/rkmh_amd.h
+API_DEPS := $(CSRC)/rk_api_internal.hpp $(CSRC)/rk_index_plan.hpp $(CSRC)/rk_sets.hpp $(CSRC)/rk_kernels.hpp $(CSRC)/rk_device.hpp include/rkmh_amd.h
 
 all: $(LIB) bin/rkmh oracle
 

@@ -4,6 +4,7 @@
 //   rk_general.hip   the general path (any length) as plan / upload and hash / count / sort / download, and the entry points that are one run of it
 //   rk_route.hip     the classify / count routing: fused kernels, re-routes through the general path, the double-buffered host pipeline
 //   rk_index.hip     reference sketches -> the resident index (buckets, postings, k-mer-space structures), depth filter masks
+//   rk_index_plan.hpp  the host-only half of an index build: every resident structure laid out in plain vectors (included by rk_index.hip alone)
 //   rk_counters.hip  HASHTCounter (full and compact), its (de)serialisation
 //   rk_frontend.hip  FASTQ slots (text parsed on the device), BGZF jobs inflated on the device, reference FASTA through the device
 //   rk_call.hip      `call`
@@ -138,7 +139,7 @@ struct rk_ctx {
     int kmer_cache_state = 0; // of the last index build: 0 no file given, 1 loaded, 2 enumerated and written, 3 enumerated (the file could not be written)
     RefIndex ix{};
     bool have_refs = false;
-    rk_index_stats_t istats{}; // rk_index_stats: which form each key of the index took, counted by build_index / build_kpost as they go
+    rk_index_stats_t istats{}; // rk_index_stats: which form each key of the index took, counted by the planning steps (rk_index_plan.hpp) as they go
     double density = 1.0; // fraction of a reference's k-mers that its sketch keeps (largest over references)
     std::mutex general_mu; // the general path (rerouted rows) works in the context's own buffers: FASTQ slots take turns
     // -M
@@ -273,6 +274,5 @@ struct GzScratch {
 int gzip_reserve(GzScratch& S, rk_ctx* c, uint64_t comp_bytes, uint64_t cap_out); // rk_gunzip.hip
 int gzip_next(rk_gzip* gz, GzScratch& S, rk_ctx* c, hipStream_t st, hipEvent_t ev, int64_t call, uint8_t* d_out, uint64_t cap_out, uint64_t* nbytes, uint64_t* text_off, bool raw = false); // rk_gunzip.hip
 int counter_settle(const rk_counter* k);                                                                    // rk_counters.hip
-int build_index(rk_ctx* c);                                                                                 // rk_index.hip
 int set_references_impl(rk_ctx* c, const uint8_t* bases, const uint8_t* d_bases, const uint64_t* offsets, int nref, const int* ks, int nks, int S,
                         int max_samples, uint64_t counter_slots);

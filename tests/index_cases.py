@@ -1,4 +1,4 @@
-"""Reference panels built key by key, so that every value form of the resident index (rk_index.hip, build_index / build_kpost) is
+"""Reference panels built key by key, so that every value form of the resident index (rk_index_plan.hpp: fill_hash_table / build_kpost, driven by build_index in rk_index.hip) is
 built on purpose and on both sides of the threshold that selects it, and read sets that show each such key to each of the three
 readers that decode the forms independently: accumulate_posting (the general path, rk_kernels.hip), the drain of k_classify_tile
 (rk_classify.hip) and the drain and phase 2 of k_classify_kmer (rk_kmer.hip).  tests/test_index_cases_cpu.py checks without a GPU
@@ -37,7 +37,7 @@ KS = [K]
 POL = tc.DEFAULT
 UNIT_LEN, UNIT_COPIES, RUN = 23, 40, 540
 SLOTS = 8                      # slots of a bucket (IDX_SLOTS)
-KBASE_MAX = 8                  # base lists of an index (rk_index.hip)
+KBASE_MAX = 8                  # base lists of an index (rk_index_plan.hpp)
 COUNT_SLOTS = 3000017          # depth map of the -M passes
 LONG_MIN, LONG_MAX = 1600, 2400
 HS_FORMS = ("single_once", "single_multi", "pair", "list")
@@ -46,7 +46,7 @@ KV_FORMS = ("reference", "single_multi", "pair", "inline", "base_inline", "base_
 
 # ---- the builder's rules, restated ---------------------------------------------------------------------------------------------------
 def hash_form(post):
-    """build_index: one reference with multiplicity <= 511 is stored inline; two references once each, both below 2048, as a pair of
+    """fill_hash_table (rk_index_plan.hpp): one reference with multiplicity <= 511 is stored inline; two references once each, both below 2048, as a pair of
     11-bit fields; anything else is a posting list"""
     refs = sorted(post)
     if len(refs) == 1 and post[refs[0]] <= 511:
@@ -67,7 +67,7 @@ Fill = collections.namedtuple("Fill", "nb stored overflowed longest_chain wrappe
 
 
 def bucket_fill(keys):
-    """build_index's table: keys in ascending order, home bucket = (h >> 32) & (buckets - 1), eight slots, then the next bucket (the
+    """fill_hash_table (rk_index_plan.hpp): keys in ascending order, home bucket = (h >> 32) & (buckets - 1), eight slots, then the next bucket (the
     bucket left behind gets its overflow flag).  .stored: key -> (home, bucket it lies in)"""
     nb = n_buckets(len(keys))
     used = [0] * nb
@@ -95,7 +95,7 @@ KmerForms = collections.namedtuple("KmerForms", "bases dropped form")
 
 
 def kmer_forms(panel):
-    """build_kpost and value_id_of: which lists become bases (the heaviest simple lists of >= 8 references, keys x references, none
+    """build_kpost and ValueTable::value_id_of (rk_index_plan.hpp): which lists become bases (the heaviest simple lists of >= 8 references, keys x references, none
     within max(4, size / 4) of a base already chosen, at most eight), whether the 5 % rule then clears them, and the form of every
     key's value: a list of 3 .. 6 references below 512 once each is inline; a simple list of >= 8 references whose nearest base lies
     at d with 2 (1 + d) <= size is (base, exceptions) -- inside the value up to eight exceptions (all below 512), else as a list"""

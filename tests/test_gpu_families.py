@@ -1,6 +1,6 @@
 """Panels of near-identical genomes (BASELINE config 3's shape: 61 Zika genomes, 21 HPV16 variants beside unrelated references).
 Most sketch hashes of a family are shared by most of its members, so the k-mer-space kernel stores their posting lists as
-(base list, exceptions) and expands each touched base once per read (rk_index.hip build_kpost, rk_kmer.hip phase 2).  Ties are the
+(base list, exceptions) and expands each touched base once per read (rk_index_plan.hpp build_kpost, rk_kmer.hip phase 2).  Ties are the
 rule here -- identical genomes score the same and the FIRST reference must win (rkmh.cpp:878) -- and every row must equal the
 oracle's, for every counter form (8-bit, 16-bit, sparse), with repeats inside reads, N runs, several k-mer sizes and -M."""
 import os

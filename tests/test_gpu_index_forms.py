@@ -140,6 +140,44 @@ def test_long_reads_through_the_general_path(orc, contexts, name, form):
     _report(P, rd.long, "%s form, long reads" % form, c.classify(qb, qo), _want(orc, name, "long"))
 
 
+def test_a_refused_setter_changes_nothing(orc, data_dir):
+    """rk_set_reference_sketches refuses a sketch length beyond S and a k beyond RK_MAX_K before anything in the context changes: the
+    rows of classify, index_stats() and get_reference_sketches() are those of the set before; on a fresh context nothing is set"""
+    import rkmh_amd
+    from rkmh_amd import api
+    refs = api.parse_files([os.path.join(data_dir, "all_pave_ref.fa.gz")])
+    rb, ro = refs["bases"], refs["offsets"]
+    two = [bytes(rb[int(ro[r]): int(ro[r]) + 3000]) for r in (0, 1)]
+    reads = [two[0][100:250], two[0][1500:1650], two[1][7:157], two[1][2000:2150]]
+    sk, ln = orc.sketch_refs(*orc.pack(two), [16], 1000, threads=1)
+    qb, qo = tc.pack(reads)
+    c = rkmh_amd.Context(0)
+    try:
+        c.set_reference_sketches(sk, ln, [16], 1000)
+        A, stats = c.classify(qb, qo), c.index_stats()
+        assert (A == orc.classify_stream(qb, qo, [16], 1000, sk, ln, threads=1)).all() and (A[:, 1] > 0).all()
+        ln500 = np.minimum(ln, 500)
+        long_ln = ln500.copy()
+        long_ln[0] = 501
+        for bad_ks, bad_ln in (([12], long_ln), ([65], ln500)):
+            with pytest.raises(rkmh_amd.RkmhError):
+                c.set_reference_sketches(sk[:, :500].copy(), bad_ln, bad_ks, 500)
+            assert (c.classify(qb, qo) == A).all()
+            assert c.index_stats() == stats
+            gsk, gln = c.get_reference_sketches()
+            assert gsk.shape == sk.shape and (gsk == sk).all() and (gln == ln).all()
+    finally:
+        c.close()
+    c = rkmh_amd.Context(0)
+    try:
+        with pytest.raises(rkmh_amd.RkmhError):
+            c.set_reference_sketches(sk[:, :500].copy(), long_ln, [12], 500)
+        with pytest.raises(rkmh_amd.RkmhError, match="rk_set_references"):
+            c.classify(qb, qo)
+    finally:
+        c.close()
+
+
 @pytest.mark.parametrize("form", FORMS)
 @pytest.mark.parametrize("name", ic.PANELS)
 def test_depth_filter_by_key(orc, contexts, name, form):
