@@ -868,6 +868,57 @@ int rk_search_scaled_host(const uint64_t* r_values, const uint64_t* r_offsets, i
                           int64_t nq, int min_shared, const int32_t* q_min, int threads, rk_search_hit** hits, uint64_t* nhits);
 int rk_search_min_count(double min_containment, uint64_t len, int32_t* t);
 
+/* ------------------------------------------------------------------------------------------------
+ * MULTIGATHER (`rkmh multigather`; what the sourmash family calls fastmultigather: GATHER for a batch of queries at once, through the
+ * inverted index of SEARCH).  These are this library's own definitions.
+ *   Inputs: a rk_scaled_index of the references; a query batch of nq rows in CSR (uint64 q_values[], uint64 q_offsets[nq + 1]), every
+ *   row ascending, distinct and non-zero -- rows may be empty, and rows may repeat one another; an optional uint32 q_abund[] parallel
+ *   to q_values, every entry >= 1; min_shared >= 1; max_rounds >= 1.
+ *   Answer: the rows of query i are EXACTLY the rows rk_gather_scaled gives for Q_i against the indexed references with the same
+ *   min_shared and max_rounds: (ref, unique, total, remaining), four int32; the pick is by the largest count, among equal counts the
+ *   lowest reference index; a query stops when its best count falls below min_shared, or after max_rounds rows.  With q_abund every
+ *   row also has a uint64 wunique as rk_gather_scaled_abund defines it.  Queries do not influence each other.  The output is compact:
+ *   uint64 row_offsets[nq + 1], the rows of query i at [row_offsets[i], row_offsets[i + 1]) in pick order, wunique parallel to the rows.
+ *   It follows that permuting the queries permutes the row blocks; that a query given twice gets the same rows twice; and that an
+ *   empty query, or a query with no candidate (no reference shares min_shared values with it), gets no row.
+ * rk_multigather_scaled: host arrays.  *rows4 and, when q_abund is given, *wunique are malloc'd (rk_free; never NULL on success);
+ * row_offsets (nq + 1 uint64) is the caller's; *nrows = row_offsets[nq].  The checks of rk_search_scaled, and those of rk_gather_scaled
+ * on every row: RK_ERR_ARG for a row that is not strictly ascending or holds 0, and for an abundance of 0.
+ * rk_multigather_scaled_device: resident arrays (q_nvalues = the number of uint64 behind d_q_values; d_q_abund NULL or q_nvalues
+ * uint32; d_out4 takes cap_rows rows of 16 bytes and d_wunique cap_rows uint64 -- d_wunique is used only with d_q_abund, and both may
+ * be NULL when cap_rows = 0; d_row_offsets nq + 1 uint64).  Writes the first min(total, cap_rows) rows in order, ALWAYS all of
+ * d_row_offsets, and returns the total in *nrows: the convention of rk_search_scaled_device.  It runs on hip_stream and SYNCHRONISES
+ * it, as rk_gather_scaled_device does: the number of candidates is read on the host before the state is laid out, and every group of
+ * RK_GATHER_BATCH rounds ends with a look at a 16-byte control word.  Query rows are clamped to [0, q_nvalues]; every index is checked
+ * before it is used; rows that are not ascending give meaningless rows and nothing worse.  The alive bytes lie parallel to d_q_values:
+ * query rows that share storage (possible only with offsets that do not ascend) share them, and then get meaningless rows and nothing
+ * worse.  This entry cannot check abundances cheaply: a 0 adds nothing.
+ * rk_multigather_scaled_host: host code, usable without a GPU (rk_scaled_host.cpp): the reference CSR instead of an index; the loop
+ * of rk_gather_scaled_host query after query, the queries shared among `threads` host threads (below 1: one); the same checks (and
+ * those of rk_gather_scaled_host on the references), the same arrays.
+ * All entries refuse (RK_ERR_ARG, a size beyond its limit RK_ERR_LIMIT) before anything is launched: NULL, nq < 1, min_shared < 1,
+ * max_rounds < 1, more than 2^31 - 1 rows on a side, more than 2^24 - 1 workgroups of the search (nq times the number of reference
+ * blocks), an index of another context.  More than 2^31 - 1 candidates -- (query, reference) pairs that share at least min_shared
+ * values, known after the counting pass -- give RK_ERR_LIMIT: send fewer queries per call.  The work buffers are the index's own, under
+ * its mutex, as the search's are: calls on one index take turns, and the context's structure is not touched.
+ * The kernels (rk_multigather.hip).  Candidates: k_search_block<false / true> at threshold min_shared; the hits of a query, ascending
+ * by reference, are its candidates, shared = total = the initial count.  k_mg_keypos stores once where every query value stands in
+ * keys.  A round is two launches for the whole batch: k_mg_pick, one workgroup per query, takes the maximum of (count << 32 |
+ * ~candidate position) and writes the row; k_mg_remove looks the pick up in the posting list of every alive value of its query, and
+ * on a match clears the value's byte, adds its abundance to the row's wunique and takes 1 from the count of every candidate of that
+ * query the posting list names.  THESE ARE INTEGER ATOMICS ON GLOBAL MEMORY (atomicSub, atomicAdd; the first in the sketch-set layer):
+ * integer adds commute, so the counts a pick reads, and with them the rows, never depend on the order of arrival; pick and remove are
+ * separate launches on one stream, so no pick reads counts a remove is still changing.  The last kernel, k_mg_pack, lays the rows out
+ * in query order. */
+int rk_multigather_scaled(rk_ctx* ctx, rk_scaled_index* idx, const uint64_t* q_values, const uint32_t* q_abund, const uint64_t* q_offsets,
+                          int64_t nq, int min_shared, int max_rounds, int32_t** rows4, uint64_t** wunique, uint64_t* row_offsets, uint64_t* nrows);
+int rk_multigather_scaled_device(rk_ctx* ctx, rk_scaled_index* idx, const void* d_q_values, const void* d_q_abund, const void* d_q_offsets,
+                                 int64_t nq, uint64_t q_nvalues, int min_shared, int max_rounds, void* d_out4, void* d_wunique, uint64_t cap_rows,
+                                 void* d_row_offsets, uint64_t* nrows, void* hip_stream);
+int rk_multigather_scaled_host(const uint64_t* r_values, const uint64_t* r_offsets, int64_t nref, const uint64_t* q_values, const uint32_t* q_abund,
+                               const uint64_t* q_offsets, int64_t nq, int min_shared, int max_rounds, int threads, int32_t** rows4,
+                               uint64_t** wunique, uint64_t* row_offsets, uint64_t* nrows);
+
 #ifdef __cplusplus
 }
 #endif

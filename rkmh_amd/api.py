@@ -277,6 +277,12 @@ _SIGS = {
     "rk_search_scaled_host": (C.c_int, [_u64p, _u64p, C.c_int64, _u64p, _u64p, C.c_int64, C.c_int, _i32p, C.c_int, C.POINTER(_i32p),
                                         C.POINTER(C.c_uint64)]),
     "rk_search_min_count": (C.c_int, [C.c_double, C.c_uint64, C.POINTER(C.c_int32)]),
+    "rk_multigather_scaled": (C.c_int, [C.c_void_p, C.c_void_p, _u64p, _u32p, _u64p, C.c_int64, C.c_int, C.c_int, C.POINTER(_i32p), C.POINTER(_u64p), _u64p,
+                                        C.POINTER(C.c_uint64)]),
+    "rk_multigather_scaled_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_uint64, C.c_int, C.c_int, C.c_void_p,
+                                               C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p]),
+    "rk_multigather_scaled_host": (C.c_int, [_u64p, _u64p, C.c_int64, _u64p, _u32p, _u64p, C.c_int64, C.c_int, C.c_int, C.c_int, C.POINTER(_i32p),
+                                             C.POINTER(_u64p), _u64p, C.POINTER(C.c_uint64)]),
 }
 
 
@@ -1060,6 +1066,42 @@ def search_min_count(min_containment, length):
     return int(t.value)
 
 
+def _multigather_args(q_values, q_offsets, q_abund, max_rounds):
+    """the query batch of a multigather, checked -> (values, offsets, abundances or None, nq, max_rounds, row_offsets uint64 [nq + 1])"""
+    q_values, q_offsets = _csr(q_values, q_offsets)
+    if q_abund is not None:
+        q_abund = _abund(q_abund, q_values)
+    nq = len(q_offsets) - 1
+    max_rounds = 0x7fffffff if max_rounds is None else int(max_rounds)   # no reference is picked twice: as many rows as there are candidates
+    return q_values, q_offsets, q_abund, nq, max_rounds, np.zeros(nq + 1, dtype=np.uint64)
+
+
+def _multigather_rows(lib, out, wu, n, weighted):
+    """the malloc'd answer of a multigather -> (int32 [n, 4], uint64 [n] or None); releases it"""
+    rows = np.ctypeslib.as_array(out, shape=(max(n, 1) * 4,))[: n * 4].copy().reshape(n, 4)
+    lib.rk_free(out)
+    w = None
+    if weighted:
+        w = np.ctypeslib.as_array(wu, shape=(max(n, 1),))[:n].copy()
+        lib.rk_free(wu)
+    return rows, w
+
+
+def multigather_scaled_host(r_values, r_offsets, q_values, q_offsets, q_abund=None, min_shared=1, max_rounds=None, threads=1):
+    """rk_multigather_scaled_host (host code, no GPU): gather_scaled_host for every row of the CSR query batch, the queries shared among
+    `threads` host threads -> (rows int32 [n, 4], row_offsets uint64 [nq + 1], wunique uint64 [n] or None): the rows of query i are
+    rows[row_offsets[i]:row_offsets[i + 1]], in pick order."""
+    r_values, r_offsets = _csr(r_values, r_offsets)
+    q_values, q_offsets, q_abund, nq, max_rounds, ro = _multigather_args(q_values, q_offsets, q_abund, max_rounds)
+    out, wu, n = _i32p(), _u64p(), C.c_uint64()
+    lib = load_library()
+    _chk(lib.rk_multigather_scaled_host(_p(r_values, C.c_uint64), _p(r_offsets, C.c_uint64), len(r_offsets) - 1, _p(q_values, C.c_uint64),
+                                        None if q_abund is None else _p(q_abund, C.c_uint32), _p(q_offsets, C.c_uint64), nq, int(min_shared), max_rounds,
+                                        int(threads), C.byref(out), C.byref(wu), _p(ro, C.c_uint64), C.byref(n)))
+    rows, w = _multigather_rows(lib, out, wu, int(n.value), q_abund is not None)
+    return rows, ro, w
+
+
 class ScaledIndex:
     """rk_scaled_index: the resident inverted index of a collection of scaled sketches (Context.scaled_index)."""
 
@@ -1105,6 +1147,34 @@ class ScaledIndex:
         _chk(self._lib.rk_search_scaled_device(self._ctx._h, self._h, C.c_void_p(d_q_values_ptr), C.c_void_p(d_q_offsets_ptr), int(nq),
                                                C.c_uint64(int(q_nvalues)), int(min_shared), C.c_void_p(d_q_min_ptr), C.c_void_p(d_hits_ptr),
                                                C.c_uint64(int(cap_hits)), C.byref(n), C.c_void_p(stream)))
+        return int(n.value)
+
+    def multigather(self, q_values, q_offsets, q_abund=None, min_shared=1, max_rounds=None):
+        """rk_multigather_scaled: Context.gather_scaled for every row of the CSR query batch against the indexed references, all
+        queries at once -> (rows int32 [n, 4], row_offsets uint64 [nq + 1], wunique uint64 [n] or None): the rows (reference, unique,
+        total, remaining) of query i are rows[row_offsets[i]:row_offsets[i + 1]], in pick order; with q_abund (uint32, one per value)
+        wunique as gather_scaled_abund gives it."""
+        q_values, q_offsets, q_abund, nq, max_rounds, ro = _multigather_args(q_values, q_offsets, q_abund, max_rounds)
+        out, wu, n = _i32p(), _u64p(), C.c_uint64()
+        _chk(self._lib.rk_multigather_scaled(self._ctx._h, self._h, _p(q_values, C.c_uint64), None if q_abund is None else _p(q_abund, C.c_uint32),
+                                             _p(q_offsets, C.c_uint64), nq, int(min_shared), max_rounds, C.byref(out), C.byref(wu), _p(ro, C.c_uint64),
+                                             C.byref(n)))
+        rows, w = _multigather_rows(self._lib, out, wu, int(n.value), q_abund is not None)
+        return rows, ro, w
+
+    def multigather_device(self, d_q_values_ptr, d_q_offsets_ptr, nq, q_nvalues, d_out4_ptr, d_row_offsets_ptr, cap_rows, d_q_abund_ptr=None,
+                           d_wunique_ptr=None, min_shared=1, max_rounds=None, stream=None):
+        """Resident CSR queries (raw device pointers; d_q_abund: q_nvalues uint32 or None; d_out4: cap_rows rows of 4 int32; d_wunique:
+        cap_rows uint64, with d_q_abund; d_row_offsets: nq + 1 uint64) -> the total number of rows; the first min(total, cap_rows) are
+        written, in order, and all of d_row_offsets.  Runs on `stream` (as for search_device) and synchronises it.  Query rows are
+        clamped to [0, q_nvalues] on the device."""
+        if stream is None:
+            stream = self._ctx.stream
+        n = C.c_uint64()
+        _chk(self._lib.rk_multigather_scaled_device(self._ctx._h, self._h, C.c_void_p(d_q_values_ptr), C.c_void_p(d_q_abund_ptr), C.c_void_p(d_q_offsets_ptr),
+                                                    int(nq), C.c_uint64(int(q_nvalues)), int(min_shared), 0x7fffffff if max_rounds is None else int(max_rounds),
+                                                    C.c_void_p(d_out4_ptr), C.c_void_p(d_wunique_ptr), C.c_uint64(int(cap_rows)), C.c_void_p(d_row_offsets_ptr),
+                                                    C.byref(n), C.c_void_p(stream)))
         return int(n.value)
 
 

@@ -9,11 +9,12 @@
 //   rk_frontend.hip  FASTQ slots (text parsed on the device), BGZF jobs inflated on the device, reference FASTA through the device
 //   rk_call.hip      `call`
 //   rk_pairs.hip     all-pairs comparison of bottom-S sketches
-//   rk_sets.hpp      what the three parts below share: clamped CSR rows, the lookup in an ascending array, 64-bit shuffles, the
+//   rk_sets.hpp      what the four parts below share: the index object, clamped CSR rows, the lookup in an ascending array, 64-bit shuffles, the
 //                    order-preserving compaction (k_keep_count, k_scan_blocks, k_keep_bounds, k_keep_scatter), checks and upload of a CSR side
 //   rk_scaled.hip    scaled sketches: the keep step of the general path, all-pairs intersection of variable-length sets, plain and weighted
 //   rk_gather.hip    gather: the greedy decomposition of a scaled sketch into reference sketches, its state resident across rounds
 //   rk_search.hip    search: the resident inverted index of scaled sketches (value -> references) and the thresholded search on it
+//   rk_multigather.hip  multigather: gather for a batch of queries through that index, counts kept up to date by integer atomics
 #pragma once
 #include "../../include/rkmh_amd.h"
 #include "rk_kernels.hpp"

@@ -180,6 +180,68 @@ extern "C" int rk_gather_scaled_abund_host(const uint64_t* q, const uint32_t* q_
     return gather_host(who, q, q_abund, nq, rv, roff, nref, min_shared, max_rounds, threads, out4, wunique, nrounds);
 }
 
+// ---- multigather on the host (include/rkmh_amd.h, "MULTIGATHER"): gather_host query after query -- `threads` host threads share the
+// queries, each runs the loop above on one thread -- and the rows of all queries laid end to end.
+extern "C" int rk_multigather_scaled_host(const uint64_t* rv, const uint64_t* roff, int64_t nref, const uint64_t* qv, const uint32_t* q_abund,
+                                          const uint64_t* qoff, int64_t nq, int min_shared, int max_rounds, int threads, int32_t** rows4,
+                                          uint64_t** wunique, uint64_t* row_offsets, uint64_t* nrows) {
+    const std::string who = "rk_multigather_scaled_host";
+    if (!roff || !qoff || !rows4 || !row_offsets || !nrows || (q_abund && !wunique)) return bad(who + ": bad arguments");
+    if (nref < 1 || nq < 1) return bad(who + ": need at least one sketch on each side");
+    if (min_shared < 1 || max_rounds < 1) return bad(who + ": min_shared and max_rounds must be at least 1");
+    if (nref > 0x7fffffffll || nq > 0x7fffffffll) { rk__set_error((who + ": more than 2^31-1 sketches on one side").c_str()); return RK_ERR_LIMIT; }
+    for (int64_t i = 0; i < nq; ++i) {
+        if (qoff[i + 1] < qoff[i]) return bad(who + ": offsets of the queries decrease at sketch " + std::to_string(i));
+        if (qoff[i + 1] - qoff[i] > 0x7fffffffull) return bad(who + ": sketch " + std::to_string(i) + " of the queries holds 2^31 values or more");
+    }
+    if (qoff[nq] > qoff[0] && !qv) return bad(who + ": values are NULL");
+    // every query is checked before any is gathered (the references: by the first gather_host below, before it computes anything)
+    for (int64_t i = 0; i < nq; ++i)
+        for (uint64_t t = qoff[i]; t < qoff[i + 1]; ++t) {
+            if (qv[t] == 0 || (t > qoff[i] && qv[t] <= qv[t - 1]))
+                return bad(who + ": query " + std::to_string(i) + " is not ascending, distinct and non-zero at value " + std::to_string(t - qoff[i]));
+            if (q_abund && q_abund[t] == 0) return bad(who + ": abundance 0 at value " + std::to_string(t - qoff[i]) + " of query " + std::to_string(i));
+        }
+    for (int64_t i = 0; i < nref; ++i) {
+        if (roff[i + 1] < roff[i]) return bad(who + ": offsets of the references decrease at sketch " + std::to_string(i));
+        if (roff[i + 1] - roff[i] > 0x7fffffffull) { rk__set_error((who + ": a reference sketch of 2^31 values or more").c_str()); return RK_ERR_LIMIT; }
+    }
+    if (roff[nref] > roff[0] && !rv) return bad(who + ": r_values is NULL");
+    const int cap = (int)std::min<int64_t>(max_rounds, nref); // rows of one query at most
+    std::vector<std::vector<int32_t>> rows((size_t)nq);
+    std::vector<std::vector<uint64_t>> wu((size_t)nq);
+    std::vector<int> code((size_t)nq, RK_OK);
+    on_threads((size_t)nq, threads, 1, [&](size_t lo, size_t hi) {
+        std::vector<int32_t> out4((size_t)cap * 4);
+        std::vector<uint64_t> w((size_t)cap);
+        for (size_t i = lo; i < hi; ++i) {
+            int n = 0;
+            code[i] = gather_host(who, qv + qoff[i], q_abund ? q_abund + qoff[i] : nullptr, qoff[i + 1] - qoff[i], rv, roff, (int)nref, min_shared, max_rounds, 1,
+                                  out4.data(), q_abund ? w.data() : nullptr, &n);
+            if (code[i] != RK_OK) return;
+            rows[i].assign(out4.begin(), out4.begin() + (size_t)n * 4);
+            if (q_abund) wu[i].assign(w.begin(), w.begin() + n);
+        }
+    });
+    for (int c : code)
+        if (c != RK_OK) return c; // (the thread's message may be another thread's: the checks above leave nothing for gather_host to refuse)
+    uint64_t total = 0;
+    for (int64_t i = 0; i < nq; ++i) { row_offsets[i] = total; total += rows[(size_t)i].size() / 4; }
+    row_offsets[nq] = total;
+    int32_t* out = (int32_t*)malloc(16 * (size_t)(total ? total : 1));
+    uint64_t* out_w = q_abund ? (uint64_t*)malloc(8 * (size_t)(total ? total : 1)) : nullptr;
+    if (!out || (q_abund && !out_w)) { free(out); free(out_w); rk__set_error((who + ": malloc").c_str()); return RK_ERR_NOMEM; }
+    for (int64_t i = 0; i < nq; ++i) {
+        const std::vector<int32_t>& r = rows[(size_t)i];
+        if (!r.empty()) memcpy(out + row_offsets[i] * 4, r.data(), r.size() * 4);
+        if (q_abund && !wu[(size_t)i].empty()) memcpy(out_w + row_offsets[i], wu[(size_t)i].data(), wu[(size_t)i].size() * 8);
+    }
+    *rows4 = out;
+    if (q_abund) *wunique = out_w;
+    *nrows = total;
+    return RK_OK;
+}
+
 // ---- search on the host (include/rkmh_amd.h, "SEARCH"): the inverted index of rk_search.hip from a stable sort of (value, reference)
 // pairs, then per query one counter per reference, the touched ones read out in ascending order.  Host memory: the index, one counter
 // array per thread and the hits -- never nq x nref.

@@ -4,16 +4,7 @@
 // measurements: DESIGN.md section 15.
 #include "rk_sets.hpp"
 
-struct rk_scaled_index {
-    rk_ctx* ctx = nullptr; // compared, never followed: the index may outlive its context
-    int device = 0;
-    uint32_t nref = 0, longest = 0;
-    uint64_t npost = 0, nkeys = 0;
-    DevBuf keys, post_off, post;
-    DevBuf w_cnt, w_pre, w_qv, w_qo, w_qmin, w_hits; // searches: per-workgroup hit counts, their scan, an uploaded query batch, its hits
-    std::mutex mu;
-};
-
+// (struct rk_scaled_index: rk_sets.hpp)
 namespace {
 
 constexpr int SEARCH_T = 256;                  // threads of a workgroup of every kernel here but the scan
@@ -210,20 +201,23 @@ int make_index(rk_ctx* c, const uint64_t* d_values, const uint64_t* d_off, int64
     return RK_OK;
 }
 
-int check_search_shape(const rk_ctx* c, const rk_scaled_index* ix, int64_t nq, int min_shared, uint64_t* nwg, uint32_t* nblk) {
-    if (ix->ctx != c) return fail(RK_ERR_ARG, "search: the index was made on another context");
-    if (nq < 1) return fail(RK_ERR_ARG, "search: need at least one query sketch, got %lld", (long long)nq);
-    if (min_shared < 1) return fail(RK_ERR_ARG, "search: min_shared %d is below 1", min_shared);
-    if (nq > 0x7fffffffll) return fail(RK_ERR_LIMIT, "search: %lld query sketches are more than 2^31-1", (long long)nq);
+} // namespace
+
+// ---- the steps of a search, shared with rk_multigather.hip (declared in rk_sets.hpp) ----------------------------------------------
+int rk::check_search_shape(const rk_ctx* c, const rk_scaled_index* ix, int64_t nq, int min_shared, uint64_t* nwg, uint32_t* nblk, const char* who) {
+    if (ix->ctx != c) return fail(RK_ERR_ARG, "%s: the index was made on another context", who);
+    if (nq < 1) return fail(RK_ERR_ARG, "%s: need at least one query sketch, got %lld", who, (long long)nq);
+    if (min_shared < 1) return fail(RK_ERR_ARG, "%s: min_shared %d is below 1", who, min_shared);
+    if (nq > 0x7fffffffll) return fail(RK_ERR_LIMIT, "%s: %lld query sketches are more than 2^31-1", who, (long long)nq);
     *nblk = (ix->nref + RB - 1) / RB;
     *nwg = (uint64_t)nq * *nblk;
-    if (*nwg > 0xffffffull) return fail(RK_ERR_LIMIT, "search: %lld queries x %u reference blocks are more workgroups than one launch takes", (long long)nq, *nblk);
+    if (*nwg > 0xffffffull) return fail(RK_ERR_LIMIT, "%s: %lld queries x %u reference blocks are more workgroups than one launch takes", who, (long long)nq, *nblk);
     return RK_OK;
 }
 
 // pass 1 and the scan on stream st -> *total (synchronises st); the caller holds ix->mu
-int search_count(rk_scaled_index* ix, const uint64_t* d_qv, const uint64_t* d_qo, uint32_t nq, uint64_t q_nvalues, int min_shared, const int32_t* d_qmin,
-                 uint32_t nblk, uint32_t nwg, hipStream_t st, uint64_t* total) {
+int rk::search_count(rk_scaled_index* ix, const uint64_t* d_qv, const uint64_t* d_qo, uint32_t nq, uint64_t q_nvalues, int min_shared, const int32_t* d_qmin,
+                 uint32_t nblk, uint32_t nwg, hipStream_t st, uint64_t* total, const char* who) {
     RKCHK(ix->w_cnt.reserve((size_t)nwg * 4));
     RKCHK(ix->w_pre.reserve(((size_t)nwg + 1) * 8));
     hipLaunchKernelGGL(k_search_block<false>, dim3(nwg), dim3(SEARCH_T), 0, st, ix->keys.as<uint64_t>(), (uint32_t)ix->nkeys, ix->post_off.as<uint64_t>(),
@@ -233,10 +227,10 @@ int search_count(rk_scaled_index* ix, const uint64_t* d_qv, const uint64_t* d_qo
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(total, ix->w_pre.as<uint64_t>() + nwg, 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    if (*total > (uint64_t)nq * ix->nref) return fail(RK_ERR_HIP, "search: %llu hits of %u x %u pairs", (unsigned long long)*total, nq, ix->nref);
+    if (*total > (uint64_t)nq * ix->nref) return fail(RK_ERR_HIP, "%s: %llu hits of %u x %u pairs", who, (unsigned long long)*total, nq, ix->nref);
     return RK_OK;
 }
-int search_emit(rk_scaled_index* ix, const uint64_t* d_qv, const uint64_t* d_qo, uint32_t nq, uint64_t q_nvalues, int min_shared, const int32_t* d_qmin,
+int rk::search_emit(rk_scaled_index* ix, const uint64_t* d_qv, const uint64_t* d_qo, uint32_t nq, uint64_t q_nvalues, int min_shared, const int32_t* d_qmin,
                 uint32_t nblk, uint32_t nwg, hipStream_t st, int32_t* d_hits, uint64_t cap_hits) {
     hipLaunchKernelGGL(k_search_block<true>, dim3(nwg), dim3(SEARCH_T), 0, st, ix->keys.as<uint64_t>(), (uint32_t)ix->nkeys, ix->post_off.as<uint64_t>(),
                        ix->post.as<uint32_t>(), ix->npost, ix->nref, d_qv, d_qo, nq, q_nvalues, (int32_t)min_shared, d_qmin, nblk, nwg, ix->w_cnt.as<uint32_t>(),
@@ -245,12 +239,10 @@ int search_emit(rk_scaled_index* ix, const uint64_t* d_qv, const uint64_t* d_qo,
     return RK_OK;
 }
 
-} // namespace
-
 extern "C" void rk_scaled_index_destroy(rk_scaled_index* ix) {
     if (!ix) return;
     hipError_t e = hipSetDevice(ix->device); (void)e;
-    for (DevBuf* b : {&ix->keys, &ix->post_off, &ix->post, &ix->w_cnt, &ix->w_pre, &ix->w_qv, &ix->w_qo, &ix->w_qmin, &ix->w_hits}) b->release();
+    for (DevBuf* b : {&ix->keys, &ix->post_off, &ix->post, &ix->w_cnt, &ix->w_pre, &ix->w_qv, &ix->w_qo, &ix->w_qmin, &ix->w_hits, &ix->w_mg, &ix->w_mg_io, &ix->w_mg_out}) b->release();
     delete ix;
 }
 
@@ -294,13 +286,13 @@ extern "C" int rk_search_scaled_device(rk_ctx* c, rk_scaled_index* ix, const voi
     if (!c || !ix || !d_q_offsets || !nhits || (!d_q_values && q_nvalues) || (!d_hits && cap_hits)) return fail(RK_ERR_ARG, "bad arguments");
     uint64_t nwg = 0, total = 0;
     uint32_t nblk = 0;
-    RKCHK(check_search_shape(c, ix, nq, min_shared, &nwg, &nblk));
+    RKCHK(check_search_shape(c, ix, nq, min_shared, &nwg, &nblk, "search"));
     RKCHK(set_dev(c));
     std::lock_guard<std::mutex> lk(ix->mu);
     hipStream_t st = (hipStream_t)hip_stream;
     const uint64_t* qv = (const uint64_t*)d_q_values;
     const uint64_t* qo = (const uint64_t*)d_q_offsets;
-    RKCHK(search_count(ix, qv, qo, (uint32_t)nq, q_nvalues, min_shared, (const int32_t*)d_q_min, nblk, (uint32_t)nwg, st, &total));
+    RKCHK(search_count(ix, qv, qo, (uint32_t)nq, q_nvalues, min_shared, (const int32_t*)d_q_min, nblk, (uint32_t)nwg, st, &total, "search"));
     if (total && cap_hits) {
         RKCHK(search_emit(ix, qv, qo, (uint32_t)nq, q_nvalues, min_shared, (const int32_t*)d_q_min, nblk, (uint32_t)nwg, st, (int32_t*)d_hits, cap_hits));
         HIPCHK(hipStreamSynchronize(st));
@@ -314,7 +306,7 @@ extern "C" int rk_search_scaled(rk_ctx* c, rk_scaled_index* ix, const uint64_t* 
     if (!c || !ix || !q_offsets || !hits || !nhits) return fail(RK_ERR_ARG, "bad arguments");
     uint64_t nwg = 0, total = 0;
     uint32_t nblk = 0;
-    RKCHK(check_search_shape(c, ix, nq, min_shared, &nwg, &nblk));
+    RKCHK(check_search_shape(c, ix, nq, min_shared, &nwg, &nblk, "search"));
     RKCHK(check_csr(q_offsets, nq, "search: ", "the queries", RK_ERR_ARG));
     for (int64_t i = 0; q_min && i < nq; ++i)
         if (q_min[i] < 1) return fail(RK_ERR_ARG, "search: q_min %d of query %lld is below 1", q_min[i], (long long)i);
@@ -331,7 +323,7 @@ extern "C" int rk_search_scaled(rk_ctx* c, rk_scaled_index* ix, const uint64_t* 
     const int32_t* qm = q_min ? ix->w_qmin.as<int32_t>() : nullptr;
     RKCHK(upload_csr(q_values, q_offsets, nq, ix->w_qv.as<uint64_t>(), ix->w_qo.as<uint64_t>(), off, c->st));
     if (q_min) HIPCHK(hipMemcpyAsync(ix->w_qmin.p, q_min, (size_t)nq * 4, hipMemcpyHostToDevice, c->st));
-    RKCHK(search_count(ix, qv, qo, (uint32_t)nq, qn, min_shared, qm, nblk, (uint32_t)nwg, c->st, &total)); // (synchronises: off lives until there)
+    RKCHK(search_count(ix, qv, qo, (uint32_t)nq, qn, min_shared, qm, nblk, (uint32_t)nwg, c->st, &total, "search")); // (synchronises: off lives until there)
     rk_search_hit* out = (rk_search_hit*)malloc(sizeof(rk_search_hit) * (size_t)std::max<uint64_t>(total, 1));
     if (!out) return fail(RK_ERR_NOMEM, "malloc of %llu hits", (unsigned long long)total);
     if (total) {

@@ -1,8 +1,31 @@
-// rk_sets.hpp -- what the parts that work on sets of scaled sketches (rk_scaled.hip, rk_gather.hip, rk_search.hip) share: rows of a
-// CSR side clamped on the device, the lookup in an ascending array, 64-bit shuffles, the order-preserving compaction, and the host
-// checks and upload of a CSR side.  Everything has internal linkage: each of the three compiles its own copy of what it uses.
+// rk_sets.hpp -- what the parts that work on sets of scaled sketches (rk_scaled.hip, rk_gather.hip, rk_search.hip, rk_multigather.hip)
+// share: the resident inverted index and the steps of a search on it (defined in rk_search.hip, used by rk_multigather.hip too), rows
+// of a CSR side clamped on the device, the lookup in an ascending array, 64-bit shuffles, the order-preserving compaction, and the host
+// checks and upload of a CSR side.  Everything in the unnamed namespace has internal linkage: each part compiles its own copy of what it uses.
 #pragma once
 #include "rk_api_internal.hpp"
+
+// ---- the resident inverted index (rk_search.hip builds and searches it; rk_multigather.hip gathers through it) -----------------
+struct rk_scaled_index {
+    rk_ctx* ctx = nullptr; // compared, never followed: the index may outlive its context
+    int device = 0;
+    uint32_t nref = 0, longest = 0;
+    uint64_t npost = 0, nkeys = 0;
+    DevBuf keys, post_off, post;
+    DevBuf w_cnt, w_pre, w_qv, w_qo, w_qmin, w_hits; // searches: per-workgroup hit counts, their scan, an uploaded query batch, its hits
+    DevBuf w_mg, w_mg_io, w_mg_out; // multigather: the state of one call (candidates, counts, key positions, alive bytes, rows); the host entry's row offsets and abundances; its packed answer
+    std::mutex mu;
+};
+namespace rk {
+// The steps of a search (rk_search.hip), for the entries there and for multigather; `who` begins the messages; the caller holds ix->mu.
+// search_count: pass 1 and the scan on stream st -> *total (synchronises st); ix->w_pre then holds, at entry q * nblk, how many hits
+// lie before query q's.  search_emit: pass 2, the hits in (query, reference) order as far as cap_hits.
+int check_search_shape(const rk_ctx* c, const rk_scaled_index* ix, int64_t nq, int min_shared, uint64_t* nwg, uint32_t* nblk, const char* who);
+int search_count(rk_scaled_index* ix, const uint64_t* d_qv, const uint64_t* d_qo, uint32_t nq, uint64_t q_nvalues, int min_shared, const int32_t* d_qmin,
+                 uint32_t nblk, uint32_t nwg, hipStream_t st, uint64_t* total, const char* who);
+int search_emit(rk_scaled_index* ix, const uint64_t* d_qv, const uint64_t* d_qo, uint32_t nq, uint64_t q_nvalues, int min_shared, const int32_t* d_qmin,
+                uint32_t nblk, uint32_t nwg, hipStream_t st, int32_t* d_hits, uint64_t cap_hits);
+}
 
 namespace {
 

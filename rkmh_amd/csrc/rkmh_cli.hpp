@@ -11,7 +11,7 @@
 //   rkmh_commands.cpp   the hashing policy and the help text; call and hash
 //   rkmh_sketch_json.cpp  the reader of the JSON sketches `sketch` writes (stream -R, dist, gather); stands alone
 //   rkmh_sketches.cpp   sketch sets: made from sequence files, written as JSON, loaded from -R / -Q files, cut to one scaled
-//   rkmh_compare.cpp    sketch, dist, gather and manysearch
+//   rkmh_compare.cpp    sketch, dist, gather, multigather and manysearch
 //   rkmh_hpv16.cpp      hpv16
 #pragma once
 #include <getopt.h>
@@ -153,6 +153,7 @@ int main_call(int argc, char** argv);
 int main_sketch(int argc, char** argv);
 int main_dist(int argc, char** argv);
 int main_gather(int argc, char** argv);
+int main_multigather(int argc, char** argv);
 int main_manysearch(int argc, char** argv);
 int main_hash(int argc, char** argv);
 int main_hpv16(int argc, char** argv);

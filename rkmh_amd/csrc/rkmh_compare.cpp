@@ -1,5 +1,5 @@
-// rkmh_compare.cpp -- the commands on sketch sets (rkmh_sketches.cpp): sketch writes them, dist compares all pairs, gather decomposes,
-// manysearch reports the pairs that match.
+// rkmh_compare.cpp -- the commands on sketch sets (rkmh_sketches.cpp): sketch writes them, dist compares all pairs, gather decomposes
+// one query after the other and multigather all at once, manysearch reports the pairs that match.
 #include <algorithm>
 
 #include "rkmh_cli.hpp"
@@ -256,11 +256,18 @@ static void help_gather() {
             "  abundance of those hashes, wunique / unique; abundances in -R files are ignored\n" HASH_POLICY_HELP);
 }
 static const CompareRules gather_rules = {"gather", "gather", "gather decomposes scaled ones (rkmh sketch --scaled)", true, nullptr};
-int main_gather(int argc, char** argv) {
+// what gather and multigather share: the switches, the refusals (all before a context exists), the run's two sides
+struct GatherRun {
     CompareInputs in;
-    int min_shared = 1, max_rounds = 0x7fffffff;
+    int min_shared = 1, max_rounds = 0x7fffffff, k = 0;
+    LoadedSides ld;
+    ScaledRun run;
+};
+static void start_gather_run(int argc, char** argv, const CompareRules& rules, void (*help)(), GatherRun& g) {
+    CompareInputs& in = g.in;
+    int &min_shared = g.min_shared, &max_rounds = g.max_rounds;
     bool min_ok = true, rounds_ok = true;
-    if (argc <= 2) { help_gather(); exit(1); }
+    if (argc <= 2) { help(); exit(1); }
     static struct option long_options[] = {COMPARE_OPTIONS, {"min-shared", required_argument, 0, 1006}, {"max-rounds", required_argument, 0, 1007}, {"abund", no_argument, 0, 1008}, {0, 0, 0, 0}};
     optind = 2;
     int c;
@@ -270,31 +277,56 @@ int main_gather(int argc, char** argv) {
             case 1006: min_ok = parse_at_least_1(optarg, min_shared); break;
             case 1007: rounds_ok = parse_at_least_1(optarg, max_rounds); break;
             case 1008: in.abund = true; break;
-            default: help_gather(); exit(1);
+            default: help(); exit(1);
         }
     }
-    LoadedSides ld;
-    ld.k = one_k(in, gather_rules);
-    if (in.S != 0) refuse(gather_rules, "-s makes bottom-s sketches, which cannot be decomposed; gather works on scaled ones (--scaled)");
-    if (in.scaled_given && !in.scaled_ok) refuse(gather_rules, "--scaled takes a number of at least 1");
-    if (!min_ok) refuse(gather_rules, "--min-shared takes a number of at least 1");
-    if (!rounds_ok) refuse(gather_rules, "--max-rounds takes a number of at least 1");
-    if (in.ref_files.empty() == in.ref_json.empty()) refuse(gather_rules, "references come from -r <fasta> ... or from -R <sketches.json> ..., one of the two");
-    if (in.query_files.empty() == in.query_json.empty()) refuse(gather_rules, "queries come from -f <fasta|fastq> ... or from -Q <sketches.json> ..., one of the two");
-    if (in.whole_files && in.ref_files.empty()) refuse(gather_rules, "-g says how -r files are sketched; sketches loaded with -R are what they are");
-    load_sketch_files(in, gather_rules, ld);
-    if (!in.scaled_given && ld.largest_scaled == 0) refuse(gather_rules, "no sketch file says at which scaled to sketch: give --scaled <n>");
-    const int k = run_k(gather_rules, ld.k);
-    ScaledRun run;
-    start_scaled_run(in, gather_rules, ld, k, run);
-    rk_ctx* ctx = run.ctx;
-    const ScaledSet &sr = run.refs, &sq = *run.queries;
+    LoadedSides& ld = g.ld;
+    ld.k = one_k(in, rules);
+    if (in.S != 0) refuse(rules, "-s makes bottom-s sketches, which cannot be decomposed; gather works on scaled ones (--scaled)");
+    if (in.scaled_given && !in.scaled_ok) refuse(rules, "--scaled takes a number of at least 1");
+    if (!min_ok) refuse(rules, "--min-shared takes a number of at least 1");
+    if (!rounds_ok) refuse(rules, "--max-rounds takes a number of at least 1");
+    if (in.ref_files.empty() == in.ref_json.empty()) refuse(rules, "references come from -r <fasta> ... or from -R <sketches.json> ..., one of the two");
+    if (in.query_files.empty() == in.query_json.empty()) refuse(rules, "queries come from -f <fasta|fastq> ... or from -Q <sketches.json> ..., one of the two");
+    if (in.whole_files && in.ref_files.empty()) refuse(rules, "-g says how -r files are sketched; sketches loaded with -R are what they are");
+    load_sketch_files(in, rules, ld);
+    if (!in.scaled_given && ld.largest_scaled == 0) refuse(rules, "no sketch file says at which scaled to sketch: give --scaled <n>");
+    g.k = run_k(rules, ld.k);
+    start_scaled_run(in, rules, ld, g.k, g.run);
+    const ScaledSet &sr = g.run.refs, &sq = *g.run.queries;
+    if (sr.names.size() > 0x7fffffffull) refuse(rules, "more than 2^31-1 reference sketches");
+    for (size_t i = 0; i < sq.names.size(); ++i)
+        if (sq.off[i + 1] - sq.off[i] > 0x7fffffffull) refuse(rules, "a query of more than 2^31-1 hashes");
+}
+// the lines of one query: its n rows (ref, unique, total, remaining), with wunique and the query's wtotal when the run carries abundances
+static void append_gather_rows(OutBuf& o, const char* cmd, const ScaledSet& sq, size_t i, const ScaledSet& sr, const int32_t* out4, int n, const uint64_t* wunique,
+                               uint64_t wtotal) {
+    const size_t nr = sr.names.size();
+    const uint64_t lq = sq.off[i + 1] - sq.off[i];
+    for (int t = 0; t < n; ++t) {
+        const int32_t* r = &out4[(size_t)t * 4];
+        const size_t ref = (size_t)r[0];
+        if (ref >= nr) { fprintf(stderr, "rkmh %s: row %d names reference %d of %zu\n", cmd, t, r[0], nr); exit(1); }
+        o.append(sq.names[i]);
+        o.appendf("\t%d\t", t + 1);
+        o.append(sr.names[ref]);
+        o.appendf("\t%d/%llu\t%d/%llu\t%d/%llu\t%d", r[1], (unsigned long long)lq, r[2], (unsigned long long)lq, r[2], (unsigned long long)(sr.off[ref + 1] - sr.off[ref]), r[3]);
+        if (wunique) o.appendf("\t%llu/%llu\t%.6g", (unsigned long long)wunique[(size_t)t], (unsigned long long)wtotal, (double)wunique[(size_t)t] / (double)r[1]);
+        o.append("\n");
+    }
+    o.end_row();
+}
+int main_gather(int argc, char** argv) {
+    GatherRun g;
+    start_gather_run(argc, argv, gather_rules, help_gather, g);
+    const CompareInputs& in = g.in;
+    const int min_shared = g.min_shared, max_rounds = g.max_rounds;
+    rk_ctx* ctx = g.run.ctx;
+    const ScaledSet &sr = g.run.refs, &sq = *g.run.queries;
     const size_t nq = sq.names.size(), nr = sr.names.size();
-    if (nr > 0x7fffffffull) refuse(gather_rules, "more than 2^31-1 reference sketches");
     // the references go to the device once; every query follows them into the same two arrays
     uint64_t longest = 0;
     for (size_t i = 0; i < nq; ++i) longest = std::max(longest, sq.off[i + 1] - sq.off[i]);
-    if (longest > 0x7fffffffull) refuse(gather_rules, "a query of more than 2^31-1 hashes");
     const int rows = (int)std::min<size_t>((size_t)max_rounds, nr);
     void *d_rv = nullptr, *d_ro = nullptr, *d_q = nullptr, *d_out = nullptr, *d_qa = nullptr, *d_wu = nullptr;
     CK(rk_device_alloc(ctx, sr.values.size() * 8, &d_rv));
@@ -324,22 +356,67 @@ int main_gather(int argc, char** argv) {
         } else
             CK(rk_gather_scaled_device(ctx, d_q, lq, d_rv, d_ro, (int)nr, sr.values.size(), min_shared, rows, d_out, &n, rk_ctx_stream(ctx)));
         CK(rk_device_download(ctx, out4.data(), d_out, (size_t)n * 16));
-        for (int t = 0; t < n; ++t) {
-            const int32_t* r = &out4[(size_t)t * 4];
-            const size_t ref = (size_t)r[0];
-            if (ref >= nr) { fprintf(stderr, "rkmh gather: row %d names reference %d of %zu\n", t, r[0], nr); exit(1); }
-            o.append(sq.names[i]);
-            o.appendf("\t%d\t", t + 1);
-            o.append(sr.names[ref]);
-            o.appendf("\t%d/%llu\t%d/%llu\t%d/%llu\t%d", r[1], (unsigned long long)lq, r[2], (unsigned long long)lq, r[2], (unsigned long long)(sr.off[ref + 1] - sr.off[ref]), r[3]);
-            if (in.abund) o.appendf("\t%llu/%llu\t%.6g", (unsigned long long)wunique[(size_t)t], (unsigned long long)wtotal, (double)wunique[(size_t)t] / (double)r[1]);
-            o.append("\n");
-        }
-        o.end_row();
+        append_gather_rows(o, "gather", sq, i, sr, out4.data(), n, in.abund ? wunique.data() : nullptr, wtotal);
     }
     o.flush();
     fflush(stdout);
     for (void* p : {d_rv, d_ro, d_q, d_out, d_qa, d_wu}) if (p) rk_device_free(ctx, p);
+    rk_ctx_destroy(ctx);
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------
+// multigather: gather for all queries at once (include/rkmh_amd.h, "MULTIGATHER").  The switches, the refusals and the lines are
+// gather's; the references become one resident inverted index (rk_scaled_index_create) and the queries go through
+// rk_multigather_scaled in as few calls as its limits allow -- queries do not influence each other, so the lines do not depend on
+// where the batch is cut.
+static void help_multigather() {
+    fprintf(stderr,
+            "rkmh multigather (-r <refs.fa> ... | -R <refs.json> ...) (-f <sample.fa|fq[.gz]> ... | -Q <queries.json> ...) [-k <k>] [--scaled <n>] [-g]\n"
+            "                 [--min-shared <n>] [--max-rounds <n>] [--abund] [--device <id>]\n"
+            "  `rkmh gather` for many queries at once: the same switches, the same lines, byte for byte; the references become one resident\n"
+            "  inverted index (hash -> the references that hold it) and all queries are decomposed together, a round of picks for the whole\n"
+            "  batch at a time, so the work follows the hashes the queries share with the references, not queries x references\n"
+            "  -f: every file is ONE query, the union of its records;  -Q: every sketch of the file is a query;  -r / -R, -g, --scaled,\n"
+            "  --min-shared, --max-rounds, --abund: as for `rkmh gather`\n" HASH_POLICY_HELP);
+}
+static const CompareRules multigather_rules = {"multigather", "multigather", "multigather decomposes scaled ones (rkmh sketch --scaled)", true, nullptr};
+int main_multigather(int argc, char** argv) {
+    GatherRun g;
+    start_gather_run(argc, argv, multigather_rules, help_multigather, g);
+    rk_ctx* ctx = g.run.ctx;
+    const ScaledSet &sr = g.run.refs, &sq = *g.run.queries;
+    const size_t nq = sq.names.size(), nr = sr.names.size();
+    rk_scaled_index* idx = nullptr;
+    CK(rk_scaled_index_create(ctx, sr.values.data(), sr.off.data(), (int64_t)nr, &idx));
+    // queries per call: the search's workgroup limit (queries x reference blocks below 2^24), and at most 2^31 - 1 candidates, of
+    // which a query has nr at most
+    const uint64_t nblk = (nr + RK_SEARCH_REF_BLOCK - 1) / RK_SEARCH_REF_BLOCK;
+    const size_t per_call = (size_t)std::max<uint64_t>(1, std::min<uint64_t>(0xffffffull / nblk, 0x7fffffffull / nr));
+    std::vector<uint64_t> row_off;
+    OutBuf o(stdout);
+    for (size_t q0 = 0; q0 < nq; q0 += per_call) {
+        const size_t n = std::min(per_call, nq - q0);
+        row_off.assign(n + 1, 0);
+        int32_t* rows = nullptr;
+        uint64_t* wunique = nullptr;
+        uint64_t nrows = 0;
+        CK(rk_multigather_scaled(ctx, idx, sq.values.data(), g.in.abund ? sq.abund.data() : nullptr, sq.off.data() + q0, (int64_t)n, g.min_shared, g.max_rounds,
+                                 &rows, &wunique, row_off.data(), &nrows));
+        for (size_t i = 0; i < n; ++i) {
+            const uint64_t a = row_off[i], b = row_off[i + 1];
+            if (a > b || b > nrows || b - a > nr) { fprintf(stderr, "rkmh multigather: query %zu has rows %llu .. %llu of %llu\n", q0 + i, (unsigned long long)a, (unsigned long long)b, (unsigned long long)nrows); exit(1); }
+            uint64_t wtotal = 0;
+            if (g.in.abund)
+                for (uint64_t j = sq.off[q0 + i]; j < sq.off[q0 + i + 1]; ++j) wtotal += sq.abund[j];
+            append_gather_rows(o, "multigather", sq, q0 + i, sr, rows + a * 4, (int)(b - a), g.in.abund ? wunique + a : nullptr, wtotal);
+        }
+        rk_free(rows);
+        if (wunique) rk_free(wunique);
+    }
+    o.flush();
+    fflush(stdout);
+    rk_scaled_index_destroy(idx);
     rk_ctx_destroy(ctx);
     return 0;
 }

@@ -36,6 +36,7 @@ int main(int argc, char** argv) {
     if (cmd == "sketch") return main_sketch(argc, argv);
     if (cmd == "dist") return main_dist(argc, argv);
     if (cmd == "gather") return main_gather(argc, argv);
+    if (cmd == "multigather") return main_multigather(argc, argv);
     if (cmd == "manysearch") return main_manysearch(argc, argv);
     if (cmd == "pack") return main_pack(argc, argv);
     if (cmd == "hpv16") return main_hpv16(argc, argv);
