@@ -919,6 +919,64 @@ int rk_multigather_scaled_host(const uint64_t* r_values, const uint64_t* r_offse
                                const uint64_t* q_offsets, int64_t nq, int min_shared, int max_rounds, int threads, int32_t** rows4,
                                uint64_t** wunique, uint64_t* row_offsets, uint64_t* nrows);
 
+/* ------------------------------------------------------------------------------------------------
+ * SAMPLE SKETCHES (the -g / one-sketch-per-file side of `rkmh sketch --scaled`, `gather`, `multigather`: the one scaled sketch of a
+ * whole read set, built on the device).  These are this library's own definitions.
+ *   A sample is one abundance sketch at (ks, the context's policy, max_hash) that reads are ADDED to.  After any sequence of adds it
+ *   equals rk_merge_scaled_abund over the rk_sketch_scaled_abund_batch rows of every sequence fed, at the same ks, policy and
+ *   max_hash, bit for bit: values ascending, distinct, 0 < h <= max_hash; abund[j] = the number of windows, over all sequences fed,
+ *   that hash to values[j], saturating at 2^32 - 1.  A sample created without abundances holds the same values and no abund array.
+ *   The result never depends on batch boundaries, the order of the feeds, pending_cap or the number of folds.
+ *   On the device the sample is a resident distinct set (values, counts) and, behind it, a PENDING array of kept window hashes.  A
+ *   feed (k_sample_keep, rk_sample.hip) treats the batch's bases as one piece cut into tiles of 2048 window positions, stages a tile
+ *   in LDS, marks the read starts that fall into it, hashes every position that is a window of its read -- a window that crosses a
+ *   read start is none, a read has len - k or len - k + 1 windows as the policy says, a window with an invalid base hashes to 0 and 0
+ *   is never kept -- and appends the hashes 0 < h <= max_hash to the pending array: compacted with wave ballots in LDS, then one
+ *   64-bit atomicAdd on a device cursor per flush of a workgroup (integer atomics on global memory, as in MULTIGATHER; the array is
+ *   sorted afterwards, so the order of arrival never reaches the result).  The window hashes of the batch are never written out.
+ *   Every store is guarded by position + count <= capacity and the cursor always advances: after a feed the host reads the cursor
+ *   (the one look a feed needs).  Beyond the capacity, the cursor is set back to where the batch began, the values from before are
+ *   folded, the pending array grows to what the cursor asked for and the batch runs again: nothing is lost, nothing counted twice.
+ *   A FOLD unites pending and resident: (value, count) pairs, pending ones with count 1, are radix-sorted by value, the first of every
+ *   run is kept (the order-preserving compaction of the sketch-set layer) and k_run_sums adds each run's counts, saturating at
+ *   2^32 - 1.  Without abundances only the values are sorted.  A fold synchronises.
+ * rk_sample_create: pending_cap = values the pending array holds; 0 = the library's default (2^22 values, 32 MB); any other value is
+ *   taken as given, down to 1 (it grows when one batch needs more).  RK_ERR_ARG / RK_ERR_LIMIT for NULL, nks outside 1 .. RK_MAX_KS, a k
+ *   outside 1 .. RK_MAX_K, max_hash = 0.  The sample uses the policy its context has at each feed and is used with that context only;
+ *   destroy it before the context.
+ * rk_sample_add_batch: host arrays as for rk_hash_batch; refuses offsets that decrease and a sequence of 2^31 bases or more.  The
+ *   bases are uploaded in pieces of whole sequences (about 64 MB; a longer sequence alone in its piece) on the context's stream.
+ * rk_sample_add_batch_device: resident bases and uint32 offsets[nseq + 1], the form rk_count_batch_device takes, any read lengths;
+ *   runs on hip_stream (NULL = HIP's null stream) and SYNCHRONISES it for the look at the cursor.  Offsets that do not ascend give a
+ *   meaningless sample and no store outside the sample's arrays; the bases from offsets[0] to offsets[nseq] (and up to three bytes
+ *   beyond, to the next dword) must be readable.
+ * rk_sample_add_sketch: unites an abundance sketch (ascending, distinct, non-zero values; abundances >= 1: the checks of
+ *   rk_merge_scaled_abund) into the sample; values above max_hash are cut off.  abund may be NULL only for a sample without abundances;
+ *   such a sample ignores abundances that are given and adds one per value to `kept`.
+ * rk_fastq_slot_sample: rk_fastq_slot_count's steps on a block of raw FASTQ text, then a feed from the slot's packed bases.
+ *   *status != 0: the block is not four lines per record and NOTHING of it was added.  The only slot entry that works on a context
+ *   without references.  RK_ERR_ARG for a sample of another context.
+ * rk_sample_finish: folds what is pending; *values and, for a sample with abundances, *abund are malloc'd (rk_free; never NULL on
+ *   success), *n their length.  The sample stays usable.  abund may be NULL for a sample without abundances.
+ * rk_sample_device: folds, then gives the resident arrays (uint64 values, uint32 abundances or NULL): valid until the next add, reset
+ *   or destroy; what rk_gather_scaled_device and rk_multigather_scaled_device take as a query, without a round trip.
+ * rk_sample_stats: the caller sets out->struct_size as for rk_index_stats.  nseq, nbases: sequences and bases fed (a refused FASTQ
+ *   block adds none); kept: windows kept = the unsaturated sum of the abundances; distinct: the length after the last fold; folds,
+ *   retries: folds done, batches run a second time.
+ * rk_sample_reset: an empty sample again, its arrays kept.  Calls on one sample take turns. */
+typedef struct rk_sample rk_sample;
+typedef struct rk_sample_stats_t { uint32_t struct_size, folds, retries, reserved; uint64_t nseq, nbases, kept, distinct; } rk_sample_stats_t;
+int rk_sample_create(rk_ctx* ctx, const int* ks, int nks, uint64_t max_hash, int with_abund, uint64_t pending_cap, rk_sample** out);
+void rk_sample_destroy(rk_sample* sample);
+int rk_sample_reset(rk_sample* sample);
+int rk_sample_add_batch(rk_sample* sample, const uint8_t* bases, const uint64_t* offsets, int64_t nseq);
+int rk_sample_add_batch_device(rk_sample* sample, const void* d_bases, const void* d_offsets_u32, int64_t nseq, void* hip_stream);
+int rk_sample_add_sketch(rk_sample* sample, const uint64_t* values, const uint32_t* abund, uint64_t n);
+int rk_fastq_slot_sample(rk_fastq_slot* slot, uint64_t nbytes, rk_sample* sample, int32_t* status, int64_t* nrec);
+int rk_sample_finish(rk_sample* sample, uint64_t** values, uint32_t** abund, uint64_t* n);
+int rk_sample_device(rk_sample* sample, const void** d_values, const void** d_abund, uint64_t* n);
+int rk_sample_stats(rk_sample* sample, rk_sample_stats_t* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -283,6 +283,17 @@ _SIGS = {
                                                C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p]),
     "rk_multigather_scaled_host": (C.c_int, [_u64p, _u64p, C.c_int64, _u64p, _u32p, _u64p, C.c_int64, C.c_int, C.c_int, C.c_int, C.POINTER(_i32p),
                                              C.POINTER(_u64p), _u64p, C.POINTER(C.c_uint64)]),
+    # the sample accumulator: include/rkmh_amd.h "SAMPLE SKETCHES"
+    "rk_sample_create": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int, C.c_uint64, C.c_int, C.c_uint64, C.POINTER(C.c_void_p)]),
+    "rk_sample_destroy": (None, [C.c_void_p]),
+    "rk_sample_reset": (C.c_int, [C.c_void_p]),
+    "rk_sample_add_batch": (C.c_int, [C.c_void_p, _u8p, _u64p, C.c_int64]),
+    "rk_sample_add_batch_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "rk_sample_add_sketch": (C.c_int, [C.c_void_p, _u64p, _u32p, C.c_uint64]),
+    "rk_fastq_slot_sample": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+    "rk_sample_finish": (C.c_int, [C.c_void_p, C.POINTER(_u64p), C.POINTER(_u32p), C.POINTER(C.c_uint64)]),
+    "rk_sample_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
+    "rk_sample_stats": (C.c_int, [C.c_void_p, C.c_void_p]),
 }
 
 
@@ -625,6 +636,26 @@ class FastqSlot:
         st, nrec = C.c_int32(), C.c_int64()
         _chk(self._lib.rk_fastq_slot_count(self._h, n, counter._h, C.byref(st), C.byref(nrec)))
         return st.value, nrec.value
+
+    def sample(self, text, sample):
+        """A block into a Sample (rk_fastq_slot_sample): returns (status, records); status != 0: nothing of it was added.  text: bytes,
+        or -- for a slot whose block was named with set_source or loaded on the device -- the number of bytes."""
+        if isinstance(text, (bytes, bytearray)):
+            n = len(text)
+            if n > self.max_bytes:
+                raise ValueError("block larger than the slot")
+            if self.device_text:
+                raise ValueError("a device-text slot takes its block from set_source or load_bgzf: pass the number of bytes")
+            C.memmove(self._lib.rk_fastq_slot_text(self._h), bytes(text), n)
+        else:
+            n = int(text)
+        st, nrec = C.c_int32(), C.c_int64()
+        _chk(self._lib.rk_fastq_slot_sample(self._h, n, sample._h, C.byref(st), C.byref(nrec)))
+        return st.value, nrec.value
+
+    def set_source(self, address):
+        """rk_fastq_slot_set_source: the next block is read from caller memory at `address` (valid until the block's call has returned)."""
+        _chk(self._lib.rk_fastq_slot_set_source(self._h, C.c_void_p(address)))
 
     # -- the zero-copy forms the one-process-per-GPU front end uses (rkmh_amd/cli.py): the caller reads file bytes straight into the
     # slot's page-locked buffer and the output text is formatted in C from the result where it lies
@@ -1261,6 +1292,87 @@ def angular_similarity(dot, sumsq_a, sumsq_b):
     return c.value, a.value
 
 
+class SampleStats(C.Structure):
+    """rk_sample_stats_t (rkmh_amd.h, "SAMPLE SKETCHES")"""
+    _fields_ = [("struct_size", C.c_uint32), ("folds", C.c_uint32), ("retries", C.c_uint32), ("reserved", C.c_uint32), ("nseq", C.c_uint64),
+                ("nbases", C.c_uint64), ("kept", C.c_uint64), ("distinct", C.c_uint64)]
+
+
+class Sample:
+    """rk_sample: one scaled sketch, with or without abundances, accumulated on the device from the reads fed to it (Context.sample)."""
+
+    def __init__(self, ctx, ks, max_hash, abund=False, pending_cap=0):
+        self._ctx, self._lib = ctx, ctx._lib
+        self.abund = bool(abund)
+        ks = _ks(ks)
+        self._h = C.c_void_p()
+        _chk(self._lib.rk_sample_create(ctx._h, _p(ks, C.c_int), len(ks), C.c_uint64(int(max_hash)), 1 if abund else 0, C.c_uint64(int(pending_cap)),
+                                        C.byref(self._h)))
+
+    def add(self, bases, offsets):
+        """rk_sample_add_batch: host bases (uint8) and uint64 offsets[n + 1]; refuses offsets that reach past the bases."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        if offsets.ndim != 1 or len(offsets) < 1:
+            raise ValueError("offsets must hold n + 1 entries")
+        bases = np.frombuffer(bases, dtype=np.uint8) if isinstance(bases, (bytes, bytearray)) else np.ascontiguousarray(bases, dtype=np.uint8)
+        if int(offsets.max()) > len(bases):
+            raise ValueError("offsets reach past the %d bases" % len(bases))
+        _chk(self._lib.rk_sample_add_batch(self._h, _p(bases, C.c_uint8), _p(offsets, C.c_uint64), len(offsets) - 1))
+
+    def add_device(self, d_bases_ptr, d_offsets_ptr, nseq, stream=None):
+        """rk_sample_add_batch_device: resident bases and uint32 offsets[nseq + 1]; synchronises the stream."""
+        _chk(self._lib.rk_sample_add_batch_device(self._h, C.c_void_p(d_bases_ptr), C.c_void_p(d_offsets_ptr), int(nseq), C.c_void_p(stream or 0)))
+
+    def add_sketch(self, values, abund=None):
+        """rk_sample_add_sketch: an abundance sketch (or, for a sample without abundances, a plain one) united into the sample."""
+        values = np.ascontiguousarray(values, dtype=np.uint64)
+        if values.ndim != 1:
+            raise ValueError("values must be one-dimensional")
+        if abund is not None:
+            abund = _abund(abund, values)
+        _chk(self._lib.rk_sample_add_sketch(self._h, _p(values, C.c_uint64), None if abund is None else _p(abund, C.c_uint32), len(values)))
+
+    def finish(self):
+        """rk_sample_finish -> (values uint64, abund uint32 or None); the sample stays usable."""
+        out, oa, n = _u64p(), _u32p(), C.c_uint64()
+        _chk(self._lib.rk_sample_finish(self._h, C.byref(out), C.byref(oa), C.byref(n)))
+        m = int(n.value)
+        r = np.ctypeslib.as_array(out, shape=(max(m, 1),))[:m].copy()
+        self._lib.rk_free(out)
+        a = None
+        if self.abund:
+            a = np.ctypeslib.as_array(oa, shape=(max(m, 1),))[:m].copy()
+            self._lib.rk_free(oa)
+        return r, a
+
+    def device(self):
+        """rk_sample_device -> (device pointer of the values, of the abundances or None, n): valid until the next add, reset or close."""
+        dv, da, n = C.c_void_p(), C.c_void_p(), C.c_uint64()
+        _chk(self._lib.rk_sample_device(self._h, C.byref(dv), C.byref(da), C.byref(n)))
+        return dv.value, da.value, int(n.value)
+
+    def stats(self):
+        """-> dict(folds, retries, nseq, nbases, kept, distinct)"""
+        s = SampleStats()
+        s.struct_size = C.sizeof(SampleStats)
+        _chk(self._lib.rk_sample_stats(self._h, C.byref(s)))
+        return {k: int(getattr(s, k)) for k in ("folds", "retries", "nseq", "nbases", "kept", "distinct")}
+
+    def reset(self):
+        _chk(self._lib.rk_sample_reset(self._h))
+
+    def close(self):
+        if self._h:
+            self._lib.rk_sample_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Context:
     """One GPU. Methods are named after the reference's functions they replace."""
 
@@ -1415,6 +1527,10 @@ class Context:
         self._lib.rk_free(out)
         self._lib.rk_free(oa)
         return r, a, so
+
+    def sample(self, ks, max_hash, abund=False, pending_cap=0):
+        """rk_sample_create: an empty Sample at (ks, this context's policy, max_hash); pending_cap 0 = the library's default."""
+        return Sample(self, ks, max_hash, abund=abund, pending_cap=pending_cap)
 
     def compare_scaled(self, a_values, a_offsets, b_values=None, b_offsets=None, lanes=0):
         """rk_compare_scaled: every CSR sketch of `a` against every one of `b` (None: of `a` itself) -> int32 [na, nb], the number

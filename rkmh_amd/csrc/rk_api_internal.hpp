@@ -15,6 +15,7 @@
 //   rk_gather.hip    gather: the greedy decomposition of a scaled sketch into reference sketches, its state resident across rounds
 //   rk_search.hip    search: the resident inverted index of scaled sketches (value -> references) and the thresholded search on it
 //   rk_multigather.hip  multigather: gather for a batch of queries through that index, counts kept up to date by integer atomics
+//   rk_sample.hip    the sample accumulator: one scaled sketch built on the device from reads fed batch by batch (fused hash-and-keep, folds)
 #pragma once
 #include "../../include/rkmh_amd.h"
 #include "rk_kernels.hpp"
@@ -274,6 +275,13 @@ struct GzScratch {
 };
 int gzip_reserve(GzScratch& S, rk_ctx* c, uint64_t comp_bytes, uint64_t cap_out); // rk_gunzip.hip
 int gzip_next(rk_gzip* gz, GzScratch& S, rk_ctx* c, hipStream_t st, hipEvent_t ev, int64_t call, uint8_t* d_out, uint64_t cap_out, uint64_t* nbytes, uint64_t* text_off, bool raw = false); // rk_gunzip.hip
+// the sample accumulator (rk_sample.hip) as the FASTQ slots feed it: the context it was made on; one resident batch (rk_sample_add_batch_device
+// with an upper bound of the bases behind it, which sizes the grid; 0: not known) -- synchronises st
+struct rk_sample;
+namespace rk {
+rk_ctx* sample_ctx(const rk_sample* s);
+int sample_feed_device(rk_sample* s, const void* d_bases, const void* d_offs_u32, int64_t nseq, uint64_t bound_bases, hipStream_t st);
+}
 int counter_settle(const rk_counter* k);                                                                    // rk_counters.hip
 int set_references_impl(rk_ctx* c, const uint8_t* bases, const uint8_t* d_bases, const uint64_t* offsets, int nref, const int* ks, int nks, int S,
                         int max_samples, uint64_t counter_slots);

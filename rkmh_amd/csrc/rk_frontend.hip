@@ -294,10 +294,11 @@ extern "C" int rk_fastq_slot_load_gzip(rk_fastq_slot* s, rk_gzip* gz, int64_t ca
 // The two halves of rk_fastq_slot_classify, for callers that keep two slots per thread: submit() enqueues the upload and the
 // index / check / pack kernels and returns at once; finish() waits for them, launches the classification and collects the rows.
 // Between the two the caller can read its next block into its other slot -- the link and the GPU work while the host reads.
-static int slot_submit(rk_fastq_slot* s, uint64_t nbytes, bool for_output) {
+// need_refs = false: rk_fastq_slot_sample alone, which looks nothing up in the reference index
+static int slot_submit(rk_fastq_slot* s, uint64_t nbytes, bool for_output, bool need_refs = true) {
     if (!s || nbytes > s->max_bytes) return fail(RK_ERR_ARG, "bad arguments");
     rk_ctx* c = s->c;
-    if (!c->have_refs) return fail(RK_ERR_STATE, "classify before rk_set_references");
+    if (need_refs && !c->have_refs) return fail(RK_ERR_STATE, "classify before rk_set_references");
     s->pending = nbytes;
     s->submitted = true;
     if (nbytes == 0) return RK_OK;
@@ -427,6 +428,27 @@ extern "C" int rk_fastq_slot_count(rk_fastq_slot* s, uint64_t nbytes, rk_counter
     HIPCHK(hipEventRecord(s->ev, s->st));
     HIPCHK(hipEventSynchronize(s->ev));
     return RK_OK;
+}
+
+// A block of raw FASTQ text into a sample accumulator (rk_sample.hip): split, check and pack on the device as rk_fastq_slot_count does,
+// then k_sample_keep on the packed bases where they lie.  *status != 0: the block is not four lines per record and NOTHING of it was
+// added.  The context needs no references.
+extern "C" int rk_fastq_slot_sample(rk_fastq_slot* s, uint64_t nbytes, rk_sample* sample, int32_t* status, int64_t* nrec_out) {
+    if (!s || !sample || !status) return fail(RK_ERR_ARG, "bad arguments");
+    if (sample_ctx(sample) != s->c) return fail(RK_ERR_ARG, "the sample belongs to another context");
+    *status = 0;
+    if (nrec_out) *nrec_out = 0;
+    RKCHK(slot_submit(s, nbytes, false, false));
+    s->submitted = false;
+    if (nbytes == 0) return RK_OK;
+    RKCHK(set_dev(s->c));
+    uint32_t* info = s->h_info.as<uint32_t>();
+    HIPCHK(hipEventSynchronize(s->ev));
+    if (info[0] != 0) { *status = (int32_t)info[0]; return RK_OK; }
+    const int64_t nrec = (int64_t)info[1];
+    if (nrec_out) *nrec_out = nrec;
+    if (nrec == 0) return RK_OK;
+    return sample_feed_device(sample, s->d.bases, s->d.out_off, nrec, nbytes, s->st);
 }
 
 extern "C" int rk_fastq_slot_classify(rk_fastq_slot* s, uint64_t nbytes, rk_fastq_result* res) {

@@ -11,6 +11,7 @@
 //   rkmh_commands.cpp   the hashing policy and the help text; call and hash
 //   rkmh_sketch_json.cpp  the reader of the JSON sketches `sketch` writes (stream -R, dist, gather); stands alone
 //   rkmh_sketches.cpp   sketch sets: made from sequence files, written as JSON, loaded from -R / -Q files, cut to one scaled
+//   rkmh_sample.cpp     one scaled sketch per sequence file built on the device: the -g / one-query-per-file route of the sketch sets
 //   rkmh_compare.cpp    sketch, dist, gather, multigather and manysearch
 //   rkmh_hpv16.cpp      hpv16
 #pragma once
@@ -100,6 +101,10 @@ struct ScaledSet {
 };
 void sketch_files(rk_ctx* ctx, const std::vector<const char*>& files, const std::vector<int>& ks, int S, bool whole_files, SketchSet& out);
 void sketch_files_scaled(rk_ctx* ctx, const std::vector<const char*>& files, const std::vector<int>& ks, uint64_t max_hash, bool whole_files, ScaledSet& out);
+// whole_files on the device (rkmh_sample.cpp; RKMH_SAMPLE_DEVICE=0 keeps the route that parses each file whole): one file into an
+// empty sample -> its sketch (malloc'd, rk_free) and the bases of its records; the sample is empty again afterwards
+bool sample_on_device();
+void sample_file_device(rk_ctx* ctx, rk_sample* sample, const char* path, uint64_t** values, uint32_t** abund, uint64_t* n, uint64_t* nbases);
 struct SketchRow { const uint64_t* hashes; uint64_t n, length; const uint32_t* abund = nullptr; }; // a sketch to write; "length": the S of a bottom-s sketch, a scaled one's own size; abund: its "abundances", or none
 void write_sketch_json(FILE* fo, const std::vector<std::string>& names, const std::vector<uint64_t>& seq_len, const std::string& kstr,
                        const std::vector<SketchRow>& rows, uint64_t scaled, uint64_t max_hash); // scaled = 0: a bottom-s file

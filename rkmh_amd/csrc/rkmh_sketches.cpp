@@ -46,6 +46,24 @@ void sketch_files(rk_ctx* ctx, const std::vector<const char*>& files, const std:
                });
 }
 void sketch_files_scaled(rk_ctx* ctx, const std::vector<const char*>& files, const std::vector<int>& ks, uint64_t max_hash, bool whole_files, ScaledSet& out) {
+    if (whole_files && sample_on_device()) { // one sketch per file: accumulated on the device, no file held whole (rkmh_sample.cpp)
+        rk_sample* sample = nullptr;
+        CK(rk_sample_create(ctx, ks.data(), (int)ks.size(), max_hash, out.with_abund ? 1 : 0, 0, &sample));
+        for (const char* f : files) {
+            uint64_t *v = nullptr, n = 0, nbases = 0;
+            uint32_t* a = nullptr;
+            sample_file_device(ctx, sample, f, &v, &a, &n, &nbases);
+            out.values.insert(out.values.end(), v, v + n);
+            if (out.with_abund) out.abund.insert(out.abund.end(), a, a + n);
+            out.off.push_back(out.values.size());
+            out.names.push_back(f);
+            out.seq_len.push_back(nbases);
+            rk_free(v);
+            rk_free(a);
+        }
+        rk_sample_destroy(sample);
+        return;
+    }
     std::vector<uint64_t> off;
     auto batch = [&](const rk_seqset& s, uint64_t** v, uint32_t** a) {
         off.assign((size_t)s.nseq + 1, 0);
