@@ -4,7 +4,7 @@ ARCH := gfx950
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall -Wno-unused-result $(EXTRA_HIPFLAGS)
 CSRC := rkmh_amd/csrc
 LIB := rkmh_amd/lib/librkmh_amd.so
-OBJS := $(CSRC)/rk_kernels.o $(CSRC)/rk_classify.o $(CSRC)/rk_kmer.o $(CSRC)/rk_count.o $(CSRC)/rk_call.o $(CSRC)/rk_sort.o $(CSRC)/rk_fastq.o $(CSRC)/rk_fasta.o $(CSRC)/rk_inflate.o $(CSRC)/rk_api.o $(CSRC)/rk_general.o $(CSRC)/rk_route.o $(CSRC)/rk_index.o $(CSRC)/rk_counters.o $(CSRC)/rk_frontend.o $(CSRC)/rk_gunzip.o $(CSRC)/rk_packed.o $(CSRC)/rk_pack.o $(CSRC)/rk_parse.o $(CSRC)/rk_format.o $(CSRC)/rk_synth.o $(CSRC)/rk_policy.o $(CSRC)/rk_pairs.o $(CSRC)/rk_pairs_host.o $(CSRC)/rk_scaled.o $(CSRC)/rk_scaled_host.o $(CSRC)/rk_gather.o $(CSRC)/rk_search.o $(CSRC)/rk_multigather.o $(CSRC)/rk_sample.o
+OBJS := $(CSRC)/rk_kernels.o $(CSRC)/rk_classify.o $(CSRC)/rk_kmer.o $(CSRC)/rk_count.o $(CSRC)/rk_call.o $(CSRC)/rk_sort.o $(CSRC)/rk_fastq.o $(CSRC)/rk_fasta.o $(CSRC)/rk_inflate.o $(CSRC)/rk_api.o $(CSRC)/rk_general.o $(CSRC)/rk_route.o $(CSRC)/rk_index.o $(CSRC)/rk_counters.o $(CSRC)/rk_frontend.o $(CSRC)/rk_gunzip.o $(CSRC)/rk_packed.o $(CSRC)/rk_pack.o $(CSRC)/rk_parse.o $(CSRC)/rk_pool.o $(CSRC)/rk_parse_blocks.o $(CSRC)/rk_bgzf.o $(CSRC)/rk_format.o $(CSRC)/rk_synth.o $(CSRC)/rk_policy.o $(CSRC)/rk_pairs.o $(CSRC)/rk_pairs_host.o $(CSRC)/rk_scaled.o $(CSRC)/rk_scaled_host.o $(CSRC)/rk_gather.o $(CSRC)/rk_search.o $(CSRC)/rk_multigather.o $(CSRC)/rk_sample.o
 
 API_DEPS := $(CSRC)/rk_api_internal.hpp $(CSRC)/rk_index_plan.hpp $(CSRC)/rk_sets.hpp $(CSRC)/rk_kernels.hpp $(CSRC)/rk_device.hpp include/rkmh_amd.h
 
@@ -82,7 +82,8 @@ $(CSRC)/rk_sample.o: $(CSRC)/rk_sample.hip $(API_DEPS)
 	@cd build/isa_sample && rm -f *.bc *.hipi *.out *.resolution.txt *.hipfb *host-x86_64*.s *.o
 $(CSRC)/rk_pack.o: $(CSRC)/rk_pack.cpp $(CSRC)/rk_filter_rule.hpp include/rkmh_amd.h
 	g++ -O3 -std=c++17 -fPIC -Wall -c $< -o $@
-$(CSRC)/rk_parse.o: $(CSRC)/rk_parse.cpp include/rkmh_amd.h
+# the host read parser: pool, reader, block front end, BGZF
+$(CSRC)/rk_pool.o $(CSRC)/rk_parse.o $(CSRC)/rk_parse_blocks.o $(CSRC)/rk_bgzf.o: $(CSRC)/%.o: $(CSRC)/%.cpp $(CSRC)/rk_parse_internal.hpp include/rkmh_amd.h
 	g++ -O3 -std=c++17 -fPIC -Wall -c $< -o $@
 $(CSRC)/rk_format.o: $(CSRC)/rk_format.cpp $(CSRC)/rk_filter_rule.hpp include/rkmh_amd.h
 	g++ -O3 -std=c++17 -fPIC -Wall -c $< -o $@

@@ -28,7 +28,7 @@ extern "C" int rk_device_count(void) {
     if (hipGetDeviceCount(&n) != hipSuccess) return 0;
     return n;
 }
-extern "C" void rk__pool_forget(void* p); // rk_parse.cpp: big parser buffers are tracked for recycling
+extern "C" void rk__pool_forget(void* p); // rk_pool.cpp: big parser buffers are tracked for recycling
 extern "C" void rk_free(void* p) { rk__pool_forget(p); free(p); }
 
 extern "C" int rk_device_props(int device, int32_t* compute_units, int32_t* clock_khz, int64_t* l2_bytes, int64_t* hbm_bytes) {

@@ -1,11 +1,11 @@
 // rk_fastq.hip -- the FASTQ front end on the device (gfx950): a block of RAW FASTQ text, uploaded as it lies in the file, becomes
 // the packed batch the classify kernels read (concatenated bases + offsets) plus, for the host, where each record's name lies in
 // the raw text.  Replaces, for input that is strictly four lines per record, the host-side parse_fastas / kseq_read loop
-// (/root/reference/src/rkmh.cpp:238-263; record grammar /root/reference/src/kseq.hpp:170-208) that round 3 measured as the
+// (src/rkmh.cpp:238-263; record grammar src/kseq.hpp:170-208) that round 3 measured as the
 // stage the GPU waits for (33 M reads/s on 16 cores against a 3 G reads/s kernel).
 //
 // kseq's grammar is sequential (a quality string is read by COUNT, '@' may be data), so -- exactly like the block-parallel host
-// scanner in rk_parse.cpp -- the device only accepts text on which that grammar provably coincides with the line-oriented one:
+// scanner in rk_parse_blocks.cpp -- the device only accepts text on which that grammar provably coincides with the line-oriented one:
 //   * the block starts at a record start and its lines come in fours: '@' header, sequence, '+' line, quality;
 //   * the sequence line holds only keeper bytes (33..126 without '>', '+', '@': what kseq appends to seq.s, kseq.hpp:183-191);
 //   * the quality line is exactly as long and holds bytes 33..127;

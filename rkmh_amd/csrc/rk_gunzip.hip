@@ -17,7 +17,7 @@
 //   6. the records: the text in front of the last record start (four-line rule) goes to the caller, the rest waits for the next call.
 // Whatever the device cannot do -- a stored or fixed-code stretch longer than a chunk's scratch, text that outgrows the buffers, a
 // second gzip member behind the first -- ends with return code 1 and the offset in the TEXT of the first record that was not
-// delivered: the caller's sequential reader goes on from there (rk_reader_open_at).
+// delivered: the caller's sequential reader goes on from there (rk_reader_open_at, rk_parse.cpp).
 #include "rk_api_internal.hpp"
 #include "rk_kernels.hpp"
 #include "rk_crc32.hpp"

@@ -785,7 +785,7 @@ __global__ __launch_bounds__(256) void k_crc32_segments(const uint8_t* __restric
     if (lane == 0u) crc[m] = c;
 }
 
-// first record start (four-line rule, as find_record_start in rk_parse.cpp) at or after `from` in text[0 .. n): a line start p with
+// first record start (four-line rule, as find_record_start in rk_parse_blocks.cpp) at or after `from` in text[0 .. n): a line start p with
 // text[p] == '@' whose line two below begins with '+'.  One workgroup; cuts[which] = the position, n if there is none (the text
 // ends inside the last record's lines), 0xFFFFFFFF if the lookahead ran out of text (the caller inflates more members).
 __global__ __launch_bounds__(256) void k_fastq_first_start(const uint8_t* __restrict__ text, uint32_t n, uint32_t from, uint32_t window, uint32_t at_eof,

@@ -1,4 +1,4 @@
-"""BGZF input (rk_bgzf_*, rk_parse.cpp): members located from their headers, jobs of consecutive members, every job inflated on its
+"""BGZF input (rk_bgzf_*, rk_bgzf.cpp): members located from their headers, jobs of consecutive members, every job inflated on its
 own and cut to the whole FASTQ records that START in it -- the concatenation of all jobs' records is the original text, whatever
 the job size, with libdeflate and with zlib; plain gzip and plain text are refused; a corrupt member is an error."""
 import ctypes as C

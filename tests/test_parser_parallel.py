@@ -1,4 +1,4 @@
-"""Block-parallel FASTA/FASTQ front end (rk_parse.cpp next_block) against the kseq-grammar restatement in
+"""Block-parallel FASTA/FASTQ front end (rk_parse_blocks.cpp next_block) against the kseq-grammar restatement in
 oracle/oracle.py (kseq.hpp:170-208) and against the sequential scanner, on well-formed and hostile inputs.
 CPU only: the parser is host code."""
 import os

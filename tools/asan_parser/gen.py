@@ -27,9 +27,14 @@ def mut(d,k):
         else: b=b[:pos]
     return bytes(b)
 os.makedirs(out,exist_ok=True)
+import gzip
 for i in range(n):
     base = fq(int(rng.integers(50,600))) if rng.random()<0.6 else fa(int(rng.integers(20,200)))
-    open(os.path.join(out,"f%04d.txt"%i),"wb").write(mut(base,int(rng.integers(0,6))))
+    data = mut(base,int(rng.integers(0,6)))
+    open(os.path.join(out,"f%04d.txt"%i),"wb").write(data)
+    # every eighth file also as ordinary gzip (one deflate stream): read through gzFile, and under RKMH_GZ_BLOCKS=2 by the inflater
+    # thread and the block front end's pipe branch.  run.sh checks that f0008.gz.txt gives what f0008.txt gives
+    if i%8==0: open(os.path.join(out,"f%04d.gz.txt"%i),"wb").write(gzip.compress(data,1,mtime=0))
 
 # BGZF images of FASTQ text (rk_bgzf_open / rk_bgzf_fastq_records run on them in main.cpp): intact, two files concatenated (an
 # empty member in the middle), and damaged ones -- headers, lengths, payload and the end of the file
