@@ -4,7 +4,7 @@ ARCH := gfx950
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall -Wno-unused-result $(EXTRA_HIPFLAGS)
 CSRC := rkmh_amd/csrc
 LIB := rkmh_amd/lib/librkmh_amd.so
-OBJS := $(CSRC)/rk_kernels.o $(CSRC)/rk_classify.o $(CSRC)/rk_kmer.o $(CSRC)/rk_count.o $(CSRC)/rk_call.o $(CSRC)/rk_sort.o $(CSRC)/rk_fastq.o $(CSRC)/rk_fasta.o $(CSRC)/rk_inflate.o $(CSRC)/rk_api.o $(CSRC)/rk_general.o $(CSRC)/rk_route.o $(CSRC)/rk_index.o $(CSRC)/rk_counters.o $(CSRC)/rk_frontend.o $(CSRC)/rk_gunzip.o $(CSRC)/rk_packed.o $(CSRC)/rk_pack.o $(CSRC)/rk_parse.o $(CSRC)/rk_pool.o $(CSRC)/rk_parse_blocks.o $(CSRC)/rk_bgzf.o $(CSRC)/rk_format.o $(CSRC)/rk_synth.o $(CSRC)/rk_policy.o $(CSRC)/rk_pairs.o $(CSRC)/rk_pairs_host.o $(CSRC)/rk_scaled.o $(CSRC)/rk_scaled_host.o $(CSRC)/rk_gather.o $(CSRC)/rk_search.o $(CSRC)/rk_multigather.o $(CSRC)/rk_sample.o
+OBJS := $(CSRC)/rk_kernels.o $(CSRC)/rk_classify.o $(CSRC)/rk_kmer.o $(CSRC)/rk_count.o $(CSRC)/rk_call.o $(CSRC)/rk_sort.o $(CSRC)/rk_fastq.o $(CSRC)/rk_fasta.o $(CSRC)/rk_inflate.o $(CSRC)/rk_api.o $(CSRC)/rk_general.o $(CSRC)/rk_route.o $(CSRC)/rk_index.o $(CSRC)/rk_counters.o $(CSRC)/rk_frontend.o $(CSRC)/rk_gunzip.o $(CSRC)/rk_packed.o $(CSRC)/rk_pack.o $(CSRC)/rk_parse.o $(CSRC)/rk_pool.o $(CSRC)/rk_parse_blocks.o $(CSRC)/rk_bgzf.o $(CSRC)/rk_format.o $(CSRC)/rk_synth.o $(CSRC)/rk_policy.o $(CSRC)/rk_pairs.o $(CSRC)/rk_pairs_host.o $(CSRC)/rk_scaled.o $(CSRC)/rk_scaled_host.o $(CSRC)/rk_gather.o $(CSRC)/rk_search.o $(CSRC)/rk_multigather.o $(CSRC)/rk_sample.o $(CSRC)/rk_bottom.o $(CSRC)/rk_bottom_host.o
 
 API_DEPS := $(CSRC)/rk_api_internal.hpp $(CSRC)/rk_index_plan.hpp $(CSRC)/rk_sets.hpp $(CSRC)/rk_kernels.hpp $(CSRC)/rk_device.hpp include/rkmh_amd.h
 
@@ -80,6 +80,11 @@ $(CSRC)/rk_sample.o: $(CSRC)/rk_sample.hip $(API_DEPS)
 	@mkdir -p build/isa_sample
 	cd build/isa_sample && $(HIPCC) $(HIPFLAGS) -save-temps -c $(CURDIR)/$< -o $(CURDIR)/$@
 	@cd build/isa_sample && rm -f *.bc *.hipi *.out *.resolution.txt *.hipfb *host-x86_64*.s *.o
+# the cut of a bottom sample: block weights and the scan inside the crossing block, ISA under build/isa_bottom
+$(CSRC)/rk_bottom.o: $(CSRC)/rk_bottom.hip $(API_DEPS)
+	@mkdir -p build/isa_bottom
+	cd build/isa_bottom && $(HIPCC) $(HIPFLAGS) -save-temps -c $(CURDIR)/$< -o $(CURDIR)/$@
+	@cd build/isa_bottom && rm -f *.bc *.hipi *.out *.resolution.txt *.hipfb *host-x86_64*.s *.o
 $(CSRC)/rk_pack.o: $(CSRC)/rk_pack.cpp $(CSRC)/rk_filter_rule.hpp include/rkmh_amd.h
 	g++ -O3 -std=c++17 -fPIC -Wall -c $< -o $@
 # the host read parser: pool, reader, block front end, BGZF
@@ -91,6 +96,8 @@ $(CSRC)/rk_format.o: $(CSRC)/rk_format.cpp $(CSRC)/rk_filter_rule.hpp include/rk
 $(CSRC)/rk_policy.o: $(CSRC)/rk_policy.cpp include/rkmh_amd.h
 	g++ -O2 -std=c++17 -fPIC -Wall -c $< -o $@
 $(CSRC)/rk_pairs_host.o: $(CSRC)/rk_pairs_host.cpp include/rkmh_amd.h
+	g++ -O2 -std=c++17 -fPIC -Wall -c $< -o $@
+$(CSRC)/rk_bottom_host.o: $(CSRC)/rk_bottom_host.cpp include/rkmh_amd.h
 	g++ -O2 -std=c++17 -fPIC -Wall -c $< -o $@
 $(CSRC)/rk_scaled_host.o: $(CSRC)/rk_scaled_host.cpp include/rkmh_amd.h
 	g++ -O2 -std=c++17 -fPIC -Wall -pthread -c $< -o $@

@@ -977,6 +977,58 @@ int rk_sample_finish(rk_sample* sample, uint64_t** values, uint32_t** abund, uin
 int rk_sample_device(rk_sample* sample, const void** d_values, const void** d_abund, uint64_t* n);
 int rk_sample_stats(rk_sample* sample, rk_sample_stats_t* out);
 
+/* BOTTOM SAMPLES (the -g side of `rkmh sketch -s` and `rkmh dist -s`: the one bottom-s sketch of a whole read set, built on the
+ * device, with --min-copies).  These are this library's own definitions.
+ *   Let W be the multiset of the non-zero window hashes of every sequence fed -- the windows are the policy's and the k list is
+ *   pooled, exactly as rk_sketch_batch and the samples above take them -- and c(v) the multiplicity of v in W.  At sketch_size S
+ *   (1 .. RK_MAX_SKETCH) and min_copies m (1 .. 2^32 - 1), v QUALIFIES when c(v) >= m.  The sketch is, ascending:
+ *     dedup=distinct: the S smallest qualifying values, each once;
+ *     dedup=multiset: the S smallest elements of W restricted to qualifying values -- each qualifying value c(v) times, the last
+ *       one cut off where S is reached.
+ *   The dedup rule is the context's policy.  At m = 1 this is rk_merge_sketches over the rk_sketch_batch rows of every sequence fed,
+ *   bit for bit.  Counts saturate at 2^32 - 1 as above; a saturated count qualifies for every m, and S <= 16 384 keeps saturation
+ *   out of the row.  m > 1 is what `mash sketch -r -m` is for -- a sequencing error makes k new k-mers, each seen once, and the
+ *   smallest hashes of a read set are mostly those -- but exact: the copies are counted, not estimated by a Bloom filter.
+ *   On the device a bottom sample is a sample as above that always keeps counts, and a THRESHOLD T, the max_hash its feeds keep
+ *   under: 2^64 - 1 at first, and it only comes down.  The resident set holds EVERY value <= T seen so far with its exact count,
+ *   qualifying or not.  A CUT follows a fold (resident sorted and distinct, nothing pending): entry j weighs 0 when its count is
+ *   below m, else 1 (distinct) or min(count, S) (multiset); j* is the first entry at which the running sum of the weights reaches S;
+ *   when there is one, T becomes values[j*] and the resident set ends behind j* -- a truncation, nothing moves.  This is exact: S
+ *   sketch elements lie at or below the new T already, counts only grow, so the final row ends at or below T, and every value <= T
+ *   keeps its exact count because every later window <= T is still kept.  The kernels (rk_bottom.hip): k_cut_weights sums the
+ *   weights of every 1 024 entries, k_scan_blocks scans the sums, k_cut_find scans inside the one block that crosses S and stores
+ *   (j* + 1, values[j*], the weight up to j*); the host reads those 24 bytes.  A sample folds and cuts after its first feed and then
+ *   whenever more values wait than are resident (and where a scaled sample would fold); the fold inside a batch that is run again does
+ *   not cut.  The row never depends on any of this, nor on batch boundaries, feed order or pending_cap.
+ *   MEMORY: while fewer than S values qualify, every value is a candidate and stays.  At m = 1 that ends with the first feed (a
+ *   sample that has not cut yet takes a large batch as sub-batches of 4 096, 8 192, ... reads, so T is down before most of it is
+ *   hashed).  At m >= 2 a file of low coverage, where few k-mers repeat, keeps EVERY distinct k-mer with its count: 12 bytes each,
+ *   twice (two array pairs), until RK_ERR_LIMIT (2^40 values) or the allocation's RK_ERR_NOMEM.
+ * rk_sample_create_bottom: an rk_sample; rk_sample_add_batch, rk_sample_add_batch_device, rk_fastq_slot_sample, rk_sample_stats,
+ *   rk_sample_reset (T back to 2^64 - 1) and rk_sample_destroy work on it unchanged.  Refuses what rk_sample_create refuses, and a
+ *   sketch_size or min_copies outside its range (RK_ERR_ARG), before anything is launched.
+ * rk_sample_finish_bottom: folds, cuts, downloads the resident set and writes row[sketch_size] (zero padded) and *len with
+ *   rk_bottom_emit; the sample stays usable.  RK_ERR_ARG on a scaled sample.
+ * rk_sample_finish / rk_sample_device on a bottom sample give its STATE, the resident candidates: every value <= T fed so far, with
+ *   its count (T: rk_sample_bottom_state after the call).  rk_sample_add_sketch on a bottom sample is RK_ERR_ARG: uniting two bottom
+ *   samples needs the smaller of two thresholds.
+ * rk_sample_bottom_state: T, the resident candidates after the latest fold, the weight of the resident set at the latest cut (below
+ *   S: no cut yet; it is not kept up to date between cuts) and the number of cuts that lowered T.  Any pointer may be NULL.  RK_ERR_ARG
+ *   on a scaled sample.  (rk_sample_stats_t is as it was.)
+ * rk_bottom_cut: the cut on host arrays -- values ascending and distinct, counts parallel --: uploads them, runs the three kernels;
+ *   *cut_len = j* + 1 and *threshold = values[j*], or *cut_len = 0 (and *threshold = 0): no cut.  Arrays that do not ascend give a
+ *   meaningless cut and nothing worse.  RK_ERR_ARG for NULL, sketch_size outside 1 .. RK_MAX_SKETCH, min_copies outside 1 .. 2^32 - 1;
+ *   RK_ERR_LIMIT for n >= 2^31 * 1 024; all before anything is launched.
+ * rk_bottom_emit (host code, usable without a GPU; rk_bottom_host.cpp): the row of a sorted distinct (values, counts) set under the
+ *   definition above; RK_ERR_ARG when the values do not ascend, or one is 0. */
+int rk_sample_create_bottom(rk_ctx* ctx, const int* ks, int nks, int sketch_size, uint64_t min_copies, uint64_t pending_cap, rk_sample** out);
+int rk_sample_finish_bottom(rk_sample* sample, uint64_t* row, int32_t* len);
+int rk_sample_bottom_state(rk_sample* sample, uint64_t* threshold, uint64_t* candidates, uint64_t* qualifying_weight, uint32_t* cuts);
+int rk_bottom_cut(rk_ctx* ctx, const uint64_t* values, const uint32_t* counts, uint64_t n, int sketch_size, uint64_t min_copies, int distinct,
+                  uint64_t* cut_len, uint64_t* threshold);
+int rk_bottom_emit(const uint64_t* values, const uint32_t* counts, uint64_t n, int sketch_size, uint64_t min_copies, int distinct, uint64_t* row,
+                   int32_t* len);
+
 #ifdef __cplusplus
 }
 #endif

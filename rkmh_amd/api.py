@@ -294,6 +294,12 @@ _SIGS = {
     "rk_sample_finish": (C.c_int, [C.c_void_p, C.POINTER(_u64p), C.POINTER(_u32p), C.POINTER(C.c_uint64)]),
     "rk_sample_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
     "rk_sample_stats": (C.c_int, [C.c_void_p, C.c_void_p]),
+    # bottom samples: include/rkmh_amd.h "BOTTOM SAMPLES"
+    "rk_sample_create_bottom": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.POINTER(C.c_void_p)]),
+    "rk_sample_finish_bottom": (C.c_int, [C.c_void_p, _u64p, _i32p]),
+    "rk_sample_bottom_state": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
+    "rk_bottom_cut": (C.c_int, [C.c_void_p, _u64p, _u32p, C.c_uint64, C.c_int, C.c_uint64, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "rk_bottom_emit": (C.c_int, [_u64p, _u32p, C.c_uint64, C.c_int, C.c_uint64, C.c_int, _u64p, _i32p]),
 }
 
 
@@ -1292,6 +1298,41 @@ def angular_similarity(dot, sumsq_a, sumsq_b):
     return c.value, a.value
 
 
+def _value_counts(values, counts):
+    values = np.ascontiguousarray(values, dtype=np.uint64)
+    counts = np.ascontiguousarray(counts, dtype=np.uint32)
+    if values.ndim != 1 or counts.shape != values.shape:
+        raise ValueError("values and counts must be one-dimensional and of one length")
+    return values, counts
+
+
+def bottom_cut(values, counts, sketch_size, min_copies=1, distinct=False, ctx=None):
+    """rk_bottom_cut: where the bottom sketch_size of the sorted distinct set (values uint64 ascending, counts uint32) ends, found on
+    the GPU -> (cut_len, threshold); cut_len = 0: no cut.  ctx: the Context to run on; None makes one on device 0 for the call."""
+    values, counts = _value_counts(values, counts)
+    own = ctx is None
+    if own:
+        ctx = Context(0)
+    try:
+        n, t = C.c_uint64(), C.c_uint64()
+        _chk(ctx._lib.rk_bottom_cut(ctx._h, _p(values, C.c_uint64), _p(counts, C.c_uint32), len(values), int(sketch_size), C.c_uint64(int(min_copies)),
+                                    1 if distinct else 0, C.byref(n), C.byref(t)))
+        return int(n.value), int(t.value)
+    finally:
+        if own:
+            ctx.close()
+
+
+def bottom_emit(values, counts, sketch_size, min_copies=1, distinct=False):
+    """rk_bottom_emit (host code, no GPU): the bottom-s row of a sorted distinct (values, counts) set -> (uint64 [sketch_size], length)."""
+    values, counts = _value_counts(values, counts)
+    row = np.zeros(max(int(sketch_size), 1), dtype=np.uint64)
+    m = C.c_int32()
+    _chk(load_library().rk_bottom_emit(_p(values, C.c_uint64), _p(counts, C.c_uint32), len(values), int(sketch_size), C.c_uint64(int(min_copies)),
+                                       1 if distinct else 0, _p(row, C.c_uint64), C.byref(m)))
+    return row[:max(int(sketch_size), 0)], int(m.value)
+
+
 class SampleStats(C.Structure):
     """rk_sample_stats_t (rkmh_amd.h, "SAMPLE SKETCHES")"""
     _fields_ = [("struct_size", C.c_uint32), ("folds", C.c_uint32), ("retries", C.c_uint32), ("reserved", C.c_uint32), ("nseq", C.c_uint64),
@@ -1299,13 +1340,22 @@ class SampleStats(C.Structure):
 
 
 class Sample:
-    """rk_sample: one scaled sketch, with or without abundances, accumulated on the device from the reads fed to it (Context.sample)."""
+    """rk_sample: one scaled sketch, with or without abundances, accumulated on the device from the reads fed to it (Context.sample);
+    or, with sketch_size, a bottom sample (Context.sample_bottom; rkmh_amd.h "BOTTOM SAMPLES"): one bottom-s sketch of the values seen at
+    least min_copies times, which always keeps counts."""
 
-    def __init__(self, ctx, ks, max_hash, abund=False, pending_cap=0):
+    def __init__(self, ctx, ks, max_hash, abund=False, pending_cap=0, sketch_size=None, min_copies=1):
         self._ctx, self._lib = ctx, ctx._lib
-        self.abund = bool(abund)
+        self.abund = bool(abund) or sketch_size is not None
+        self.sketch_size = None if sketch_size is None else int(sketch_size)
         ks = _ks(ks)
         self._h = C.c_void_p()
+        if sketch_size is not None:
+            if not 0 <= int(min_copies) < 1 << 64:
+                raise ValueError("min_copies outside the range of uint64")
+            _chk(self._lib.rk_sample_create_bottom(ctx._h, _p(ks, C.c_int), len(ks), max(min(int(sketch_size), 2 ** 31 - 1), -2 ** 31),
+                                                   C.c_uint64(int(min_copies)), C.c_uint64(int(pending_cap)), C.byref(self._h)))
+            return
         _chk(self._lib.rk_sample_create(ctx._h, _p(ks, C.c_int), len(ks), C.c_uint64(int(max_hash)), 1 if abund else 0, C.c_uint64(int(pending_cap)),
                                         C.byref(self._h)))
 
@@ -1344,6 +1394,21 @@ class Sample:
             a = np.ctypeslib.as_array(oa, shape=(max(m, 1),))[:m].copy()
             self._lib.rk_free(oa)
         return r, a
+
+    def finish_bottom(self):
+        """rk_sample_finish_bottom -> (row uint64 [sketch_size], zero padded, length); the sample stays usable."""
+        if self.sketch_size is None:
+            raise RkmhError("a scaled sample has no bottom-s row")
+        row = np.zeros(self.sketch_size, dtype=np.uint64)
+        m = C.c_int32()
+        _chk(self._lib.rk_sample_finish_bottom(self._h, _p(row, C.c_uint64), C.byref(m)))
+        return row, int(m.value)
+
+    def bottom_state(self):
+        """rk_sample_bottom_state -> dict(threshold, candidates, qualifying_weight, cuts)"""
+        t, n, w, c = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint32()
+        _chk(self._lib.rk_sample_bottom_state(self._h, C.byref(t), C.byref(n), C.byref(w), C.byref(c)))
+        return dict(threshold=int(t.value), candidates=int(n.value), qualifying_weight=int(w.value), cuts=int(c.value))
 
     def device(self):
         """rk_sample_device -> (device pointer of the values, of the abundances or None, n): valid until the next add, reset or close."""
@@ -1531,6 +1596,14 @@ class Context:
     def sample(self, ks, max_hash, abund=False, pending_cap=0):
         """rk_sample_create: an empty Sample at (ks, this context's policy, max_hash); pending_cap 0 = the library's default."""
         return Sample(self, ks, max_hash, abund=abund, pending_cap=pending_cap)
+
+    def sample_bottom(self, ks, sketch_size, min_copies=1, pending_cap=0):
+        """rk_sample_create_bottom: an empty bottom sample at (ks, this context's policy, sketch_size, min_copies)."""
+        return Sample(self, ks, 0, pending_cap=pending_cap, sketch_size=sketch_size, min_copies=min_copies)
+
+    def bottom_cut(self, values, counts, sketch_size, min_copies=1, distinct=False):
+        """rk_bottom_cut on this context: see the module's bottom_cut."""
+        return bottom_cut(values, counts, sketch_size, min_copies, distinct, ctx=self)
 
     def compare_scaled(self, a_values, a_offsets, b_values=None, b_offsets=None, lanes=0):
         """rk_compare_scaled: every CSR sketch of `a` against every one of `b` (None: of `a` itself) -> int32 [na, nb], the number

@@ -16,6 +16,7 @@
 //   rk_search.hip    search: the resident inverted index of scaled sketches (value -> references) and the thresholded search on it
 //   rk_multigather.hip  multigather: gather for a batch of queries through that index, counts kept up to date by integer atomics
 //   rk_sample.hip    the sample accumulator: one scaled sketch built on the device from reads fed batch by batch (fused hash-and-keep, folds)
+//   rk_bottom.hip    the cut of a bottom sample: where the bottom sketch_size of a sorted counted set ends (block weights, scan, the crossing block)
 #pragma once
 #include "../../include/rkmh_amd.h"
 #include "rk_kernels.hpp"
@@ -281,6 +282,12 @@ struct rk_sample;
 namespace rk {
 rk_ctx* sample_ctx(const rk_sample* s);
 int sample_feed_device(rk_sample* s, const void* d_bases, const void* d_offs_u32, int64_t nseq, uint64_t bound_bases, hipStream_t st);
+// the cut of a bottom sample (rk_bottom.hip): where the bottom sketch_size of the sorted distinct set (d_values, d_counts)[0, n) ends.
+// Enqueues on st, synchronises nothing; d_state (uint64[3] on the device) then holds (cut length, threshold, weight): (0, 0, the
+// weight of all n entries) when that weight stays below sketch_size, else (j* + 1, values[j*], the weight of entries 0 .. j*).
+// cnt and pre are the caller's scratch.  n < 2^31 * 1024 is the caller's to check.
+int bottom_cut_device(DevBuf& cnt, DevBuf& pre, const uint64_t* d_values, const uint32_t* d_counts, uint64_t n, uint32_t sketch_size, uint32_t min_copies,
+                      bool distinct, uint64_t* d_state, hipStream_t st);
 }
 int counter_settle(const rk_counter* k);                                                                    // rk_counters.hip
 int set_references_impl(rk_ctx* c, const uint8_t* bases, const uint8_t* d_bases, const uint64_t* offsets, int nref, const int* ks, int nks, int S,

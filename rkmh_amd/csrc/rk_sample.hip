@@ -26,6 +26,12 @@ struct rk_sample {
     DevBuf w_cnt, w_pre, w_src, w_tmp, w_bases, w_offs;
     uint32_t folds = 0, retries = 0;
     uint64_t kept = 0;
+    // a bottom sample ("BOTTOM SAMPLES"): sketch_size > 0, counts always kept, and max_hash is its threshold T, which a cut lowers
+    int sketch_size = 0;
+    uint32_t min_copies = 1;
+    uint32_t cuts = 0;
+    uint64_t weight = 0;    // the weight of the resident set at the latest look of a cut
+    DevBuf cut_state;       // uint64[3] on the device: what k_cut_find leaves (cut length, threshold, weight)
     std::mutex mu; // feeds, folds and reads of one sample take turns
 };
 
@@ -37,6 +43,7 @@ constexpr int SK_BND_DW = (HASH_TILE_WIN + MAX_K + 2 + 31) / 32 + 2;   // the re
 constexpr uint32_t SK_BND_BITS = (uint32_t)(SK_BND_DW - 2) * 32u;
 constexpr uint64_t SK_DEFAULT_PENDING = (uint64_t)1 << 22;             // values (32 MB): DESIGN.md section 20
 constexpr uint64_t SK_PIECE_BASES = (uint64_t)64 << 20;                // rk_sample_add_batch uploads pieces of about this many bases
+constexpr uint32_t SK_FIRST_READS = 4096;                              // a bottom sample before its first cut: reads of the first sub-batch, doubling
 
 // bits [bit, bit + left) of the bitmap all zero?  (window_valid's walk, on the read-start bitmap)
 __device__ __forceinline__ bool no_boundary(const uint32_t* bnd, uint32_t bit, int left) {
@@ -260,6 +267,28 @@ int fold_values(rk_sample* s, uint64_t m, bool fill_ones, hipStream_t st) {
 }
 int fold_pending(rk_sample* s, hipStream_t st) { return fold_values(s, s->pending, true, st); }
 
+// A bottom sample behind a fold -- the resident set sorted and distinct, nothing pending --: where its bottom sketch_size ends
+// (rk_bottom.hip); when it ends inside the set, T comes down to the value there and the set is cut off behind it.  One 24-byte look.
+int cut_resident(rk_sample* s, hipStream_t st) {
+    uint64_t* h = s->h_state.as<uint64_t>();
+    RKCHK(bottom_cut_device(s->w_cnt, s->w_pre, s->keys[s->cur].as<uint64_t>(), s->cnts[s->cur].as<uint32_t>(), s->n_res, (uint32_t)s->sketch_size, s->min_copies,
+                            s->ctx->dedup, s->cut_state.as<uint64_t>(), st));
+    HIPCHK(hipMemcpyAsync(h + 5, s->cut_state.p, 24, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (h[5] > s->n_res) return fail(RK_ERR_HIP, "sample cut at %llu of %llu values", (unsigned long long)h[5], (unsigned long long)s->n_res);
+    s->weight = h[7];
+    if (h[5]) {
+        if (h[5] < s->n_res || h[6] < s->max_hash) ++s->cuts; // (a cut behind its own last entry changes nothing and is not counted)
+        s->n_res = h[5];
+        s->max_hash = h[6];
+    }
+    return RK_OK;
+}
+int fold_and_cut(rk_sample* s, hipStream_t st) {
+    RKCHK(fold_pending(s, st));
+    return s->sketch_size ? cut_resident(s, st) : RK_OK;
+}
+
 int launch_keep(rk_sample* s, const void* d_bases, const void* d_offs, uint32_t n, uint64_t bound_bases, int add_totals, hipStream_t st) {
     const uint32_t grid = (uint32_t)std::min<uint64_t>(std::max<uint64_t>((bound_bases + HASH_TILE_WIN - 1) / HASH_TILE_WIN, 1), 4096);
     uint64_t* pend = s->keys[s->cur].as<uint64_t>() + s->n_res;
@@ -277,7 +306,7 @@ int launch_keep(rk_sample* s, const void* d_bases, const void* d_offs, uint32_t 
 }
 
 // one batch of resident reads into the sample; the caller holds s->mu and has set the device.  Synchronises st.
-int feed_locked(rk_sample* s, const void* d_bases, const void* d_offs, uint32_t n, uint64_t bound_bases, hipStream_t st) {
+int feed_one(rk_sample* s, const void* d_bases, const void* d_offs, uint32_t n, uint64_t bound_bases, hipStream_t st) {
     uint64_t* h = s->h_state.as<uint64_t>();
     const uint64_t before = s->pending;
     // a batch whose size the caller cannot say (the device entry) gets the grid of twice the batch before it: the base total comes
@@ -295,7 +324,7 @@ int feed_locked(rk_sample* s, const void* d_bases, const void* d_offs, uint32_t 
         // forgotten), the values from before are folded, the pending array grows to what the batch asked for, and the batch runs again
         h[0] = before;
         HIPCHK(hipMemcpyAsync(s->state.p, h, 8, hipMemcpyHostToDevice, st)); // (h[0] is written next by the copy behind the second run, on this stream)
-        RKCHK(fold_pending(s, st));
+        RKCHK(fold_pending(s, st)); // (a bottom sample: no cut here -- T stays, so the second run keeps what the first kept)
         if (need > s->pend_cap) {
             s->pend_cap = need;
             RKCHK(ensure_capacity(s, s->n_res + s->pend_cap, st));
@@ -310,8 +339,19 @@ int feed_locked(rk_sample* s, const void* d_bases, const void* d_offs, uint32_t 
     s->kept += need;
     s->last_need = need;
     // the look is paid for: when the next batch, if it keeps what this one kept, would not fit, fold now and spare it the second run
-    if (s->pend_cap - s->pending < s->last_need) RKCHK(fold_pending(s, st));
+    // (a bottom sample also folds, and then cuts, whenever more waits than is resident: T follows the data at a cost that stays
+    // proportional to what was kept; the first feed always does)
+    if (s->pend_cap - s->pending < s->last_need || (s->sketch_size && s->pending > s->n_res)) RKCHK(fold_and_cut(s, st));
     return RK_OK;
+}
+// A bottom sample that has not cut yet keeps every window: a large batch goes in as sub-batches of 4 096, 8 192, ... reads (offs + i
+// with a smaller n is a batch like any other) until the first cut has brought T down, and the rest then goes in as one.
+int feed_locked(rk_sample* s, const void* d_bases, const void* d_offs, uint32_t n, uint64_t bound_bases, hipStream_t st) {
+    if (!s->sketch_size || s->cuts || n <= SK_FIRST_READS) return feed_one(s, d_bases, d_offs, n, bound_bases, st);
+    const uint32_t* offs = (const uint32_t*)d_offs;
+    uint32_t i = 0;
+    for (uint32_t step = SK_FIRST_READS; s->cuts == 0 && n - i > step; i += step, step *= 2) RKCHK(feed_one(s, d_bases, offs + i, step, 0, st));
+    return feed_one(s, d_bases, offs + i, n - i, bound_bases, st);
 }
 
 int check_sample(const rk_sample* s) {
@@ -338,7 +378,7 @@ extern "C" void rk_sample_destroy(rk_sample* s) {
     if (!s) return;
     hipError_t e = hipSetDevice(s->device); (void)e;
     // (every feed, fold and download of the sample ended with its stream synchronised: nothing of it is in flight)
-    for (DevBuf* b : {&s->keys[0], &s->keys[1], &s->cnts[0], &s->cnts[1], &s->state, &s->w_cnt, &s->w_pre, &s->w_src, &s->w_tmp, &s->w_bases, &s->w_offs}) b->release();
+    for (DevBuf* b : {&s->keys[0], &s->keys[1], &s->cnts[0], &s->cnts[1], &s->state, &s->w_cnt, &s->w_pre, &s->w_src, &s->w_tmp, &s->w_bases, &s->w_offs, &s->cut_state}) b->release();
     s->h_state.release();
     delete s;
 }
@@ -372,6 +412,7 @@ extern "C" int rk_sample_reset(rk_sample* s) {
     HIPCHK(hipMemsetAsync(s->state.p, 0, 32, s->ctx->st));
     HIPCHK(hipStreamSynchronize(s->ctx->st));
     s->n_res = 0; s->pending = 0; s->last_need = 0; s->seen_bases = 0; s->last_bases = 0; s->kept = 0; s->folds = 0; s->retries = 0;
+    if (s->sketch_size) { s->max_hash = ~0ull; s->cuts = 0; s->weight = 0; }
     return RK_OK;
 }
 
@@ -410,6 +451,7 @@ extern "C" int rk_sample_add_batch(rk_sample* s, const uint8_t* bases, const uin
 
 extern "C" int rk_sample_add_sketch(rk_sample* s, const uint64_t* values, const uint32_t* abund, uint64_t n) {
     RKCHK(check_sample(s));
+    if (s->sketch_size) return fail(RK_ERR_ARG, "a bottom sample takes reads, not sketches: uniting two of them needs the smaller of two thresholds");
     if (n && !values) return fail(RK_ERR_ARG, "bad arguments");
     if (s->with_abund && n && !abund) return fail(RK_ERR_ARG, "a sample with abundances takes a sketch with abundances");
     if (n > 0x7fffffffull) return fail(RK_ERR_LIMIT, "a sketch of 2^31 values or more");
@@ -484,5 +526,50 @@ extern "C" int rk_sample_stats(rk_sample* s, rk_sample_stats_t* out) {
     const uint32_t size = std::min<uint32_t>(out->struct_size, (uint32_t)sizeof t);
     t.struct_size = size;
     memcpy(out, &t, size);
+    return RK_OK;
+}
+
+// ---- bottom samples
+extern "C" int rk_sample_create_bottom(rk_ctx* c, const int* ks, int nks, int sketch_size, uint64_t min_copies, uint64_t pending_cap, rk_sample** out) {
+    if (!c || !out) return fail(RK_ERR_ARG, "bad arguments");
+    if (sketch_size < 1 || sketch_size > RK_MAX_SKETCH) return fail(RK_ERR_ARG, "sketch size %d outside [1,%d]", sketch_size, RK_MAX_SKETCH);
+    if (min_copies < 1 || min_copies > 0xffffffffull) return fail(RK_ERR_ARG, "min_copies %llu outside [1,2^32-1]", (unsigned long long)min_copies);
+    rk_sample* s = nullptr;
+    RKCHK(rk_sample_create(c, ks, nks, ~0ull, 1, pending_cap, &s));
+    s->sketch_size = sketch_size;
+    s->min_copies = (uint32_t)min_copies;
+    const int rc = s->cut_state.reserve(32);
+    if (rc != RK_OK) { rk_sample_destroy(s); return rc; }
+    *out = s;
+    return RK_OK;
+}
+
+extern "C" int rk_sample_finish_bottom(rk_sample* s, uint64_t* row, int32_t* len) {
+    RKCHK(check_sample(s));
+    if (!row || !len) return fail(RK_ERR_ARG, "bad arguments");
+    if (!s->sketch_size) return fail(RK_ERR_ARG, "a scaled sample has no bottom-s row: rk_sample_finish gives its values");
+    rk_ctx* c = s->ctx;
+    RKCHK(set_dev(c));
+    std::lock_guard<std::mutex> lk(s->mu);
+    RKCHK(fold_and_cut(s, c->st));
+    const uint64_t nd = s->n_res;
+    std::vector<uint64_t> v((size_t)nd);
+    std::vector<uint32_t> a((size_t)nd);
+    if (nd) {
+        HIPCHK(hipMemcpyAsync(v.data(), s->keys[s->cur].p, (size_t)nd * 8, hipMemcpyDeviceToHost, c->st));
+        HIPCHK(hipMemcpyAsync(a.data(), s->cnts[s->cur].p, (size_t)nd * 4, hipMemcpyDeviceToHost, c->st));
+        HIPCHK(hipStreamSynchronize(c->st));
+    }
+    return rk_bottom_emit(v.data(), a.data(), nd, s->sketch_size, s->min_copies, c->dedup ? 1 : 0, row, len);
+}
+
+extern "C" int rk_sample_bottom_state(rk_sample* s, uint64_t* threshold, uint64_t* candidates, uint64_t* qualifying_weight, uint32_t* cuts) {
+    RKCHK(check_sample(s));
+    if (!s->sketch_size) return fail(RK_ERR_ARG, "a scaled sample has no bottom state");
+    std::lock_guard<std::mutex> lk(s->mu);
+    if (threshold) *threshold = s->max_hash;
+    if (candidates) *candidates = s->n_res;
+    if (qualifying_weight) *qualifying_weight = s->weight;
+    if (cuts) *cuts = s->cuts;
     return RK_OK;
 }

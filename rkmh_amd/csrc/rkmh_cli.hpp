@@ -99,15 +99,22 @@ struct ScaledSet {
     std::vector<std::string> names; std::vector<uint64_t> seq_len; std::vector<uint64_t> values; std::vector<uint64_t> off = std::vector<uint64_t>(1, 0);
     bool with_abund = false; std::vector<uint32_t> abund;
 };
-void sketch_files(rk_ctx* ctx, const std::vector<const char*>& files, const std::vector<int>& ks, int S, bool whole_files, SketchSet& out);
+// min_copies (--min-copies; above 1 only with whole_files on the device): only values seen that often over the whole file count
+void sketch_files(rk_ctx* ctx, const std::vector<const char*>& files, const std::vector<int>& ks, int S, bool whole_files, SketchSet& out, uint64_t min_copies = 1);
 void sketch_files_scaled(rk_ctx* ctx, const std::vector<const char*>& files, const std::vector<int>& ks, uint64_t max_hash, bool whole_files, ScaledSet& out);
-// whole_files on the device (rkmh_sample.cpp; RKMH_SAMPLE_DEVICE=0 keeps the route that parses each file whole): one file into an
-// empty sample -> its sketch (malloc'd, rk_free) and the bases of its records; the sample is empty again afterwards
+// whole_files on the device (rkmh_sample.cpp; RKMH_SAMPLE_DEVICE=0 keeps the route that parses each file whole): sample_file_feed
+// sends one file into an empty sample; the caller takes its sketch (rk_sample_finish, rk_sample_finish_bottom); sample_file_done
+// gives the bases of its records, prints the timing line and leaves the sample empty again
 bool sample_on_device();
-void sample_file_device(rk_ctx* ctx, rk_sample* sample, const char* path, uint64_t** values, uint32_t** abund, uint64_t* n, uint64_t* nbases);
+struct SampleFed { const char* route = ""; int64_t blocks = 0; double t0 = 0, t1 = 0; }; // the route taken, its blocks, when the feed began and ended
+SampleFed sample_file_feed(rk_ctx* ctx, rk_sample* sample, const char* path);
+void sample_file_done(rk_sample* sample, const char* path, const SampleFed& fed, uint64_t* nbases);
+// --min-copies: a number of 1 .. 2^32 - 1; and its three refusals, which sketch and dist word alike (`command`: "sketch" / "dist")
+bool parse_min_copies(const char* text, uint64_t& m);
+void refuse_min_copies(const char* command, uint64_t m, bool whole_files, bool scaled);
 struct SketchRow { const uint64_t* hashes; uint64_t n, length; const uint32_t* abund = nullptr; }; // a sketch to write; "length": the S of a bottom-s sketch, a scaled one's own size; abund: its "abundances", or none
 void write_sketch_json(FILE* fo, const std::vector<std::string>& names, const std::vector<uint64_t>& seq_len, const std::string& kstr,
-                       const std::vector<SketchRow>& rows, uint64_t scaled, uint64_t max_hash); // scaled = 0: a bottom-s file
+                       const std::vector<SketchRow>& rows, uint64_t scaled, uint64_t max_hash, uint64_t min_copies = 1); // scaled = 0: a bottom-s file; min_copies > 1: "minCopies"
 bool parse_scaled(const char* text, uint64_t& scaled); // --scaled: a number of at least 1, nothing else
 bool parse_at_least_1(const char* text, int& v);
 // What dist and gather are told alike (-r -f -R -Q -k -s -g --scaled --device --hash-policy): the rows of their long_options, and
@@ -119,6 +126,7 @@ struct CompareInputs {
     bool whole_files = false, scaled_given = false, scaled_ok = true;
     bool abund = false; // gather --abund: the queries carry abundances; dist --abund: both sides do
     uint64_t scaled = 0;
+    uint64_t min_copies = 1; // dist --min-copies (0: not a number of 1 .. 2^32 - 1)
     bool self() const { return query_files.empty() && query_json.empty(); }
 };
 #define COMPARE_OPTIONS \

@@ -6,9 +6,13 @@
 
 static void help_sketch() {
     fprintf(stderr,
-            "rkmh sketch -f <seqs.fa|fq> [-k <k>]... [-s <sketch> | --scaled <n> [--abund]] [-g] [-o <out.json>] [--kmer-cache <file>]\n"
+            "rkmh sketch -f <seqs.fa|fq> [-k <k>]... [-s <sketch> | --scaled <n> [--abund]] [-g [--min-copies <m>]] [-o <out.json>] [--kmer-cache <file>]\n"
             "  writes a JSON array with one MinHash sketch per sequence (schema of the reference's dump_hash_json);\n"
             "  -g: one sketch per input FILE (named by its path; no k-mer spans two of its records), as Mash sketches an assembly;\n"
+            "  a bottom-s sketch with -g is built on the device as the file is read: no file is held whole (RKMH_SAMPLE_DEVICE=0: the old route)\n"
+            "  --min-copies <m> (with -g and -s; default 1): only k-mers seen at least m times over the whole file count, as `mash sketch -r -m`\n"
+            "  filters the errors out of a read set, but exactly; objects gain \"minCopies\".  While fewer than <sketch> k-mers have m copies every\n"
+            "  distinct k-mer of the file is kept on the device with its count: a file of low coverage at m >= 2 needs memory for all of them\n"
             "  --scaled <n>: scaled (FracMinHash) sketches instead of bottom-s ones: every distinct hash up to (2^64 - 1) / n, so the size\n"
             "  grows with the sequence; objects gain \"scaled\" and \"maxHash\"; such files serve `rkmh dist` only\n"
             "  --abund (with --scaled): \"sketches\" gains \"abundances\", parallel to \"hashes\": how many windows of the sequence hash to each\n"
@@ -25,17 +29,18 @@ int main_sketch(int argc, char** argv) {
     const char* outp = nullptr;
     const char* kmer_cache = nullptr;
     bool whole_files = false, s_given = false, scaled_given = false, scaled_ok = true, abund = false;
-    uint64_t scaled = 0;
+    uint64_t scaled = 0, min_copies = 1;
     if (argc <= 2) { help_sketch(); exit(1); }
     optind = 2;
     int c;
     static struct option long_options[] = {{"help", no_argument, 0, 'h'}, {"kmer", required_argument, 0, 'k'},
         {"fasta", required_argument, 0, 'f'}, {"reference", required_argument, 0, 'r'}, {"sketch-size", required_argument, 0, 's'},
         {"output", required_argument, 0, 'o'}, {"device", required_argument, 0, 1000}, {"kmer-cache", required_argument, 0, 1003},
-        {"whole-files", no_argument, 0, 'g'}, {"scaled", required_argument, 0, 1005}, {"abund", no_argument, 0, 1008}, HASH_POLICY_OPTION, {0, 0, 0, 0}};
+        {"whole-files", no_argument, 0, 'g'}, {"scaled", required_argument, 0, 1005}, {"abund", no_argument, 0, 1008}, {"min-copies", required_argument, 0, 1012}, HASH_POLICY_OPTION, {0, 0, 0, 0}};
     while ((c = getopt_long(argc, argv, "hgk:f:r:s:o:t:", long_options, nullptr)) != -1) {
         switch (c) {
             case 1008: abund = true; break;
+            case 1012: if (!parse_min_copies(optarg, min_copies)) min_copies = 0; break;
             case 1004: policy_apply(optarg, "--hash-policy"); break;
             case 1005: scaled_given = true; scaled_ok = parse_scaled(optarg, scaled); break;
             case 1003: kmer_cache = optarg; break;
@@ -57,6 +62,7 @@ int main_sketch(int argc, char** argv) {
         if (kmer_cache) { fprintf(stderr, "rkmh sketch: --kmer-cache serves `stream -R`; scaled sketches serve `rkmh dist` only\n"); exit(1); }
     }
     if (abund && !scaled_given) { fprintf(stderr, "rkmh sketch: --abund goes with --scaled <n>; bottom-s sketches keep no abundances\n"); exit(1); }
+    refuse_min_copies("sketch", min_copies, whole_files, scaled_given);
     if (!scaled_given && whole_files && (S < 1 || S > RK_MAX_SKETCH)) { fprintf(stderr, "rkmh sketch: -g needs a sketch size of 1 .. %d\n", RK_MAX_SKETCH); exit(1); }
     rk_ctx* ctx = nullptr;
     CK(rk_ctx_create(device, &g_policy, &ctx));
@@ -73,7 +79,7 @@ int main_sketch(int argc, char** argv) {
         for (size_t i = 0; i < sc.names.size(); ++i)
             rows.push_back({sc.values.data() + sc.off[i], sc.off[i + 1] - sc.off[i], sc.off[i + 1] - sc.off[i], ab ? ab + sc.off[i] : nullptr});
     } else {
-        sketch_files(ctx, files, ks, S, whole_files, set);
+        sketch_files(ctx, files, ks, S, whole_files, set, min_copies);
         if (kmer_cache && *kmer_cache) {
             // the index of these sketches is built once here, for its k-mer enumeration: the file's tag hashes the index keys, k and the
             // hashing policy, so a later `stream -R <these sketches> --kmer-cache <file>` finds it -- and anything else does not use it
@@ -87,7 +93,7 @@ int main_sketch(int argc, char** argv) {
     if (!fo) { fprintf(stderr, "rkmh: cannot write %s\n", outp); exit(1); }
     std::string kstr;
     for (size_t i = 0; i < ks.size(); ++i) { kstr += std::to_string(ks[i]); if (i + 1 < ks.size()) kstr += ' '; }
-    write_sketch_json(fo, scaled_given ? sc.names : set.names, scaled_given ? sc.seq_len : set.seq_len, kstr, rows, scaled_given ? scaled : 0, max_hash);
+    write_sketch_json(fo, scaled_given ? sc.names : set.names, scaled_given ? sc.seq_len : set.seq_len, kstr, rows, scaled_given ? scaled : 0, max_hash, min_copies);
     if (fo != stdout) fclose(fo);
     rk_ctx_destroy(ctx);
     return 0;
@@ -108,7 +114,7 @@ static int run_k(const CompareRules& rules, int k) {
 // Everything that can be refused is refused before a context exists: nothing is printed by a run that fails.
 static void help_dist() {
     fprintf(stderr,
-            "rkmh dist (-r <refs.fa> ... | -R <refs.json>) [-f <queries.fa|fq> ... | -Q <queries.json>] [-k <k>] [-s <sketch> | --scaled <n> [--abund]] [-g] [-d <maxdist>]\n"
+            "rkmh dist (-r <refs.fa> ... | -R <refs.json>) [-f <queries.fa|fq> ... | -Q <queries.json>] [-k <k>] [-s <sketch> | --scaled <n> [--abund]] [-g [--min-copies <m>]] [-d <maxdist>]\n"
             "  prints one line per (query, reference) pair, query by query: reference, query, Mash distance, common/denom of the merged\n"
             "  bottom-s sketch, shared hashes (the multiset intersection `stream` counts); without -f / -Q every reference is compared\n"
             "  with every reference\n"
@@ -122,6 +128,9 @@ static void help_dist() {
             "  gains three: the angular similarity of the two abundance vectors, 1 - 2 acos(cosine) / pi (1: the same proportions, 0: nothing\n"
             "  shared), wq_in/wq_total (the query's windows whose hash the reference holds / all windows the query kept) and wr_in/wr_total\n"
             "  (the same for the reference); -d still filters on the distance column\n"
+            "  --min-copies <m> (with -g, bottom-s sketches only): -f files -- without -f, the -r files -- are sketched from the k-mers seen at\n"
+            "  least m times over the whole file (read sets: `mash sketch -r -m`; -r genomes beside -f read sets are sketched as they are);\n"
+            "  until <sketch> k-mers have m copies, every distinct k-mer of a file stays on the device\n"
             "  -g: one sketch per input FILE, as Mash sketches an assembly;  -d <x>: only pairs at distance <= x;  --device <id>: GPU to use\n" HASH_POLICY_HELP);
 }
 // the six columns of a pair of scaled sketches, without the end of the line: dist --scaled and manysearch print a pair alike
@@ -176,8 +185,8 @@ static int dist_bottom(const CompareInputs& in, LoadedSides& ld, int k, double m
     rk_ctx* ctx = nullptr;
     CK(rk_ctx_create(in.device, &g_policy, &ctx));
     const std::vector<int> k1(1, k);
-    if (!in.ref_files.empty()) sketch_files(ctx, in.ref_files, k1, S, in.whole_files, ld.refs);
-    if (!in.query_files.empty()) sketch_files(ctx, in.query_files, k1, S, in.whole_files, ld.queries);
+    if (!in.ref_files.empty()) sketch_files(ctx, in.ref_files, k1, S, in.whole_files, ld.refs, in.self() ? in.min_copies : 1); // (genomes hold most k-mers once: --min-copies is for the read sets)
+    if (!in.query_files.empty()) sketch_files(ctx, in.query_files, k1, S, in.whole_files, ld.queries, in.min_copies);
     const SketchSet &refs = ld.refs, &q = in.self() ? ld.refs : ld.queries;
     const size_t nq = q.names.size(), nr = refs.names.size();
     if (nr == 0 || nq == 0) refuse(dist_rules, std::string("no ") + (nr == 0 ? "reference" : "query") + " sketches");
@@ -204,7 +213,7 @@ int main_dist(int argc, char** argv) {
     CompareInputs in;
     double max_dist = 2.0;
     if (argc <= 2) { help_dist(); exit(1); }
-    static struct option long_options[] = {COMPARE_OPTIONS, {"max-dist", required_argument, 0, 'd'}, {"threads", required_argument, 0, 't'}, {"abund", no_argument, 0, 1008}, {0, 0, 0, 0}};
+    static struct option long_options[] = {COMPARE_OPTIONS, {"max-dist", required_argument, 0, 'd'}, {"threads", required_argument, 0, 't'}, {"abund", no_argument, 0, 1008}, {"min-copies", required_argument, 0, 1012}, {0, 0, 0, 0}};
     optind = 2;
     int c;
     while ((c = getopt_long(argc, argv, "hgk:f:r:R:Q:s:d:t:", long_options, nullptr)) != -1) {
@@ -213,6 +222,7 @@ int main_dist(int argc, char** argv) {
             case 'd': max_dist = atof(optarg); break;
             case 't': break;
             case 1008: in.abund = true; break;
+            case 1012: if (!parse_min_copies(optarg, in.min_copies)) in.min_copies = 0; break;
             default: help_dist(); exit(1);
         }
     }
@@ -225,7 +235,9 @@ int main_dist(int argc, char** argv) {
     if (in.ref_files.empty() == in.ref_json.empty()) refuse(dist_rules, "references come from -r <fasta> ... or from -R <sketches.json> ..., one of the two");
     if (!in.query_files.empty() && !in.query_json.empty()) refuse(dist_rules, "queries come from -f <fasta|fastq> ... or from -Q <sketches.json> ..., not both");
     if (in.whole_files && in.ref_files.empty() && in.query_files.empty()) refuse(dist_rules, "-g says how -r / -f files are sketched; sketches loaded with -R / -Q are what they are");
+    refuse_min_copies("dist", in.min_copies, in.whole_files, in.scaled_given);
     load_sketch_files(in, dist_rules, ld);
+    refuse_min_copies("dist", in.min_copies, in.whole_files, ld.largest_scaled != 0);
     if (in.abund && !in.scaled_given && ld.largest_scaled == 0)
         refuse(dist_rules, "--abund compares scaled sketches: give --scaled <n>, or -R / -Q files of `rkmh sketch --scaled <n> --abund`");
     const int k = run_k(dist_rules, ld.k);

@@ -1,5 +1,6 @@
-// rkmh_sample.cpp -- ONE scaled sketch per sequence file, built on the device (rk_sample_*, include/rkmh_amd.h "SAMPLE SKETCHES"): the
-// route of sketch_files_scaled for `sketch --scaled -g`, the query side of gather and multigather, and dist / manysearch with -g.
+// rkmh_sample.cpp -- ONE sketch per sequence file, built on the device (rk_sample_*, include/rkmh_amd.h "SAMPLE SKETCHES"): the
+// route of sketch_files_scaled for `sketch --scaled -g`, the query side of gather and multigather, and dist / manysearch with -g; and,
+// into a bottom sample ("BOTTOM SAMPLES"), the route of sketch_files for `sketch -g -s` and `dist -g -s`.
 // A file is never held whole: plain FASTQ text goes block by block through two alternating FASTQ slots (the next block is read while
 // the device works on this one), a BGZF file job by job through two device-text slots, everything else (FASTA, ordinary gzip,
 // standard input) through the sequential reader in bounded batches.  A block the device refuses -- text that is not four lines per
@@ -168,20 +169,27 @@ struct SampleFile {
 
 } // namespace
 
-// One sketch of all records of `path` into (values, abund); *nbases = the bases of its records.  `sample` is empty before and after.
-void sample_file_device(rk_ctx* ctx, rk_sample* sample, const char* path, uint64_t** values, uint32_t** abund, uint64_t* n, uint64_t* nbases) {
-    const double t0 = now_s();
+// All records of `path` into the empty `sample`, by whichever route the file takes.  The caller then takes what it wants from the
+// sample (rk_sample_finish, rk_sample_finish_bottom) and ends with sample_file_done.
+SampleFed sample_file_feed(rk_ctx* ctx, rk_sample* sample, const char* path) {
+    SampleFed fed;
+    fed.t0 = now_s();
     SampleFile F{ctx, sample, path};
     F.run();
-    const double t1 = now_s();
-    CKE(rk_sample_finish(sample, values, abund, n), path);
+    fed.route = F.route;
+    fed.blocks = F.blocks;
+    fed.t1 = now_s();
+    return fed;
+}
+// *nbases = the bases of the file's records; the timing line; `sample` is empty again
+void sample_file_done(rk_sample* sample, const char* path, const SampleFed& fed, uint64_t* nbases) {
     rk_sample_stats_t st;
     st.struct_size = sizeof st;
     CKE(rk_sample_stats(sample, &st), path);
     *nbases = st.nbases;
     if (g_timing)
         fprintf(stderr, "[rkmh timing] sample %s: %s route, %lld blocks, %llu sequences, %llu bases, %llu windows kept, %llu distinct, %u folds, %u batches run again: feed %.3f s, finish %.3f s\n",
-                path, F.route, (long long)F.blocks, (unsigned long long)st.nseq, (unsigned long long)st.nbases, (unsigned long long)st.kept, (unsigned long long)st.distinct,
-                st.folds, st.retries, t1 - t0, now_s() - t1);
+                path, fed.route, (long long)fed.blocks, (unsigned long long)st.nseq, (unsigned long long)st.nbases, (unsigned long long)st.kept, (unsigned long long)st.distinct,
+                st.folds, st.retries, fed.t1 - fed.t0, now_s() - fed.t1);
     CKE(rk_sample_reset(sample), path);
 }

@@ -4,6 +4,7 @@
 #include <cerrno>
 
 #include "rkmh_cli.hpp"
+#include "rkmh_min_copies.hpp"
 
 // ---- from sequence files.  The walk both kinds share: all(s) makes a sketch of every record of s, one(s) ONE sketch of all of them.
 template <class All, class One>
@@ -29,7 +30,28 @@ static void walk_files(const std::vector<const char*>& files, bool whole_files, 
         rk_seqset_free(&s);
     }
 }
-void sketch_files(rk_ctx* ctx, const std::vector<const char*>& files, const std::vector<int>& ks, int S, bool whole_files, SketchSet& out) {
+void sketch_files(rk_ctx* ctx, const std::vector<const char*>& files, const std::vector<int>& ks, int S, bool whole_files, SketchSet& out, uint64_t min_copies) {
+    if (whole_files && sample_on_device()) { // one sketch per file: a bottom sample on the device, no file held whole (rkmh_sample.cpp)
+        rk_sample* sample = nullptr;
+        CK(rk_sample_create_bottom(ctx, ks.data(), (int)ks.size(), S, min_copies, 0, &sample));
+        for (const char* f : files) {
+            const SampleFed fed = sample_file_feed(ctx, sample, f);
+            out.sk.resize(out.sk.size() + (size_t)S, 0);
+            out.lens.push_back(0);
+            CKE(rk_sample_finish_bottom(sample, &out.sk[out.sk.size() - (size_t)S], &out.lens.back()), f);
+            uint64_t threshold = 0, candidates = 0, weight = 0, nbases = 0;
+            uint32_t cuts = 0;
+            CKE(rk_sample_bottom_state(sample, &threshold, &candidates, &weight, &cuts), f);
+            sample_file_done(sample, f, fed, &nbases);
+            if (g_timing)
+                fprintf(stderr, "[rkmh timing] bottom sample %s: sketch size %d, min copies %llu: threshold %llu, %llu candidates of weight %llu, %u cuts\n", f, S,
+                        (unsigned long long)min_copies, (unsigned long long)threshold, (unsigned long long)candidates, (unsigned long long)weight, cuts);
+            out.names.push_back(f);
+            out.seq_len.push_back(nbases);
+        }
+        rk_sample_destroy(sample);
+        return;
+    }
     auto batch = [&](const rk_seqset& s, std::vector<uint64_t>& sk, std::vector<int32_t>& lens) {
         sk.assign((size_t)s.nseq * (size_t)S, 0);
         lens.assign((size_t)s.nseq, 0);
@@ -52,7 +74,9 @@ void sketch_files_scaled(rk_ctx* ctx, const std::vector<const char*>& files, con
         for (const char* f : files) {
             uint64_t *v = nullptr, n = 0, nbases = 0;
             uint32_t* a = nullptr;
-            sample_file_device(ctx, sample, f, &v, &a, &n, &nbases);
+            const SampleFed fed = sample_file_feed(ctx, sample, f);
+            CKE(rk_sample_finish(sample, &v, &a, &n), f);
+            sample_file_done(sample, f, fed, &nbases);
             out.values.insert(out.values.end(), v, v + n);
             if (out.with_abund) out.abund.insert(out.abund.end(), a, a + n);
             out.off.push_back(out.values.size());
@@ -108,10 +132,10 @@ static void json_escape(std::string& out, const char* s) {
     }
 }
 void write_sketch_json(FILE* fo, const std::vector<std::string>& names, const std::vector<uint64_t>& seq_len, const std::string& kstr,
-                       const std::vector<SketchRow>& rows, uint64_t scaled, uint64_t max_hash) {
+                       const std::vector<SketchRow>& rows, uint64_t scaled, uint64_t max_hash, uint64_t min_copies) {
     const std::string head = "{\"alphabet\":\"ATGC\",\"canonical\":\"true\",\"hashBits\":64,\"hashPolicy\":\"" + policy_text(g_policy) + "\",\"hashSeed\":" +
                              std::to_string(g_policy.seed) + ",\"hashType\":\"MurmurHash3_x64_128\",\"kmer\":\"" + kstr + "\"" +
-                             (scaled ? ",\"maxHash\":" + std::to_string(max_hash) : std::string()) + ",\"name\":\"";
+                             (scaled ? ",\"maxHash\":" + std::to_string(max_hash) : std::string()) + min_copies_json(min_copies) + ",\"name\":\"";
     const std::string scaled_key = scaled ? "\"scaled\":" + std::to_string(scaled) + "," : std::string();
     OutBuf o(fo);
     o.append("[");
@@ -156,6 +180,18 @@ bool parse_at_least_1(const char* text, int& v) {
     if (!parse_scaled(text, u) || u > 0x7fffffffull) return false;
     v = (int)u;
     return true;
+}
+bool parse_min_copies(const char* text, uint64_t& m) { return min_copies_from_text(text, m); }
+void refuse_min_copies(const char* command, uint64_t m, bool whole_files, bool scaled) {
+    const char* why = m == 0 ? "--min-copies takes a number of 1 .. 4294967295"
+                    : m == 1 ? nullptr
+                    : scaled ? "--min-copies filters bottom-s sketches (-s); scaled sketches keep every copy count with --abund"
+                    : !whole_files ? "--min-copies counts the copies of a k-mer over a whole file: it needs -g"
+                    : !sample_on_device() ? "--min-copies needs the sample built on the device: not with RKMH_SAMPLE_DEVICE=0"
+                    : nullptr;
+    if (!why) return;
+    fprintf(stderr, "rkmh %s: %s\n", command, why);
+    exit(1);
 }
 bool shared_option(int c, CompareInputs& in) {
     switch (c) {
