@@ -1029,6 +1029,78 @@ int rk_bottom_cut(rk_ctx* ctx, const uint64_t* values, const uint32_t* counts, u
 int rk_bottom_emit(const uint64_t* values, const uint32_t* counts, uint64_t n, int sketch_size, uint64_t min_copies, int distinct, uint64_t* row,
                    int32_t* len);
 
+/* ------------------------------------------------------------------------------------------------
+ * CLUSTER (`rkmh cluster`; what the sourmash family does with pairwise + cluster: the single-linkage clusters of a collection of
+ * scaled sketches at a similarity threshold).  These are this library's own definitions.
+ *   Inputs: n sketches with lengths len[i] < 2^31; a list of hits rk_search_hit {query, ref, shared} over those n sketches (SEARCH); a
+ *   measure and a threshold min_ppm in parts per million, 0 .. 1 000 000.
+ *   A hit LINKS i = query and j = ref when 0 <= i, j < n, i != j, shared >= 1 and
+ *       shared * 1000000 >= min_ppm * denom,   denom = len[i] + len[j] - shared  (RK_CLUSTER_JACCARD)
+ *                                              denom = min(len[i], len[j])       (RK_CLUSTER_MAX_CONTAINMENT)
+ *   evaluated exactly in signed 64-bit integers (shared * 10^6 < 2^51, |min_ppm * denom| < 2^53: nothing wraps), so host and device
+ *   agree bit for bit -- floating point, host only.  A hit whose shared exceeds what the lengths allow is no error: it is judged by
+ *   the formula as written (a denom of 0 or below links).
+ *   The graph is undirected: one direction of a pair is enough; duplicate hits, self hits and hits naming an index outside [0, n) change
+ *   nothing.  Answer: int32 labels[n], labels[i] = the smallest index in the connected component of i.  It follows that
+ *   labels[labels[i]] == labels[i] <= i; that the answer depends neither on the order nor on the multiplicity of the hits; that with no
+ *   linking hit labels[i] = i; that at min_ppm = 0 every hit with shared >= 1 links; and that at min_ppm = 1 000 000 under Jaccard only
+ *   identical sets link.
+ * rk_cluster_hits_host: host code, usable without a GPU (rk_cluster_host.cpp): union-find over the linking hits.  lens: n uint64.
+ * rk_cluster_hits: the same host arrays; uploads them (the lengths as CSR offsets), runs the device path, downloads the labels.
+ * rk_cluster_hits_device: resident hits (nhits of 12 bytes; may be NULL when nhits = 0) and the collection's CSR offsets (n + 1
+ * uint64): the length of sketch i is that of row i clamped to [0, nvalues], as every kernel of the layer takes it.  d_labels takes n
+ * int32.  It runs on hip_stream and SYNCHRONISES it, as rk_gather_scaled_device does: every round ends with a look at a 4-byte word.
+ * *rounds = the number of hook launches (the pointer may be NULL).  Every index is checked before it is used.
+ * rk_cluster_scaled: host CSR arrays of the collection the index was made from (nref = the index's); searches the collection against
+ * its own index at min_shared and clusters it; the hits never leave the device.  Never more than hit_cap hits are held (0: the
+ * library's default, RK_CLUSTER_HIT_CAP; any other value is taken as given, down to 1): the queries go through in blocks of at most
+ * (2^24 - 1) / (reference blocks) queries, the search's workgroup limit; the counting pass gives a block's total, a block that does not
+ * fit is halved, down to a single query, and a single query with more hits than hit_cap is emitted and clustered in pieces of hit_cap
+ * hits.  Each block (each piece) is hooked to its fixpoint before its hits are dropped: sound because a tree never splits (below), so
+ * two sketches once under one root stay under one root.  The work buffers are the index's own, under its mutex, as the search's are.
+ * rk_cluster_scaled_device: the same on resident d_values / d_offsets (nvalues uint64 behind d_values); d_labels takes nref int32;
+ * runs on hip_stream and SYNCHRONISES it.
+ * All entries refuse (RK_ERR_ARG, a size beyond its limit RK_ERR_LIMIT) before anything is launched: NULL, n < 1, n > 2^31 - 1, a
+ * measure outside the two defined, min_ppm > 1 000 000, min_shared < 1, an index of another context or of another number of sketches;
+ * host arrays only: a length of 2^31 or more, offsets that decrease.
+ * rk_cluster_members: host only.  *ncl = the number of clusters; cl_off[0 .. ncl] and members[n]: the clusters ordered by their
+ * smallest member, members ascending inside a cluster (cluster c = members[cl_off[c], cl_off[c + 1])); rep[c] = its member with the
+ * largest len, among equal lengths the lowest index.  cl_off takes n + 1, members and rep n int32.  RK_ERR_ARG for labels that do not
+ * satisfy labels[labels[i]] == labels[i] <= i.
+ * The kernels (rk_cluster.hip): hook and compress on parent[n].  k_cluster_init: parent[i] = i.  k_cluster_hook: lanes stride the hits
+ * under a grid cap; each applies the link test, reads pu = parent[u], pv = parent[v] and, when they differ,
+ * atomicMin(&parent[max(pu, pv)], min(pu, pv)) and marks the round as changed.  k_cluster_compress: every node follows parent[] to
+ * its root and stores it.  The loop: hook; while the hook changed something: compress, hook.  Why this is right:
+ *   - parent[i] <= i always, and a parent value only decreases: init, atomicMin with a smaller value, compress to an ancestor.
+ *   - Before every hook every tree is a star (init; compress).  A hook therefore writes only to nodes that were roots when it began,
+ *     and only roots of that moment as values; a changed round makes at least one of those roots a non-root: the loop ends.
+ *   - A hook that changes nothing found pu == pv for every linking hit, exactly (the launch before it is complete): both ends of every
+ *     linking hit are under one root.  Links are only made between the ends of linking hits, so a tree lies inside one component:
+ *     at the fixpoint trees and components are the same sets.  A root is the minimum of its tree (parent[i] <= i), so the label is
+ *     the component's smallest index.
+ *   - An atomicMin that overrides an earlier link of the same round (a hung under c, then under b < c) loses that link for now; the
+ *     hit that made it is looked at again in the next round, which the override has marked as changed.
+ *   - Trees never split: the star under a root a stays under a, whatever a is hung under.  The trees after a round are unions of the
+ *     trees before it; that is what lets rk_cluster_scaled drop a block's hits once they are at their fixpoint.
+ *   Integer atomics on global memory are device scope and commute (the precedent: k_mg_remove); which of two links wins is not fixed,
+ *   the fixpoint is.  Plain reads of parent[] inside a launch may be stale on a part with several L2s; harmless: in a hook the
+ *   non-roots are not written and a root's stale value is the root itself, still in the tree and a root when the launch began; in a
+ *   compress an older parent is still an ancestor and roots are not written; launch boundaries make the writes of the launch before
+ *   visible. */
+#define RK_CLUSTER_JACCARD 0
+#define RK_CLUSTER_MAX_CONTAINMENT 1
+#define RK_CLUSTER_HIT_CAP (1ull << 25) /* hits held at once by rk_cluster_scaled when hit_cap = 0: 384 MB */
+int rk_cluster_hits_host(const rk_search_hit* hits, uint64_t nhits, const uint64_t* lens, int64_t n, int measure, uint32_t min_ppm, int32_t* labels);
+int rk_cluster_hits(rk_ctx* ctx, const rk_search_hit* hits, uint64_t nhits, const uint64_t* lens, int64_t n, int measure, uint32_t min_ppm,
+                    int32_t* labels);
+int rk_cluster_hits_device(rk_ctx* ctx, const void* d_hits, uint64_t nhits, const void* d_offsets, int64_t n, uint64_t nvalues, int measure,
+                           uint32_t min_ppm, void* d_labels, uint32_t* rounds, void* hip_stream);
+int rk_cluster_scaled(rk_ctx* ctx, rk_scaled_index* idx, const uint64_t* r_values, const uint64_t* r_offsets, int64_t nref, int min_shared,
+                      int measure, uint32_t min_ppm, uint64_t hit_cap, int32_t* labels);
+int rk_cluster_scaled_device(rk_ctx* ctx, rk_scaled_index* idx, const void* d_values, const void* d_offsets, int64_t nref, uint64_t nvalues,
+                             int min_shared, int measure, uint32_t min_ppm, uint64_t hit_cap, void* d_labels, void* hip_stream);
+int rk_cluster_members(const int32_t* labels, const uint64_t* lens, int64_t n, int64_t* ncl, int32_t* cl_off, int32_t* members, int32_t* rep);
+
 #ifdef __cplusplus
 }
 #endif

@@ -283,6 +283,15 @@ _SIGS = {
                                                C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p]),
     "rk_multigather_scaled_host": (C.c_int, [_u64p, _u64p, C.c_int64, _u64p, _u32p, _u64p, C.c_int64, C.c_int, C.c_int, C.c_int, C.POINTER(_i32p),
                                              C.POINTER(_u64p), _u64p, C.POINTER(C.c_uint64)]),
+    # cluster: include/rkmh_amd.h "CLUSTER"
+    "rk_cluster_hits_host": (C.c_int, [_i32p, C.c_uint64, _u64p, C.c_int64, C.c_int, C.c_uint32, _i32p]),
+    "rk_cluster_hits": (C.c_int, [C.c_void_p, _i32p, C.c_uint64, _u64p, C.c_int64, C.c_int, C.c_uint32, _i32p]),
+    "rk_cluster_hits_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int64, C.c_uint64, C.c_int, C.c_uint32, C.c_void_p,
+                                         C.POINTER(C.c_uint32), C.c_void_p]),
+    "rk_cluster_scaled": (C.c_int, [C.c_void_p, C.c_void_p, _u64p, _u64p, C.c_int64, C.c_int, C.c_int, C.c_uint32, C.c_uint64, _i32p]),
+    "rk_cluster_scaled_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_uint64, C.c_int, C.c_int, C.c_uint32, C.c_uint64,
+                                           C.c_void_p, C.c_void_p]),
+    "rk_cluster_members": (C.c_int, [_i32p, _u64p, C.c_int64, C.POINTER(C.c_int64), _i32p, _i32p, _i32p]),
     # the sample accumulator: include/rkmh_amd.h "SAMPLE SKETCHES"
     "rk_sample_create": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int, C.c_uint64, C.c_int, C.c_uint64, C.POINTER(C.c_void_p)]),
     "rk_sample_destroy": (None, [C.c_void_p]),
@@ -1103,6 +1112,43 @@ def search_min_count(min_containment, length):
     return int(t.value)
 
 
+RK_CLUSTER_JACCARD, RK_CLUSTER_MAX_CONTAINMENT = 0, 1  # include/rkmh_amd.h "CLUSTER": the measure of a link
+
+
+def _cluster_args(hits, lens):
+    """the hits and lengths of a clustering, checked -> (int32 [nhits, 3], uint64 [n], labels int32 [n])"""
+    hits = np.ascontiguousarray(hits, dtype=np.int32).reshape(-1, 3)
+    lens = np.ascontiguousarray(lens, dtype=np.uint64)
+    if lens.ndim != 1:
+        raise ValueError("lens is not one-dimensional")
+    return hits, lens, np.zeros(len(lens), dtype=np.int32)
+
+
+def cluster_hits_host(hits, lens, measure=RK_CLUSTER_JACCARD, min_ppm=0):
+    """rk_cluster_hits_host (host code, no GPU): the single-linkage clusters of n sketches of the lengths `lens` under the hits (rows
+    (query, reference, shared)) that link at `measure` and `min_ppm` parts per million -> int32 [n]: the smallest index of every
+    sketch's cluster."""
+    hits, lens, labels = _cluster_args(hits, lens)
+    _chk(load_library().rk_cluster_hits_host(_p(hits, C.c_int32), C.c_uint64(len(hits)), _p(lens, C.c_uint64), len(lens), int(measure),
+                                             C.c_uint32(int(min_ppm)), _p(labels, C.c_int32)))
+    return labels
+
+
+def cluster_members(labels, lens):
+    """rk_cluster_members (host code, no GPU) -> (cl_off int32 [ncl + 1], members int32 [n], rep int32 [ncl]): the clusters ordered by
+    their smallest member, members ascending; rep: the member with the largest length, among equal lengths the lowest index."""
+    labels = np.ascontiguousarray(labels, dtype=np.int32)
+    lens = np.ascontiguousarray(lens, dtype=np.uint64)
+    if labels.ndim != 1 or lens.shape != labels.shape:
+        raise ValueError("%d labels for %d lengths" % (labels.size, lens.size))
+    n = len(labels)
+    ncl = C.c_int64()
+    cl_off, members, rep = np.zeros(n + 1, dtype=np.int32), np.zeros(max(n, 1), dtype=np.int32), np.zeros(max(n, 1), dtype=np.int32)
+    _chk(load_library().rk_cluster_members(_p(labels, C.c_int32), _p(lens, C.c_uint64), n, C.byref(ncl), _p(cl_off, C.c_int32), _p(members, C.c_int32),
+                                           _p(rep, C.c_int32)))
+    return cl_off[: ncl.value + 1].copy(), members[:n], rep[: ncl.value].copy()
+
+
 def _multigather_args(q_values, q_offsets, q_abund, max_rounds):
     """the query batch of a multigather, checked -> (values, offsets, abundances or None, nq, max_rounds, row_offsets uint64 [nq + 1])"""
     q_values, q_offsets = _csr(q_values, q_offsets)
@@ -1213,6 +1259,26 @@ class ScaledIndex:
                                                     C.c_void_p(d_out4_ptr), C.c_void_p(d_wunique_ptr), C.c_uint64(int(cap_rows)), C.c_void_p(d_row_offsets_ptr),
                                                     C.byref(n), C.c_void_p(stream)))
         return int(n.value)
+
+    def cluster(self, r_values, r_offsets, min_shared=1, measure=RK_CLUSTER_JACCARD, min_ppm=0, hit_cap=0):
+        """rk_cluster_scaled: the collection the index was made from (the same CSR arrays) searched against the index and grouped
+        into single-linkage clusters -> int32 [nref]: the smallest index of every sketch's cluster.  The hits stay on the device,
+        never more than hit_cap of them at once (0: the library's default)."""
+        r_values, r_offsets = _csr(r_values, r_offsets)
+        labels = np.zeros(max(len(r_offsets) - 1, 1), dtype=np.int32)
+        _chk(self._lib.rk_cluster_scaled(self._ctx._h, self._h, _p(r_values, C.c_uint64), _p(r_offsets, C.c_uint64), len(r_offsets) - 1, int(min_shared),
+                                         int(measure), C.c_uint32(int(min_ppm)), C.c_uint64(int(hit_cap)), _p(labels, C.c_int32)))
+        return labels[: len(r_offsets) - 1]
+
+    def cluster_device(self, d_values_ptr, d_offsets_ptr, nref, nvalues, d_labels_ptr, min_shared=1, measure=RK_CLUSTER_JACCARD, min_ppm=0, hit_cap=0,
+                       stream=None):
+        """rk_cluster_scaled_device: the same on the resident CSR arrays of the collection (raw device pointers; d_labels: nref int32).
+        Runs on `stream` (as for search_device) and synchronises it.  Rows are clamped to [0, nvalues] on the device."""
+        if stream is None:
+            stream = self._ctx.stream
+        _chk(self._lib.rk_cluster_scaled_device(self._ctx._h, self._h, C.c_void_p(d_values_ptr), C.c_void_p(d_offsets_ptr), int(nref),
+                                                C.c_uint64(int(nvalues)), int(min_shared), int(measure), C.c_uint32(int(min_ppm)),
+                                                C.c_uint64(int(hit_cap)), C.c_void_p(d_labels_ptr), C.c_void_p(stream)))
 
 
 def _abund(abund, values):
@@ -1681,6 +1747,27 @@ class Context:
         _chk(self._lib.rk_scaled_index_create_device(self._h, C.c_void_p(d_values_ptr), C.c_void_p(d_offsets_ptr), int(nref), C.c_uint64(int(nvalues)),
                                                      C.c_void_p(stream), C.byref(h)))
         return ScaledIndex(self, h)
+
+    # ---- cluster ---------------------------------------------------------------------------------
+    def cluster_hits(self, hits, lens, measure=RK_CLUSTER_JACCARD, min_ppm=0):
+        """rk_cluster_hits: cluster_hits_host's answer from the device: the hits and lengths are uploaded, hooked and compressed to
+        the fixpoint, the labels downloaded -> int32 [n]."""
+        hits, lens, labels = _cluster_args(hits, lens)
+        _chk(self._lib.rk_cluster_hits(self._h, _p(hits, C.c_int32), C.c_uint64(len(hits)), _p(lens, C.c_uint64), len(lens), int(measure),
+                                       C.c_uint32(int(min_ppm)), _p(labels, C.c_int32)))
+        return labels
+
+    def cluster_hits_device(self, d_hits_ptr, nhits, d_offsets_ptr, n, nvalues, d_labels_ptr, measure=RK_CLUSTER_JACCARD, min_ppm=0, stream=None):
+        """rk_cluster_hits_device: resident hits (raw device pointers; nhits rows of 3 int32), the collection's CSR offsets (n + 1
+        uint64; rows clamped to [0, nvalues]) -> the number of hook launches; d_labels takes n int32.  Runs on `stream` (as for
+        compare_sketches_device) and synchronises it."""
+        if stream is None:
+            stream = self.stream
+        rounds = C.c_uint32()
+        _chk(self._lib.rk_cluster_hits_device(self._h, C.c_void_p(d_hits_ptr), C.c_uint64(int(nhits)), C.c_void_p(d_offsets_ptr), int(n),
+                                              C.c_uint64(int(nvalues)), int(measure), C.c_uint32(int(min_ppm)), C.c_void_p(d_labels_ptr),
+                                              C.byref(rounds), C.c_void_p(stream)))
+        return int(rounds.value)
 
     # ---- gather ----------------------------------------------------------------------------------
     def gather_scaled(self, q, r_values, r_offsets, min_shared=1, max_rounds=None):

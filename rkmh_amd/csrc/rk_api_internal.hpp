@@ -9,12 +9,13 @@
 //   rk_frontend.hip  FASTQ slots (text parsed on the device), BGZF jobs inflated on the device, reference FASTA through the device
 //   rk_call.hip      `call`
 //   rk_pairs.hip     all-pairs comparison of bottom-S sketches
-//   rk_sets.hpp      what the four parts below share: the index object, clamped CSR rows, the lookup in an ascending array, 64-bit shuffles, the
+//   rk_sets.hpp      what the five parts below share: the index object, clamped CSR rows, the lookup in an ascending array, 64-bit shuffles, the
 //                    order-preserving compaction (k_keep_count, k_scan_blocks, k_keep_bounds, k_keep_scatter), checks and upload of a CSR side
 //   rk_scaled.hip    scaled sketches: the keep step of the general path, all-pairs intersection of variable-length sets, plain and weighted
 //   rk_gather.hip    gather: the greedy decomposition of a scaled sketch into reference sketches, its state resident across rounds
 //   rk_search.hip    search: the resident inverted index of scaled sketches (value -> references) and the thresholded search on it
 //   rk_multigather.hip  multigather: gather for a batch of queries through that index, counts kept up to date by integer atomics
+//   rk_cluster.hip   cluster: hook and compress on the hits of a search; the self-search of a collection, block by block, hits resident
 //   rk_sample.hip    the sample accumulator: one scaled sketch built on the device from reads fed batch by batch (fused hash-and-keep, folds)
 //   rk_bottom.hip    the cut of a bottom sample: where the bottom sketch_size of a sorted counted set ends (block weights, scan, the crossing block)
 #pragma once

@@ -242,7 +242,7 @@ int rk::search_emit(rk_scaled_index* ix, const uint64_t* d_qv, const uint64_t* d
 extern "C" void rk_scaled_index_destroy(rk_scaled_index* ix) {
     if (!ix) return;
     hipError_t e = hipSetDevice(ix->device); (void)e;
-    for (DevBuf* b : {&ix->keys, &ix->post_off, &ix->post, &ix->w_cnt, &ix->w_pre, &ix->w_qv, &ix->w_qo, &ix->w_qmin, &ix->w_hits, &ix->w_mg, &ix->w_mg_io, &ix->w_mg_out}) b->release();
+    for (DevBuf* b : {&ix->keys, &ix->post_off, &ix->post, &ix->w_cnt, &ix->w_pre, &ix->w_qv, &ix->w_qo, &ix->w_qmin, &ix->w_hits, &ix->w_cl, &ix->w_mg, &ix->w_mg_io, &ix->w_mg_out}) b->release();
     delete ix;
 }
 

@@ -1,5 +1,6 @@
-// rk_sets.hpp -- what the parts that work on sets of scaled sketches (rk_scaled.hip, rk_gather.hip, rk_search.hip, rk_multigather.hip)
-// share: the resident inverted index and the steps of a search on it (defined in rk_search.hip, used by rk_multigather.hip too), rows
+// rk_sets.hpp -- what the parts that work on sets of scaled sketches (rk_scaled.hip, rk_gather.hip, rk_search.hip, rk_multigather.hip,
+// rk_cluster.hip) share: the resident inverted index and the steps of a search on it (defined in rk_search.hip, used by rk_multigather.hip
+// and rk_cluster.hip too), rows
 // of a CSR side clamped on the device, the lookup in an ascending array, 64-bit shuffles, the order-preserving compaction, and the host
 // checks and upload of a CSR side.  Everything in the unnamed namespace has internal linkage: each part compiles its own copy of what it uses.
 #pragma once
@@ -13,6 +14,7 @@ struct rk_scaled_index {
     uint64_t npost = 0, nkeys = 0;
     DevBuf keys, post_off, post;
     DevBuf w_cnt, w_pre, w_qv, w_qo, w_qmin, w_hits; // searches: per-workgroup hit counts, their scan, an uploaded query batch, its hits
+    DevBuf w_cl; // cluster (rk_cluster.hip): the flag word of the rounds, then the host entry's parent[]
     DevBuf w_mg, w_mg_io, w_mg_out; // multigather: the state of one call (candidates, counts, key positions, alive bytes, rows); the host entry's row offsets and abundances; its packed answer
     std::mutex mu;
 };

@@ -13,6 +13,7 @@
 //   rkmh_sketches.cpp   sketch sets: made from sequence files, written as JSON, loaded from -R / -Q files, cut to one scaled
 //   rkmh_sample.cpp     one scaled sketch per sequence file built on the device: the -g / one-query-per-file route of the sketch sets
 //   rkmh_compare.cpp    sketch, dist, gather, multigather and manysearch
+//   rkmh_cluster.cpp    cluster
 //   rkmh_hpv16.cpp      hpv16
 #pragma once
 #include <getopt.h>
@@ -144,6 +145,7 @@ struct CompareRules { // where the two differ in what they accept and in their w
 };
 [[noreturn]] void refuse(const CompareRules& rules, const std::string& why);
 int one_k(const CompareInputs& in, const CompareRules& rules); // -k, 0 without one; several are refused
+int run_k(const CompareRules& rules, int k); // -k, or what the sketch files said, or the default; inside the library's range (rkmh_compare.cpp)
 // The -R and -Q files: each agrees in itself (load_sketch_json), with the others, with -k / -s / --scaled where given, and with the
 // run's policy.  Bottom-s files join refs / queries; scaled files are kept as loaded, each at its own "scaled", until the run's value
 // is known.  k: one_k()'s answer, then what the files said; S likewise (0: nobody said).
@@ -168,6 +170,7 @@ int main_dist(int argc, char** argv);
 int main_gather(int argc, char** argv);
 int main_multigather(int argc, char** argv);
 int main_manysearch(int argc, char** argv);
+int main_cluster(int argc, char** argv);
 int main_hash(int argc, char** argv);
 int main_hpv16(int argc, char** argv);
 int main_pack(int argc, char** argv);

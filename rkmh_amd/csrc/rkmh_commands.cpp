@@ -28,6 +28,7 @@ void print_help() {
             "  gather              decompose a sample's scaled sketch into references, greedily: what each explains once the better matches are taken out\n"
             "  multigather         gather for many queries at once, through an inverted index of the references: the lines of gather, byte for byte\n"
             "  manysearch          search many scaled sketches against a collection through an inverted index: only the pairs that match, in dist's columns\n"
+            "  cluster             group a collection of scaled sketches into single-linkage clusters at a Jaccard or max-containment threshold\n"
             "  pack                write reads as a packed file (2 bits per base + names): stream|filter -F <file> classifies it without parsing\n"
             "Run a command without options for its help text.\n");
 }

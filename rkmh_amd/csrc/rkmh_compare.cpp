@@ -100,7 +100,7 @@ int main_sketch(int argc, char** argv) {
 }
 
 // -k, or what the sketch files said, or the default; inside the library's range
-static int run_k(const CompareRules& rules, int k) {
+int run_k(const CompareRules& rules, int k) {
     if (k == 0) k = default_k();
     if (k < 1 || k > RK_MAX_K) refuse(rules, "k-mer size outside 1 .. " + std::to_string(RK_MAX_K));
     return k;

@@ -38,6 +38,7 @@ int main(int argc, char** argv) {
     if (cmd == "gather") return main_gather(argc, argv);
     if (cmd == "multigather") return main_multigather(argc, argv);
     if (cmd == "manysearch") return main_manysearch(argc, argv);
+    if (cmd == "cluster") return main_cluster(argc, argv);
     if (cmd == "pack") return main_pack(argc, argv);
     if (cmd == "hpv16") return main_hpv16(argc, argv);
     print_help();
