@@ -4,9 +4,9 @@ ARCH := gfx950
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall -Wno-unused-result $(EXTRA_HIPFLAGS)
 CSRC := rkmh_amd/csrc
 LIB := rkmh_amd/lib/librkmh_amd.so
-OBJS := $(CSRC)/rk_kernels.o $(CSRC)/rk_classify.o $(CSRC)/rk_kmer.o $(CSRC)/rk_count.o $(CSRC)/rk_call.o $(CSRC)/rk_sort.o $(CSRC)/rk_fastq.o $(CSRC)/rk_fasta.o $(CSRC)/rk_inflate.o $(CSRC)/rk_api.o $(CSRC)/rk_general.o $(CSRC)/rk_route.o $(CSRC)/rk_index.o $(CSRC)/rk_counters.o $(CSRC)/rk_frontend.o $(CSRC)/rk_gunzip.o $(CSRC)/rk_packed.o $(CSRC)/rk_pack.o $(CSRC)/rk_parse.o $(CSRC)/rk_pool.o $(CSRC)/rk_parse_blocks.o $(CSRC)/rk_bgzf.o $(CSRC)/rk_format.o $(CSRC)/rk_synth.o $(CSRC)/rk_policy.o $(CSRC)/rk_pairs.o $(CSRC)/rk_pairs_host.o $(CSRC)/rk_scaled.o $(CSRC)/rk_scaled_host.o $(CSRC)/rk_gather.o $(CSRC)/rk_search.o $(CSRC)/rk_multigather.o $(CSRC)/rk_cluster.o $(CSRC)/rk_cluster_host.o $(CSRC)/rk_sample.o $(CSRC)/rk_bottom.o $(CSRC)/rk_bottom_host.o
+OBJS := $(CSRC)/rk_kernels.o $(CSRC)/rk_classify.o $(CSRC)/rk_kmer.o $(CSRC)/rk_count.o $(CSRC)/rk_call.o $(CSRC)/rk_sort.o $(CSRC)/rk_fastq.o $(CSRC)/rk_fasta.o $(CSRC)/rk_inflate.o $(CSRC)/rk_api.o $(CSRC)/rk_general.o $(CSRC)/rk_route.o $(CSRC)/rk_index.o $(CSRC)/rk_counters.o $(CSRC)/rk_frontend.o $(CSRC)/rk_gunzip.o $(CSRC)/rk_packed.o $(CSRC)/rk_pack.o $(CSRC)/rk_parse.o $(CSRC)/rk_pool.o $(CSRC)/rk_parse_blocks.o $(CSRC)/rk_bgzf.o $(CSRC)/rk_format.o $(CSRC)/rk_synth.o $(CSRC)/rk_policy.o $(CSRC)/rk_pairs.o $(CSRC)/rk_pairs_host.o $(CSRC)/rk_scaled.o $(CSRC)/rk_scaled_host.o $(CSRC)/rk_gather.o $(CSRC)/rk_search.o $(CSRC)/rk_multigather.o $(CSRC)/rk_cluster.o $(CSRC)/rk_cluster_host.o $(CSRC)/rk_sample.o $(CSRC)/rk_bottom.o $(CSRC)/rk_bottom_host.o $(CSRC)/rk_screen.o $(CSRC)/rk_screen_host.o
 
-API_DEPS := $(CSRC)/rk_api_internal.hpp $(CSRC)/rk_index_plan.hpp $(CSRC)/rk_sets.hpp $(CSRC)/rk_kernels.hpp $(CSRC)/rk_device.hpp include/rkmh_amd.h
+API_DEPS := $(CSRC)/rk_api_internal.hpp $(CSRC)/rk_index_plan.hpp $(CSRC)/rk_sets.hpp $(CSRC)/rk_tile_walk.hpp $(CSRC)/rk_kernels.hpp $(CSRC)/rk_device.hpp include/rkmh_amd.h
 
 all: $(LIB) bin/rkmh oracle
 
@@ -90,6 +90,11 @@ $(CSRC)/rk_bottom.o: $(CSRC)/rk_bottom.hip $(API_DEPS)
 	@mkdir -p build/isa_bottom
 	cd build/isa_bottom && $(HIPCC) $(HIPFLAGS) -save-temps -c $(CURDIR)/$< -o $(CURDIR)/$@
 	@cd build/isa_bottom && rm -f *.bc *.hipi *.out *.resolution.txt *.hipfb *host-x86_64*.s *.o
+# screen: window hashes counted against the keys of the reference sketches, rows and owners, ISA under build/isa_screen
+$(CSRC)/rk_screen.o: $(CSRC)/rk_screen.hip $(API_DEPS)
+	@mkdir -p build/isa_screen
+	cd build/isa_screen && $(HIPCC) $(HIPFLAGS) -save-temps -c $(CURDIR)/$< -o $(CURDIR)/$@
+	@cd build/isa_screen && rm -f *.bc *.hipi *.out *.resolution.txt *.hipfb *host-x86_64*.s *.o
 $(CSRC)/rk_pack.o: $(CSRC)/rk_pack.cpp $(CSRC)/rk_filter_rule.hpp include/rkmh_amd.h
 	g++ -O3 -std=c++17 -fPIC -Wall -c $< -o $@
 # the host read parser: pool, reader, block front end, BGZF
@@ -106,6 +111,8 @@ $(CSRC)/rk_bottom_host.o: $(CSRC)/rk_bottom_host.cpp include/rkmh_amd.h
 	g++ -O2 -std=c++17 -fPIC -Wall -c $< -o $@
 $(CSRC)/rk_cluster_host.o: $(CSRC)/rk_cluster_host.cpp include/rkmh_amd.h
 	g++ -O2 -std=c++17 -fPIC -Wall -c $< -o $@
+$(CSRC)/rk_screen_host.o: $(CSRC)/rk_screen_host.cpp include/rkmh_amd.h
+	g++ -O2 -std=c++17 -fPIC -Wall -c $< -o $@
 $(CSRC)/rk_scaled_host.o: $(CSRC)/rk_scaled_host.cpp include/rkmh_amd.h
 	g++ -O2 -std=c++17 -fPIC -Wall -pthread -c $< -o $@
 $(CSRC)/rk_synth.o: $(CSRC)/rk_synth.cpp include/rkmh_amd.h
@@ -116,7 +123,7 @@ $(LIB): $(OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(OBJS) -lz -lpthread -ldl
 
 # the command line: one program from the rkmh_*.cpp files (what each holds: rkmh_cli.hpp)
-CLI_SRCS := $(CSRC)/rkmh_main.cpp $(CSRC)/rkmh_exit.cpp $(CSRC)/rkmh_frontends.cpp $(CSRC)/rkmh_rawreads.cpp $(CSRC)/rkmh_packed.cpp $(CSRC)/rkmh_refs.cpp $(CSRC)/rkmh_classify.cpp $(CSRC)/rkmh_commands.cpp $(CSRC)/rkmh_sketch_json.cpp $(CSRC)/rkmh_sketches.cpp $(CSRC)/rkmh_sample.cpp $(CSRC)/rkmh_compare.cpp $(CSRC)/rkmh_cluster.cpp $(CSRC)/rkmh_hpv16.cpp
+CLI_SRCS := $(CSRC)/rkmh_main.cpp $(CSRC)/rkmh_exit.cpp $(CSRC)/rkmh_frontends.cpp $(CSRC)/rkmh_rawreads.cpp $(CSRC)/rkmh_packed.cpp $(CSRC)/rkmh_refs.cpp $(CSRC)/rkmh_classify.cpp $(CSRC)/rkmh_commands.cpp $(CSRC)/rkmh_sketch_json.cpp $(CSRC)/rkmh_sketches.cpp $(CSRC)/rkmh_sample.cpp $(CSRC)/rkmh_compare.cpp $(CSRC)/rkmh_cluster.cpp $(CSRC)/rkmh_screen.cpp $(CSRC)/rkmh_hpv16.cpp
 bin/rkmh: $(CLI_SRCS) $(CSRC)/rkmh_cli.hpp $(LIB) include/rkmh_amd.h
 	@mkdir -p bin
 	g++ -O2 -std=c++17 -Wall -o $@ $(CLI_SRCS) -Irkmh_amd/csrc -Lrkmh_amd/lib -lrkmh_amd -Wl,-rpath,'$$ORIGIN/../rkmh_amd/lib'

@@ -1101,6 +1101,89 @@ int rk_cluster_scaled_device(rk_ctx* ctx, rk_scaled_index* idx, const void* d_va
                              int min_shared, int measure, uint32_t min_ppm, uint64_t hit_cap, void* d_labels, void* hip_stream);
 int rk_cluster_members(const int32_t* labels, const uint64_t* lens, int64_t n, int64_t* ncl, int32_t* cl_off, int32_t* members, int32_t* rep);
 
+/* ------------------------------------------------------------------------------------------------
+ * SCREEN (`rkmh screen`; what Mash calls screen: which reference sketches are CONTAINED in a read set -- a metagenome, a mixed
+ * sample -- rather than how similar the whole set is to each).  These are this library's own definitions.
+ *   Inputs: nref reference rows in CSR (uint64 values[], uint64 offsets[nref + 1]); every row ascending and non-zero; REPEATS INSIDE A
+ *   ROW ARE ALLOWED (multiset policies write them); rows may be empty.  R_r is the set of distinct values of row r, len_r = |R_r|: the
+ *   collapsed row.  The bottom-s rows of rk_sketch_batch / `rkmh sketch -s` / Mash are the intended input; any such rows work.
+ *   W is the multiset of the non-zero window hashes of every sequence fed: windows, the pooled k list, the policy and invalid bases
+ *   exactly as SAMPLE SKETCHES define them.  c(v) is the multiplicity of v in W, REPORTED as min(c, 2^32 - 1); counts injected with
+ *   rk_screen_add_counts add to it.  min_copies m is 1 .. 2^32 - 1; v is PRESENT when the reported c(v) >= m.
+ *   Per reference r, four uint32 at out4[r * 4]:
+ *     shared   #{v in R_r : v present}
+ *     median   the lower median of the reported c(v) over the present v in R_r: the element at index (shared - 1) / 2 in ascending
+ *              order; 0 when shared = 0
+ *     wshared, wmedian   the same two numbers over the present v in R_r whose OWNER is r
+ *   owner(v) is the reference in v's posting list (the references whose R holds v) with the largest shared_r / len_r, compared as
+ *   shared_a * len_b > shared_b * len_a in unsigned 64-bit (both factors are below 2^31: nothing wraps); among equal ratios the lowest
+ *   reference index.  This is Mash's one-pass winner-takes-all.
+ *   It follows that wshared_r <= shared_r; that the wshared of all references sum to the number of present keys; that the reference
+ *   with the best ratio (lowest index among equals) has wshared = shared; that for pairwise disjoint rows w* = *; that of a reference
+ *   given twice the second copy has wshared = 0; that feeding a read set twice doubles every count; and that batch boundaries, feed
+ *   order and grid size never reach the result.
+ *   IDENTITY is host arithmetic, floating point only: (shared / len)^(1 / k); 0 when shared = 0 (or len = 0), 1 when shared = len.
+ *   There is no p-value: Mash's needs genome-size and k-mer-space assumptions that this library has no pinned definition for.
+ *   On the device a screen is the inverted index of SEARCH over the collapsed rows (keys, post_off, post), pos[] -- where every value
+ *   of a collapsed row stands in keys --, uint64 counts[nkeys] and a DIRECTORY over the leading bits below the largest key (about two
+ *   buckets per key, 16 .. 2^24 buckets, chosen from nkeys at create): memory is O(reference values), whatever is fed.
+ *   The kernels (rk_screen.hip).  k_screen_count walks the windows of a resident batch exactly as k_sample_keep does (the walk is one
+ *   piece of device code, rk_tile_walk.hpp); a hash above the largest key is rejected, any other is looked up -- one directory read,
+ *   then a search among the few keys of that bucket -- and a match adds 1 to counts[position]: ONE 64-BIT atomicAdd ON GLOBAL MEMORY,
+ *   its result unused.  Integer adds commute (the precedent: k_mg_remove, k_cluster_hook), so the counts never depend on the order of
+ *   arrival; 64-bit counters cannot overflow, so there is no saturation logic: the clamp to 2^32 - 1 happens where counts are read.
+ *   Lanes of a wave that hit the same key are not combined.  There is no staging array, no cursor and no look from the host: a feed of
+ *   resident bases is asynchronous.  k_screen_rows<plain>: one wave per reference strides pos[] of the row, loads and clamps the
+ *   counts; shared from ballot popcounts, the median by bisection on the VALUE (at most 32 passes of "how many qualifying counts are
+ *   <= mid": no sort, no LDS array).  k_screen_owner: one lane per present key (one wave for posting lists of 64 entries or more)
+ *   picks the owner by the rule above from the shared of the first run, 2^32 - 1 for a key that is not present.  k_screen_rows<owned>
+ *   runs again with the test owner == r.  Every index is checked before it is used.
+ * rk_screen_create: collapses the rows on the host, builds the index (rk_scaled_index_create), pos[] and the directory, zeroes the
+ *   counts.  Refuses before anything is launched: NULL, nks outside 1 .. RK_MAX_KS, a k outside 1 .. RK_MAX_K, nref < 1 (RK_ERR_ARG);
+ *   offsets that decrease, a row that descends or holds 0 (RK_ERR_ARG); nref > 2^31 - 1, a row of 2^31 values or more, more than
+ *   2^32 - 1 collapsed values (RK_ERR_LIMIT).  The screen uses the policy its context has at each feed and is used with that context
+ *   only; destroy it before the context.
+ * rk_screen_add_batch: host arrays as for rk_sample_add_batch, the same refusals, uploaded in pieces of about 64 MB of whole
+ *   sequences on the context's stream; synchronises it.
+ * rk_screen_add_batch_device: resident bases and uint32 offsets[nseq + 1], the form rk_sample_add_batch_device takes; ASYNCHRONOUS
+ *   on hip_stream (NULL = HIP's null stream): it needs no look at a cursor.  The other entries work on the context's stream: the
+ *   caller orders them behind its own stream (synchronise it before rows, counts, stats or reset).  Offsets that do not ascend give
+ *   meaningless counts and no store outside the screen's arrays.
+ * rk_fastq_slot_screen: rk_fastq_slot_sample's steps on a block of raw FASTQ text, then the feed from the slot's packed bases, on
+ *   the slot's stream, which it synchronises.  *status != 0: the block is not four lines per record and NOTHING of it was added.
+ *   RK_ERR_ARG for a screen of another context.
+ * rk_screen_add_counts: adds counts[i] to c(values[i]) for ascending, distinct, non-zero values (RK_ERR_ARG otherwise); values that
+ *   are no key are ignored.  The route for abundance sketches made elsewhere (rk_sample_finish), and to counts of 2^32 and beyond.
+ * rk_screen_rows: out4 takes nref * 4 uint32.  rk_screen_rows_device: d_out4 the same on the device; launches rows, owner, rows on
+ *   hip_stream and does not synchronise it; calls on one screen share its owner array, so two of them must not be in flight at once.
+ *   RK_ERR_ARG for min_copies outside 1 .. 2^32 - 1.  The screen stays usable.
+ * rk_screen_counts: *keys_out (ascending) and *counts_out (the RAW 64-bit counts, not clamped), malloc'd (rk_free; never NULL on
+ *   success), *nkeys their length.
+ * rk_screen_stats: the caller sets out->struct_size as for rk_index_stats.  nkeys: distinct values of all rows; dir_buckets,
+ *   dir_shift: the directory (bucket of h = h >> dir_shift); nseq, nbases: sequences and bases fed (a refused FASTQ block adds none);
+ *   counted: windows that matched a key; injected: the sum of what rk_screen_add_counts was given, keys or not.
+ * rk_screen_reset: every count and total back to 0, the arrays kept.  Calls on one screen take turns.
+ * rk_screen_rows_host (host code, usable without a GPU; rk_screen_host.cpp): the definition on a counted set -- c_values ascending,
+ *   distinct and non-zero, c_counts parallel (uint64, clamped as above; a count of 0 is allowed and is never present) -- with the
+ *   checks of rk_screen_create on the rows and RK_ERR_ARG for a counted set that does not ascend.
+ * rk_screen_identity (host code): RK_ERR_ARG for NULL, k < 1 or shared > len. */
+typedef struct rk_screen rk_screen;
+typedef struct rk_screen_stats_t { uint32_t struct_size, nref, dir_shift, dir_buckets; uint64_t nkeys, nseq, nbases, counted, injected; } rk_screen_stats_t;
+int rk_screen_create(rk_ctx* ctx, const int* ks, int nks, const uint64_t* r_values, const uint64_t* r_offsets, int64_t nref, rk_screen** out);
+void rk_screen_destroy(rk_screen* screen);
+int rk_screen_reset(rk_screen* screen);
+int rk_screen_stats(rk_screen* screen, rk_screen_stats_t* out);
+int rk_screen_add_batch(rk_screen* screen, const uint8_t* bases, const uint64_t* offsets, int64_t nseq);
+int rk_screen_add_batch_device(rk_screen* screen, const void* d_bases, const void* d_offsets_u32, int64_t nseq, void* hip_stream);
+int rk_fastq_slot_screen(rk_fastq_slot* slot, uint64_t nbytes, rk_screen* screen, int32_t* status, int64_t* nrec);
+int rk_screen_add_counts(rk_screen* screen, const uint64_t* values, const uint32_t* counts, uint64_t n);
+int rk_screen_rows(rk_screen* screen, uint64_t min_copies, uint32_t* out4);
+int rk_screen_rows_device(rk_screen* screen, uint64_t min_copies, void* d_out4, void* hip_stream);
+int rk_screen_counts(rk_screen* screen, uint64_t** keys_out, uint64_t** counts_out, uint64_t* nkeys);
+int rk_screen_rows_host(const uint64_t* r_values, const uint64_t* r_offsets, int64_t nref, const uint64_t* c_values, const uint64_t* c_counts,
+                        uint64_t nc, uint64_t min_copies, uint32_t* out4);
+int rk_screen_identity(uint64_t shared, uint64_t len, int k, double* identity);
+
 #ifdef __cplusplus
 }
 #endif

@@ -309,6 +309,20 @@ _SIGS = {
     "rk_sample_bottom_state": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
     "rk_bottom_cut": (C.c_int, [C.c_void_p, _u64p, _u32p, C.c_uint64, C.c_int, C.c_uint64, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "rk_bottom_emit": (C.c_int, [_u64p, _u32p, C.c_uint64, C.c_int, C.c_uint64, C.c_int, _u64p, _i32p]),
+    # screen: include/rkmh_amd.h "SCREEN"
+    "rk_screen_create": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int, _u64p, _u64p, C.c_int64, C.POINTER(C.c_void_p)]),
+    "rk_screen_destroy": (None, [C.c_void_p]),
+    "rk_screen_reset": (C.c_int, [C.c_void_p]),
+    "rk_screen_stats": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "rk_screen_add_batch": (C.c_int, [C.c_void_p, _u8p, _u64p, C.c_int64]),
+    "rk_screen_add_batch_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "rk_fastq_slot_screen": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+    "rk_screen_add_counts": (C.c_int, [C.c_void_p, _u64p, _u32p, C.c_uint64]),
+    "rk_screen_rows": (C.c_int, [C.c_void_p, C.c_uint64, _u32p]),
+    "rk_screen_rows_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "rk_screen_counts": (C.c_int, [C.c_void_p, C.POINTER(_u64p), C.POINTER(_u64p), C.POINTER(C.c_uint64)]),
+    "rk_screen_rows_host": (C.c_int, [_u64p, _u64p, C.c_int64, _u64p, _u64p, C.c_uint64, C.c_uint64, _u32p]),
+    "rk_screen_identity": (C.c_int, [C.c_uint64, C.c_uint64, C.c_int, C.POINTER(C.c_double)]),
 }
 
 
@@ -666,6 +680,21 @@ class FastqSlot:
             n = int(text)
         st, nrec = C.c_int32(), C.c_int64()
         _chk(self._lib.rk_fastq_slot_sample(self._h, n, sample._h, C.byref(st), C.byref(nrec)))
+        return st.value, nrec.value
+
+    def screen(self, text, screen):
+        """A block into a Screen (rk_fastq_slot_screen): as sample() -> (status, records); status != 0: nothing of it was added."""
+        if isinstance(text, (bytes, bytearray)):
+            n = len(text)
+            if n > self.max_bytes:
+                raise ValueError("block larger than the slot")
+            if self.device_text:
+                raise ValueError("a device-text slot takes its block from set_source or load_bgzf: pass the number of bytes")
+            C.memmove(self._lib.rk_fastq_slot_text(self._h), bytes(text), n)
+        else:
+            n = int(text)
+        st, nrec = C.c_int32(), C.c_int64()
+        _chk(self._lib.rk_fastq_slot_screen(self._h, n, screen._h, C.byref(st), C.byref(nrec)))
         return st.value, nrec.value
 
     def set_source(self, address):
@@ -1281,6 +1310,112 @@ class ScaledIndex:
                                                 C.c_uint64(int(hit_cap)), C.c_void_p(d_labels_ptr), C.c_void_p(stream)))
 
 
+class ScreenStats(C.Structure):
+    """rk_screen_stats_t (rkmh_amd.h, "SCREEN")"""
+    _fields_ = [("struct_size", C.c_uint32), ("nref", C.c_uint32), ("dir_shift", C.c_uint32), ("dir_buckets", C.c_uint32), ("nkeys", C.c_uint64),
+                ("nseq", C.c_uint64), ("nbases", C.c_uint64), ("counted", C.c_uint64), ("injected", C.c_uint64)]
+
+
+def screen_rows_host(r_values, r_offsets, c_values, c_counts, min_copies=1):
+    """rk_screen_rows_host (host code, no GPU): the CSR reference rows against a counted set (values uint64 ascending, counts uint64)
+    -> uint32 [nref, 4]: (shared, median, owned shared, owned median) per reference."""
+    r_values, r_offsets = _csr(r_values, r_offsets)
+    c_values = np.ascontiguousarray(c_values, dtype=np.uint64)
+    c_counts = np.ascontiguousarray(c_counts, dtype=np.uint64)
+    if c_values.ndim != 1 or c_counts.shape != c_values.shape:
+        raise ValueError("values and counts must be one-dimensional and of one length")
+    if not 0 <= int(min_copies) < 1 << 64:
+        raise ValueError("min_copies outside the range of uint64")
+    nref = len(r_offsets) - 1
+    out = np.zeros((max(nref, 1), 4), dtype=np.uint32)
+    _chk(load_library().rk_screen_rows_host(_p(r_values, C.c_uint64), _p(r_offsets, C.c_uint64), nref, _p(c_values, C.c_uint64), _p(c_counts, C.c_uint64),
+                                            len(c_values), C.c_uint64(int(min_copies)), _p(out, C.c_uint32)))
+    return out[:max(nref, 0)]
+
+
+def screen_identity(shared, length, k):
+    """rk_screen_identity (host code): (shared / length)^(1 / k); 0 when nothing is shared, 1 when everything is."""
+    d = C.c_double()
+    _chk(load_library().rk_screen_identity(C.c_uint64(int(shared)), C.c_uint64(int(length)), int(k), C.byref(d)))
+    return float(d.value)
+
+
+class Screen:
+    """rk_screen: reference sketches (CSR rows, ascending, repeats allowed) resident as the keys of an inverted index, and one 64-bit
+    counter per key that the window hashes of the reads fed are counted into (Context.screen; rkmh_amd.h "SCREEN")."""
+
+    def __init__(self, ctx, ks, r_values, r_offsets):
+        self._ctx, self._lib = ctx, ctx._lib
+        ks = _ks(ks)
+        r_values, r_offsets = _csr(r_values, r_offsets)
+        self.nref = len(r_offsets) - 1
+        self._h = C.c_void_p()
+        _chk(self._lib.rk_screen_create(ctx._h, _p(ks, C.c_int), len(ks), _p(r_values, C.c_uint64), _p(r_offsets, C.c_uint64), self.nref, C.byref(self._h)))
+
+    def add(self, bases, offsets):
+        """rk_screen_add_batch: host bases (uint8) and uint64 offsets[n + 1]; refuses offsets that reach past the bases."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        if offsets.ndim != 1 or len(offsets) < 1:
+            raise ValueError("offsets must hold n + 1 entries")
+        bases = np.frombuffer(bases, dtype=np.uint8) if isinstance(bases, (bytes, bytearray)) else np.ascontiguousarray(bases, dtype=np.uint8)
+        if int(offsets.max()) > len(bases):
+            raise ValueError("offsets reach past the %d bases" % len(bases))
+        _chk(self._lib.rk_screen_add_batch(self._h, _p(bases, C.c_uint8), _p(offsets, C.c_uint64), len(offsets) - 1))
+
+    def add_device(self, d_bases_ptr, d_offsets_ptr, nseq, stream=None):
+        """rk_screen_add_batch_device: resident bases and uint32 offsets[nseq + 1]; asynchronous on the stream."""
+        _chk(self._lib.rk_screen_add_batch_device(self._h, C.c_void_p(d_bases_ptr), C.c_void_p(d_offsets_ptr), int(nseq), C.c_void_p(stream or 0)))
+
+    def add_counts(self, values, counts):
+        """rk_screen_add_counts: multiplicities (uint32) for ascending distinct values; values that are no key are ignored."""
+        values, counts = _value_counts(values, counts)
+        _chk(self._lib.rk_screen_add_counts(self._h, _p(values, C.c_uint64), _p(counts, C.c_uint32), len(values)))
+
+    def rows(self, min_copies=1):
+        """rk_screen_rows -> uint32 [nref, 4]: (shared, median, owned shared, owned median) per reference; the screen stays usable."""
+        if not 0 <= int(min_copies) < 1 << 64:
+            raise ValueError("min_copies outside the range of uint64")
+        out = np.zeros((max(self.nref, 1), 4), dtype=np.uint32)
+        _chk(self._lib.rk_screen_rows(self._h, C.c_uint64(int(min_copies)), _p(out, C.c_uint32)))
+        return out[:self.nref]
+
+    def rows_device(self, d_out4_ptr, min_copies=1, stream=None):
+        """rk_screen_rows_device: the same into nref * 4 uint32 on the device; runs on the stream and does not synchronise it."""
+        _chk(self._lib.rk_screen_rows_device(self._h, C.c_uint64(int(min_copies)), C.c_void_p(d_out4_ptr), C.c_void_p(stream or 0)))
+
+    def counts(self):
+        """rk_screen_counts -> (keys uint64 ascending, counts uint64: raw, not clamped)"""
+        ok, oc, n = _u64p(), _u64p(), C.c_uint64()
+        _chk(self._lib.rk_screen_counts(self._h, C.byref(ok), C.byref(oc), C.byref(n)))
+        m = int(n.value)
+        k = np.ctypeslib.as_array(ok, shape=(max(m, 1),))[:m].copy()
+        c = np.ctypeslib.as_array(oc, shape=(max(m, 1),))[:m].copy()
+        self._lib.rk_free(ok)
+        self._lib.rk_free(oc)
+        return k, c
+
+    def stats(self):
+        """-> dict(nref, nkeys, dir_shift, dir_buckets, nseq, nbases, counted, injected)"""
+        s = ScreenStats()
+        s.struct_size = C.sizeof(ScreenStats)
+        _chk(self._lib.rk_screen_stats(self._h, C.byref(s)))
+        return {k: int(getattr(s, k)) for k in ("nref", "nkeys", "dir_shift", "dir_buckets", "nseq", "nbases", "counted", "injected")}
+
+    def reset(self):
+        _chk(self._lib.rk_screen_reset(self._h))
+
+    def close(self):
+        if self._h:
+            self._lib.rk_screen_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def _abund(abund, values):
     """the abundances that lie parallel to `values`: uint32, one per value"""
     abund = np.ascontiguousarray(abund, dtype=np.uint32)
@@ -1662,6 +1797,10 @@ class Context:
     def sample(self, ks, max_hash, abund=False, pending_cap=0):
         """rk_sample_create: an empty Sample at (ks, this context's policy, max_hash); pending_cap 0 = the library's default."""
         return Sample(self, ks, max_hash, abund=abund, pending_cap=pending_cap)
+
+    def screen(self, ks, r_values, r_offsets):
+        """rk_screen_create -> Screen: the CSR reference rows resident, every count 0."""
+        return Screen(self, ks, r_values, r_offsets)
 
     def sample_bottom(self, ks, sketch_size, min_copies=1, pending_cap=0):
         """rk_sample_create_bottom: an empty bottom sample at (ks, this context's policy, sketch_size, min_copies)."""

@@ -17,6 +17,8 @@
 //   rk_multigather.hip  multigather: gather for a batch of queries through that index, counts kept up to date by integer atomics
 //   rk_cluster.hip   cluster: hook and compress on the hits of a search; the self-search of a collection, block by block, hits resident
 //   rk_sample.hip    the sample accumulator: one scaled sketch built on the device from reads fed batch by batch (fused hash-and-keep, folds)
+//   rk_tile_walk.hpp the walk over the windows of a resident read batch (tiles, read-start bitmap) that rk_sample.hip and rk_screen.hip share
+//   rk_screen.hip    screen: window hashes looked up among the keys of reference sketches and counted (64-bit atomics), rows and owners
 //   rk_bottom.hip    the cut of a bottom sample: where the bottom sketch_size of a sorted counted set ends (block weights, scan, the crossing block)
 #pragma once
 #include "../../include/rkmh_amd.h"
@@ -289,6 +291,12 @@ int sample_feed_device(rk_sample* s, const void* d_bases, const void* d_offs_u32
 // cnt and pre are the caller's scratch.  n < 2^31 * 1024 is the caller's to check.
 int bottom_cut_device(DevBuf& cnt, DevBuf& pre, const uint64_t* d_values, const uint32_t* d_counts, uint64_t n, uint32_t sketch_size, uint32_t min_copies,
                       bool distinct, uint64_t* d_state, hipStream_t st);
+}
+// the screen (rk_screen.hip) as the FASTQ slots feed it: the context it was made on; one resident batch, asynchronous on st
+struct rk_screen;
+namespace rk {
+rk_ctx* screen_ctx(const rk_screen* s);
+int screen_feed_device(rk_screen* s, const void* d_bases, const void* d_offs_u32, int64_t nseq, uint64_t bound_bases, hipStream_t st);
 }
 int counter_settle(const rk_counter* k);                                                                    // rk_counters.hip
 int set_references_impl(rk_ctx* c, const uint8_t* bases, const uint8_t* d_bases, const uint64_t* offsets, int nref, const int* ks, int nks, int S,

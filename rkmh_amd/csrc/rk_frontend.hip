@@ -294,7 +294,7 @@ extern "C" int rk_fastq_slot_load_gzip(rk_fastq_slot* s, rk_gzip* gz, int64_t ca
 // The two halves of rk_fastq_slot_classify, for callers that keep two slots per thread: submit() enqueues the upload and the
 // index / check / pack kernels and returns at once; finish() waits for them, launches the classification and collects the rows.
 // Between the two the caller can read its next block into its other slot -- the link and the GPU work while the host reads.
-// need_refs = false: rk_fastq_slot_sample alone, which looks nothing up in the reference index
+// need_refs = false: rk_fastq_slot_sample and rk_fastq_slot_screen, which look nothing up in the reference index
 static int slot_submit(rk_fastq_slot* s, uint64_t nbytes, bool for_output, bool need_refs = true) {
     if (!s || nbytes > s->max_bytes) return fail(RK_ERR_ARG, "bad arguments");
     rk_ctx* c = s->c;
@@ -449,6 +449,28 @@ extern "C" int rk_fastq_slot_sample(rk_fastq_slot* s, uint64_t nbytes, rk_sample
     if (nrec_out) *nrec_out = nrec;
     if (nrec == 0) return RK_OK;
     return sample_feed_device(sample, s->d.bases, s->d.out_off, nrec, nbytes, s->st);
+}
+
+// A block of raw FASTQ text into a screen (rk_screen.hip): rk_fastq_slot_sample's steps, then k_screen_count on the packed bases where
+// they lie.  *status != 0: the block is not four lines per record and NOTHING of it was added.  The context needs no references.
+extern "C" int rk_fastq_slot_screen(rk_fastq_slot* s, uint64_t nbytes, rk_screen* screen, int32_t* status, int64_t* nrec_out) {
+    if (!s || !screen || !status) return fail(RK_ERR_ARG, "bad arguments");
+    if (screen_ctx(screen) != s->c) return fail(RK_ERR_ARG, "the screen belongs to another context");
+    *status = 0;
+    if (nrec_out) *nrec_out = 0;
+    RKCHK(slot_submit(s, nbytes, false, false));
+    s->submitted = false;
+    if (nbytes == 0) return RK_OK;
+    RKCHK(set_dev(s->c));
+    uint32_t* info = s->h_info.as<uint32_t>();
+    HIPCHK(hipEventSynchronize(s->ev));
+    if (info[0] != 0) { *status = (int32_t)info[0]; return RK_OK; }
+    const int64_t nrec = (int64_t)info[1];
+    if (nrec_out) *nrec_out = nrec;
+    if (nrec == 0) return RK_OK;
+    RKCHK(screen_feed_device(screen, s->d.bases, s->d.out_off, nrec, nbytes, s->st));
+    HIPCHK(hipStreamSynchronize(s->st)); // the slot's text and bases may be written again
+    return RK_OK;
 }
 
 extern "C" int rk_fastq_slot_classify(rk_fastq_slot* s, uint64_t nbytes, rk_fastq_result* res) {

@@ -5,6 +5,7 @@
 // -- unites them with it.  The union over all reads is therefore taken on the device; the host sees a cursor per feed and the
 // finished arrays.  Semantics, sizes and measurements: DESIGN.md section 20.
 #include "rk_sets.hpp"
+#include "rk_tile_walk.hpp"
 
 struct rk_sample {
     rk_ctx* ctx = nullptr; // compared and used while feeding; destroy does not follow it
@@ -37,27 +38,11 @@ struct rk_sample {
 
 namespace {
 
-constexpr int SK_T = 256;
+constexpr int SK_T = TW_T;                                              // the workgroup of the tile walk (rk_tile_walk.hpp)
 constexpr int SK_STAGE = 1024;                                         // kept values a workgroup holds back in LDS
-constexpr int SK_BND_DW = (HASH_TILE_WIN + MAX_K + 2 + 31) / 32 + 2;   // the read-start bitmap of a tile (+ the word no_boundary reads ahead)
-constexpr uint32_t SK_BND_BITS = (uint32_t)(SK_BND_DW - 2) * 32u;
 constexpr uint64_t SK_DEFAULT_PENDING = (uint64_t)1 << 22;             // values (32 MB): DESIGN.md section 20
 constexpr uint64_t SK_PIECE_BASES = (uint64_t)64 << 20;                // rk_sample_add_batch uploads pieces of about this many bases
 constexpr uint32_t SK_FIRST_READS = 4096;                              // a bottom sample before its first cut: reads of the first sub-batch, doubling
-
-// bits [bit, bit + left) of the bitmap all zero?  (window_valid's walk, on the read-start bitmap)
-__device__ __forceinline__ bool no_boundary(const uint32_t* bnd, uint32_t bit, int left) {
-    uint32_t idx = bit >> 5;
-    const uint32_t sh = bit & 31;
-    uint32_t lo = bnd[idx], acc = 0;
-    while (left > 0) {
-        const uint32_t hi = bnd[idx + 1];
-        const uint32_t x = __builtin_amdgcn_alignbit(hi, lo, sh);
-        acc |= x & (left >= 32 ? 0xffffffffu : ((1u << left) - 1u));
-        lo = hi; ++idx; left -= 32;
-    }
-    return acc == 0;
-}
 
 // the workgroup's staged values leave for the pending array: one 64-bit atomicAdd on the cursor says where; the store happens only
 // when all of them fit below cap, the cursor advances either way.  Called by all threads with the same m (a register of each, never
@@ -73,17 +58,15 @@ __device__ __forceinline__ void flush_stage(const uint64_t* stage, uint32_t m, u
     __syncthreads(); // stage[] and flush_at may be written again
 }
 
-// The bases of a batch, offs[0] .. offs[n], as ONE piece cut into tiles of HASH_TILE_WIN window positions (grid-stride).  A tile
-// stages its positions and the kmax - 1 bases behind them, marks the read starts that fall into it, and hashes position p at every
-// k of the list that this instantiation serves (KT = 16: k = 16; KT = 0: every other k).  p is a window of its read when no read
-// start lies in (p, p + k - 1 + drop_last_window]: the read then holds k bases from p on, and one more where the policy drops the
-// last window.  offs[n], the end of the last read, is a start like the others.
+// The windows of a resident batch (walk_tiles, rk_tile_walk.hpp: the bases as one piece cut into tiles, read starts in a bitmap, every
+// window hashed at the k this instantiation serves); the hashes 0 < h <= max_hash are compacted with wave ballots into stage[] and leave
+// for the pending array whenever fewer than SK_T places are left there.
 template <int KT>
 __global__ __launch_bounds__(SK_T) void k_sample_keep(const uint8_t* __restrict__ bases, const uint32_t* __restrict__ offs, uint32_t n, KsArr ks, int kmax,
                                                       uint64_t max_hash, DevPolicy pol, uint64_t* __restrict__ pend, uint64_t cap,
                                                       unsigned long long* __restrict__ state, int add_totals) {
     __shared__ __attribute__((aligned(16))) uint32_t lds[stage_lds_dwords(HASH_TILE_MAXB)];
-    __shared__ uint32_t bnd[SK_BND_DW];
+    __shared__ uint32_t bnd[TW_BND_DW];
     __shared__ uint64_t stage[SK_STAGE];
     __shared__ uint64_t flush_at;
     __shared__ uint32_t wcnt[2][SK_T / 64]; // kept per wave in this round; two sets in turn, so that a wave a round ahead writes the other one
@@ -93,61 +76,29 @@ __global__ __launch_bounds__(SK_T) void k_sample_keep(const uint8_t* __restrict_
         atomicAdd(&state[2], (unsigned long long)(end > first ? end - first : 0u));
     }
     if (end <= first) return;
-    const uint32_t total = end - first;
-    const uint32_t ntiles = (uint32_t)(((uint64_t)total + HASH_TILE_WIN - 1) / HASH_TILE_WIN);
     const uint32_t wave = threadIdx.x >> 6;
     uint32_t nstage = 0, par = 0; // values waiting in stage[], the set of wcnt in turn: the same in every thread
-    for (uint32_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        __syncthreads(); // the readers of the tile before are done
-        const uint32_t a = first + tile * (uint32_t)HASH_TILE_WIN; // below `end`
-        const uint32_t left = end - a;
-        const uint32_t nb = min(left, (uint32_t)(HASH_TILE_WIN + kmax - 1));
-        const uint32_t nwin = min(left, (uint32_t)HASH_TILE_WIN);
-        const Staged s = stage_piece(bases, (uint64_t)a, nb, lds, HASH_TILE_MAXB, threadIdx.x, SK_T, [] { __syncthreads(); });
-        for (uint32_t i = threadIdx.x; i < (uint32_t)SK_BND_DW; i += SK_T) bnd[i] = 0;
+    walk_tiles<KT>(bases, offs, n, first, end, ks, kmax, pol, lds, bnd, [&](uint64_t h) {
+        const bool keep = h != 0 && h <= max_hash;
+        const uint64_t bal = __ballot(keep);
+        if ((threadIdx.x & 63) == 0) wcnt[par][wave] = (uint32_t)__popcll(bal);
         __syncthreads();
-        // the first read start behind the tile's first position: one binary search; the ones after it are marked while they fall into the bitmap
-        uint32_t lo = 0, hi = n + 1;
-        while (lo < hi) {
-            const uint32_t mid = lo + ((hi - lo) >> 1);
-            if (offs[mid] <= a) lo = mid + 1; else hi = mid;
+        uint32_t before = 0, all = 0;
+        for (uint32_t w = 0; w < SK_T / 64; ++w) {
+            const uint32_t cw = wcnt[par][w];
+            before += w < wave ? cw : 0u;
+            all += cw;
         }
-        for (uint32_t r = lo + threadIdx.x; r <= n; r += SK_T) {
-            const uint32_t rel = offs[r] - a; // (offsets that do not ascend: a wrapped difference ends the walk)
-            if (rel >= SK_BND_BITS) break;
-            atomicOr(&bnd[rel >> 5], 1u << (rel & 31u));
+        const uint32_t at = nstage + before + lanes_below(bal);
+        if (keep && at < (uint32_t)SK_STAGE) stage[at] = h; // (always: at most SK_STAGE - SK_T values wait when a round begins)
+        nstage += all;
+        par ^= 1u;
+        if (nstage > (uint32_t)(SK_STAGE - SK_T)) {
+            __syncthreads();
+            flush_stage(stage, nstage, &flush_at, pend, cap, state);
+            nstage = 0;
         }
-        __syncthreads();
-        for (int j = 0; j < ks.n; ++j) {
-            const int k = ks.k[j];
-            if (KT ? k != KT : k == 16) continue; // the other instantiation's
-            const int span = k - 1 + (pol.drop_last_window ? 1 : 0);
-            for (uint32_t i0 = 0; i0 < nwin; i0 += SK_T) { // whole workgroups
-                const uint32_t i = i0 + threadIdx.x;
-                uint64_t h = 0;
-                if (i < nwin && i + (uint32_t)k <= nb && no_boundary(bnd, i + 1, span)) h = canonical_window<KT>(s, i, k, pol);
-                const bool keep = h != 0 && h <= max_hash;
-                const uint64_t bal = __ballot(keep);
-                if ((threadIdx.x & 63) == 0) wcnt[par][wave] = (uint32_t)__popcll(bal);
-                __syncthreads();
-                uint32_t before = 0, all = 0;
-                for (uint32_t w = 0; w < SK_T / 64; ++w) {
-                    const uint32_t cw = wcnt[par][w];
-                    before += w < wave ? cw : 0u;
-                    all += cw;
-                }
-                const uint32_t at = nstage + before + lanes_below(bal);
-                if (keep && at < (uint32_t)SK_STAGE) stage[at] = h; // (always: at most SK_STAGE - SK_T values wait when a round begins)
-                nstage += all;
-                par ^= 1u;
-                if (nstage > (uint32_t)(SK_STAGE - SK_T)) {
-                    __syncthreads();
-                    flush_stage(stage, nstage, &flush_at, pend, cap, state);
-                    nstage = 0;
-                }
-            }
-        }
-    }
+    });
     __syncthreads();
     flush_stage(stage, nstage, &flush_at, pend, cap, state);
 }

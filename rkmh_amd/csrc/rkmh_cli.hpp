@@ -11,9 +11,11 @@
 //   rkmh_commands.cpp   the hashing policy and the help text; call and hash
 //   rkmh_sketch_json.cpp  the reader of the JSON sketches `sketch` writes (stream -R, dist, gather); stands alone
 //   rkmh_sketches.cpp   sketch sets: made from sequence files, written as JSON, loaded from -R / -Q files, cut to one scaled
-//   rkmh_sample.cpp     one scaled sketch per sequence file built on the device: the -g / one-query-per-file route of the sketch sets
+//   rkmh_sample.cpp     a sequence file into a device-side accumulator, never held whole (file_feed); one sketch per sequence file built so:
+//                       the -g / one-query-per-file route of the sketch sets
 //   rkmh_compare.cpp    sketch, dist, gather, multigather and manysearch
 //   rkmh_cluster.cpp    cluster
+//   rkmh_screen.cpp     screen: bottom-s reference sketches counted in whole read files
 //   rkmh_hpv16.cpp      hpv16
 #pragma once
 #include <getopt.h>
@@ -108,6 +110,13 @@ void sketch_files_scaled(rk_ctx* ctx, const std::vector<const char*>& files, con
 // gives the bases of its records, prints the timing line and leaves the sample empty again
 bool sample_on_device();
 struct SampleFed { const char* route = ""; int64_t blocks = 0; double t0 = 0, t1 = 0; }; // the route taken, its blocks, when the feed began and ended
+// what the records of a file go into: a block of raw FASTQ text in a slot (as rk_fastq_slot_sample takes it; *status != 0: nothing of it
+// was added), or a batch of the reader; both return the library's code.  file_feed is the driver, sample_file_feed its form for a sample
+struct FileSink {
+    std::function<int(rk_fastq_slot*, uint64_t, int32_t*, int64_t*)> slot_block;
+    std::function<int(const rk_seqset&)> host_batch;
+};
+SampleFed file_feed(rk_ctx* ctx, const FileSink& sink, const char* path);
 SampleFed sample_file_feed(rk_ctx* ctx, rk_sample* sample, const char* path);
 void sample_file_done(rk_sample* sample, const char* path, const SampleFed& fed, uint64_t* nbases);
 // --min-copies: a number of 1 .. 2^32 - 1; and its three refusals, which sketch and dist word alike (`command`: "sketch" / "dist")
@@ -171,6 +180,7 @@ int main_gather(int argc, char** argv);
 int main_multigather(int argc, char** argv);
 int main_manysearch(int argc, char** argv);
 int main_cluster(int argc, char** argv);
+int main_screen(int argc, char** argv);
 int main_hash(int argc, char** argv);
 int main_hpv16(int argc, char** argv);
 int main_pack(int argc, char** argv);

@@ -29,6 +29,7 @@ void print_help() {
             "  multigather         gather for many queries at once, through an inverted index of the references: the lines of gather, byte for byte\n"
             "  manysearch          search many scaled sketches against a collection through an inverted index: only the pairs that match, in dist's columns\n"
             "  cluster             group a collection of scaled sketches into single-linkage clusters at a Jaccard or max-containment threshold\n"
+            "  screen              which bottom-s reference sketches a read file contains: shared k-mers, identity and median multiplicity per reference\n"
             "  pack                write reads as a packed file (2 bits per base + names): stream|filter -F <file> classifies it without parsing\n"
             "Run a command without options for its help text.\n");
 }

@@ -39,6 +39,7 @@ int main(int argc, char** argv) {
     if (cmd == "multigather") return main_multigather(argc, argv);
     if (cmd == "manysearch") return main_manysearch(argc, argv);
     if (cmd == "cluster") return main_cluster(argc, argv);
+    if (cmd == "screen") return main_screen(argc, argv);
     if (cmd == "pack") return main_pack(argc, argv);
     if (cmd == "hpv16") return main_hpv16(argc, argv);
     print_help();

@@ -1,4 +1,5 @@
-// rkmh_sample.cpp -- ONE sketch per sequence file, built on the device (rk_sample_*, include/rkmh_amd.h "SAMPLE SKETCHES"): the
+// rkmh_sample.cpp -- the records of ONE sequence file into a device-side accumulator (file_feed over a FileSink: a sample here, the
+// screen of rkmh_screen.cpp), and on top of it ONE sketch per sequence file, built on the device (rk_sample_*, include/rkmh_amd.h "SAMPLE SKETCHES"): the
 // route of sketch_files_scaled for `sketch --scaled -g`, the query side of gather and multigather, and dist / manysearch with -g; and,
 // into a bottom sample ("BOTTOM SAMPLES"), the route of sketch_files for `sketch -g -s` and `dist -g -s`.
 // A file is never held whole: plain FASTQ text goes block by block through two alternating FASTQ slots (the next block is read while
@@ -27,13 +28,13 @@ enum LoadState { LOADED, EMPTY, REFUSED, END };
 struct Loaded { uint64_t nbytes = 0; int64_t at = 0, next = 0; LoadState state = END; };
 
 struct SampleFile {
-    rk_ctx* ctx; rk_sample* sample; const char* path;
+    rk_ctx* ctx; const FileSink& sink; const char* path;
     const char* route = "reader";
     int64_t blocks = 0, records = 0, handed_at = -1;
     rk_fastq_slot* slot[2] = {nullptr, nullptr};
     ~SampleFile() { for (rk_fastq_slot* s : slot) if (s) rk_fastq_slot_destroy(s); }
 
-    // the sequential reader, from byte `at` of the file's text on: bounded batches into the sample
+    // the sequential reader, from byte `at` of the file's text on: bounded batches into the sink
     void through_reader(uint64_t at) {
         rk_reader* rd = nullptr;
         CKE(at ? rk_reader_open_at(path, at, &rd) : rk_reader_open(path, &rd), path);
@@ -42,7 +43,7 @@ struct SampleFile {
             rk_seqset s;
             CKE(rk_reader_next(rd, 1 << 18, 1ull << 26, &s), path);
             if (s.nseq == 0) { rk_seqset_free(&s); break; }
-            CKE(rk_sample_add_batch(sample, s.bases, s.offsets, s.nseq), path);
+            CKE(sink.host_batch(s), path);
             records += s.nseq;
             rk_seqset_free(&s);
         }
@@ -65,7 +66,7 @@ struct SampleFile {
             if (ld.state == LOADED) {
                 int32_t status = 0;
                 int64_t n = 0;
-                if (rk_fastq_slot_sample(slot[cur], ld.nbytes, sample, &status, &n) != RK_OK) { const std::string e = rk_last_error(); next.wait(); fprintf(stderr, "rkmh: %s: %s\n", path, e.c_str()); fail_exit(); }
+                if (sink.slot_block(slot[cur], ld.nbytes, &status, &n) != RK_OK) { const std::string e = rk_last_error(); next.wait(); fprintf(stderr, "rkmh: %s: %s\n", path, e.c_str()); fail_exit(); }
                 if (status != 0) { next.wait(); return ld.at; } // nothing of the block was added
                 ++blocks; records += n;
             }
@@ -169,17 +170,24 @@ struct SampleFile {
 
 } // namespace
 
-// All records of `path` into the empty `sample`, by whichever route the file takes.  The caller then takes what it wants from the
-// sample (rk_sample_finish, rk_sample_finish_bottom) and ends with sample_file_done.
-SampleFed sample_file_feed(rk_ctx* ctx, rk_sample* sample, const char* path) {
+// All records of `path` into `sink`, by whichever route the file takes: raw FASTQ blocks through sink.slot_block, the reader's batches
+// through sink.host_batch.
+SampleFed file_feed(rk_ctx* ctx, const FileSink& sink, const char* path) {
     SampleFed fed;
     fed.t0 = now_s();
-    SampleFile F{ctx, sample, path};
+    SampleFile F{ctx, sink, path};
     F.run();
     fed.route = F.route;
     fed.blocks = F.blocks;
     fed.t1 = now_s();
     return fed;
+}
+// All records of `path` into the empty `sample`.  The caller then takes what it wants from the sample (rk_sample_finish,
+// rk_sample_finish_bottom) and ends with sample_file_done.
+SampleFed sample_file_feed(rk_ctx* ctx, rk_sample* sample, const char* path) {
+    const FileSink sink{[sample](rk_fastq_slot* slot, uint64_t nbytes, int32_t* status, int64_t* nrec) { return rk_fastq_slot_sample(slot, nbytes, sample, status, nrec); },
+                        [sample](const rk_seqset& s) { return rk_sample_add_batch(sample, s.bases, s.offsets, s.nseq); }};
+    return file_feed(ctx, sink, path);
 }
 // *nbases = the bases of the file's records; the timing line; `sample` is empty again
 void sample_file_done(rk_sample* sample, const char* path, const SampleFed& fed, uint64_t* nbases) {
